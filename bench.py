@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the north-star measurement: ca13 XL bounds query (count), 1/2/4/8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,9 +18,13 @@ ranks, file i belongs to rank i % N; the dataset is fixed, so this is strong sca
 
 One JSON line is printed by rank 0 (see the contract in the task statement).  `roofline` is computed
 from HIP events recorded around every launch of the dominant kernel inside the timed region, on the
-stream the kernel runs on; `cpu_baseline` times the oracle (the C restatement of the reference's
-`--optimized --parallel` loop; "port": the reference itself is Rust and cannot be built here) on a
-bounded sample of the same synthetic files on the host cores.
+stream the kernel runs on.  A plain run does only what that line's headline needs: set-up, warm-up, the
+timed steps and the check of their answers.  `--full` adds, after the timed region and at N = 1 only,
+`cpu_baseline` — the oracle (the C restatement of the reference's `--optimized --parallel` loop; "port":
+the reference itself is Rust and cannot be built here) timed on a bounded sample of the same synthetic
+files on the host cores, with the GPU's parity on that sample — and `secondary` (the host path and
+BASELINE configs 2-4).  `--dump-outputs DIR` writes the global match count of the last timed step to
+DIR/match_count.npy (float64, shape (1,)).
 """
 import argparse
 import importlib
@@ -266,9 +270,15 @@ def main():
     ap.add_argument("--points-per-file", type=int, default=163_000_000)
     ap.add_argument("--files", type=int, default=16)
     ap.add_argument("--query", type=str, default="ca13_XL")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baseline with its parity checks and the untimed measurements "
+                         "of configs 2-4 and of the host path (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the global match count of the last timed step to DIR/match_count.npy (float64)")
     ap.add_argument("--cpu-sample-points", type=int, default=20_000_000, help="points per file of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the untimed measurements of configs 2-4 and of the host path")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the untimed measurements of configs 2-4 and of the host path")
     ap.add_argument("--per-file-launch", action="store_true", help="one launch per file instead of one batched launch")
     ap.add_argument("--blocks-per-cu", type=int, default=0, help="tuning: persistent blocks per CU (0 = library default)")
     ap.add_argument("--sync-each-step", action="store_true",
@@ -279,6 +289,8 @@ def main():
                     help="multi-rank rehearsal on a single-GPU box: every rank uses device 0 and the gloo backend "
                          "(RCCL refuses two ranks on one device); numbers from such a run are not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries exactly ONE JSON line: native libraries (the RCCL banner, rocprof) write to fd 1,
     # so everything else is routed to stderr and the result is written to the saved descriptor.
@@ -428,6 +440,11 @@ def main():
     if any(g != expected for g in got):
         raise SystemExit(f"query answers differ inside the timed region: expected {expected}, got {sorted(set(got))}")
     matches = expected
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        # what a caller of the timed path receives: the global count of the last timed query (exact in float64)
+        np.save(os.path.join(args.dump_outputs, "match_count.npy"), np.array([got[-1]], dtype=np.float64))
     if use_dist:
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -516,8 +533,8 @@ def main():
             },
         }
 
-    # CPU baseline: rank 0 at N=1 only, bounded sample
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # CPU baseline (--full): rank 0 at N=1 only, bounded sample
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         oracle, threads, base, images, sample, cpu_count = cpu_baseline(specs_mod, bmin, bmax, args.cpu_sample_points, args.files)
         result["cpu_baseline"] = base
         # The TIMED kernel with a selective predicate: one untimed `--bounds ca13_L` query over the sample, resident in HBM,
@@ -563,8 +580,8 @@ def main():
         result["cpu_baseline"] = None
 
     # Everything else the driver should see, measured AFTER the timed region, outside `ms_per_step`:
-    # the PCIe-inclusive file path and BASELINE configs 2, 3, 4.  Rank 0 at N = 1 only.
-    if rank == 0 and world == 1 and not args.no_secondary:
+    # the PCIe-inclusive file path and BASELINE configs 2, 3, 4.  --full, rank 0 at N = 1 only.
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         t_sec = time.perf_counter()
         have_sample = not args.no_cpu_baseline
         result["secondary"] = secondary_measurements(

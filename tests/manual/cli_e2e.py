@@ -1,6 +1,6 @@
 """End-to-end wall clock of the `query` CLI (files on disk, page cache warm) next to the oracle CLI
 (the C restatement of the reference's `query --optimized --parallel`; the oracle CLI is single-threaded,
-the multi-threaded oracle number is bench.py's cpu_baseline).  Manual check kept under tests/ because it
+the multi-threaded oracle number is the cpu_baseline of bench.py --full).  Manual check kept under tests/ because it
 uses the oracle; the numbers go to DESIGN.md, not to the bench line.
 """
 import argparse

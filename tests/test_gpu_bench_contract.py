@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -30,8 +31,24 @@ def _check(line, n_gpus):
     return d
 
 
-def test_bench_json_contract_single_process():
+def test_bench_plain_run_is_lean_and_dumps_the_last_answer(tmp_path):
+    """Without --full the bench measures the headline only; --dump-outputs writes what the last timed step computed."""
+    out = tmp_path / "out"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--files", "4",
+                        "--points-per-file", "300007", "--dump-outputs", str(out)], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = _check(lines[0], 1)
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert d["cpu_baseline"] is None and "secondary" not in d and "parity_batched_on_sample" not in d
+    assert sorted(os.listdir(out)) == ["match_count.npy"]
+    a = np.load(out / "match_count.npy")
+    assert a.dtype == np.float64 and a.shape == (1,) and a[0] == d["matches"] == 4 * 300007
+
+
+def test_bench_json_contract_single_process():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--files", "4",
                         "--points-per-file", "300007", "--cpu-sample-points", "100003"], capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 # (the PMC passes first: the bench line quotes roofline.traffic from profiles/pmc_latest.json, and only when that file is from THIS kernel build)
 python tools/pmc_traffic.py --out $O/pmc_latest.json > $O/pmc_traffic.log 2>&1; echo "pmc rc $?"; tail -c 400 $O/pmc_traffic.log
 cp $O/pmc_latest.json profiles/pmc_latest.json
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc $?"; tail -c 600 $O/bench_n1.json
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc $?"; tail -c 600 $O/bench_n1.json
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err; echo "torchrun rc $?"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $O/bench_profiled.json 2> $O/bench_profiled.err; echo "rocprof bench rc $?"
