@@ -161,6 +161,7 @@ int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols_in, const 
             narrow = false;  // a world-space predicate (LAZER): the integer range of the matches is not known
         }
         const bool wide_t = !narrow;
+        ctx->grid_last_tuple_bytes = tuple_bytes(wide_t);
         // (a block's room: its 5120 tuples, plus the padding option — 16-byte units — that moves the blocks' phase in memory)
         const uint32_t block_bytes = P0_TILE * tuple_bytes(wide_t) + 16u * (uint32_t)ctx->grid_block_pad;
         const size_t tuple_room = (size_t)ntiles * block_bytes + 64;

@@ -253,6 +253,8 @@ void pcq_pool_clear(pcq_ctx *ctx) {
 
 int pcq_ensure_partials(pcq_ctx *ctx, size_t n) {
     if (n <= ctx->partials_cap) return PCQ_OK;
+    if (ctx->scratch_cap_words > 0 && n > (size_t)ctx->scratch_cap_words)  // (tests: an allocation that fails, before anything is freed)
+        return pcq_fail(PCQ_ERR_NOMEM, "scratch of %zu words is above the test cap of %lld", n, (long long)ctx->scratch_cap_words);
     // The old buffer may still be referenced by kernels enqueued on the context's or a caller's stream.
     if (ctx->d_partials) {
         PCQ_HIP(hipDeviceSynchronize());
@@ -381,6 +383,9 @@ extern "C" int pcq_set_option(pcq_ctx *ctx, const char *key, int64_t value) {
     } else if (!strcmp(key, "copy_threads")) {
         if (value < 1 || value > 64) return pcq_fail(PCQ_ERR_ARG, "copy_threads must be 1..64");
         ctx->copy_threads = (int)value;
+    } else if (!strcmp(key, "scratch_cap_words")) {
+        if (value < 0) return pcq_fail(PCQ_ERR_ARG, "scratch_cap_words must be >= 0");
+        ctx->scratch_cap_words = value;
     } else if (!strcmp(key, "chunk_points")) {
         if (value < 4) return pcq_fail(PCQ_ERR_ARG, "chunk_points must be >= 4");
         ctx->chunk_points = (uint64_t)value;
@@ -416,6 +421,9 @@ extern "C" int pcq_get_option(pcq_ctx *ctx, const char *key, int64_t *value) {
     else if (!strcmp(key, "emit_sparse_max")) *value = ctx->emit_sparse_max;
     else if (!strcmp(key, "grid_deferred")) *value = ctx->grid_deferred;
     else if (!strcmp(key, "grid_last_tuples")) *value = ctx->grid_last_tuples;
+    else if (!strcmp(key, "grid_last_tuple_bytes")) *value = ctx->grid_last_tuple_bytes;
+    else if (!strcmp(key, "scratch_cap_words")) *value = ctx->scratch_cap_words;
+    else if (!strcmp(key, "emit_park_fallbacks")) *value = ctx->emit_park_fallbacks;
     else if (!strcmp(key, "grid_folds")) *value = ctx->grid_folds;
     else if (!strcmp(key, "grid_level2")) *value = ctx->grid_level2;
     else if (!strcmp(key, "grid_refolds")) *value = ctx->grid_refolds;

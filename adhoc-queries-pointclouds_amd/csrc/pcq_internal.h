@@ -180,6 +180,9 @@ struct pcq_ctx {
     int grid_block_pad = 0;             // option: 16-byte units between the end of a tile's block of tuples and the next block
     int grid_tuple16 = 1;               // option (tests): 0 = every scan writes 24-byte tuples (the form a 16-byte tuple falls back to), 2 = 16-byte tuples without the second level's selector
     int64_t grid_last_tuples = 0;       // diagnostics: tuples the last fold found pending (after pass 0's own fold)
+    int64_t grid_last_tuple_bytes = 0;  // diagnostics: bytes per tuple (16 or 24) of the last grid scan's run
+    int64_t scratch_cap_words = 0;      // option (tests): > 0 = pcq_ensure_partials fails (PCQ_ERR_NOMEM) on a request above this many words
+    int64_t emit_park_fallbacks = 0;    // diagnostics: buffer scans whose emit found no room for the parked matches (park_max dropped to 0)
     // options
     int grid_blocks_per_cu = 2;   // persistent blocks per CU of the generic (strided) count kernels and the chunk index
 #ifdef PCQ_LAB                    // libpcq_lab.so only: the kernel shapes of csrc/lab/scan_count_lab.hip

@@ -505,6 +505,7 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     if (rc && park_max) {  // no room for the parked matches (a sixth of the input): the thin tiles are read a second time instead
         (void)hipGetLastError();
         park_max = 0;
+        ctx->emit_park_fallbacks++;
         rc = pcq_ensure_partials(ctx, base_words + 2);
     }
     if (rc) return rc;
