@@ -12,7 +12,11 @@
 //     mask-algebra tile kernel as K1 (scan_count.hip).
 //   * class: the first class scan writes a 256-bin histogram per 65536-point chunk; later class
 //     counts are sums of one bin per chunk and read no classification bytes at all.
-// Results are identical to the unindexed scans (tests/test_gpu_index.py).  The index never takes part
+//   * buffer collectors (the records of the matches): the index is built the same way (boxes or histograms alone), then the
+//     emit of scan_generic.hip runs with its count pass taking each 2048-point tile's state from the index first
+//     (k_tile_counts with IDX): disjoint tiles and contained tiles are not read there, disjoint ones not by the emit either.
+//     The statistics of such a scan are classified from the index when they are asked for (k_index_emit_stats).
+// Results are identical to the unindexed scans (tests/test_gpu_index.py, tests/test_gpu_index_points.py).  The index never takes part
 // in bench.py: skipping work inside the timed region would invalidate the north-star measurement.
 #include <new>
 
@@ -241,7 +245,35 @@ __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restri
     if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
 }
 
+// Statistics of an indexed buffer scan in index-chunk units: stats[0..2] += chunks disjoint from the predicate (not read by
+// the count pass) / contained (not read by the count pass) / straddling (read) — the classification k_tile_counts<.., IDX> took
+// its tile states from.  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
+__global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__restrict__ boxes, const uint32_t *__restrict__ hist, uint64_t nchunks,
+                                                            uint64_t n, DevPred pred, unsigned long long *__restrict__ stats) {
+    uint32_t k[3] = {0, 0, 0};
+    for (uint64_t ch = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; ch < nchunks; ch += (uint64_t)gridDim.x * BLOCK) {
+        int st;
+        if (boxes) {
+            const ChunkBox cb = boxes[ch];
+            st = index_box_state(cb.mn, cb.mx, pred);
+        } else {
+            const uint64_t first = ch * CLASS_CHUNK;
+            st = index_class_state(hist[ch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK);
+        }
+        k[0] += st == CHUNK_NONE, k[1] += st == CHUNK_ALL, k[2] += st == CHUNK_SCAN;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        uint32_t v = k[a];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&stats[a], (unsigned long long)v);
+    }
+}
+
 }  // namespace
+static_assert(sizeof(ChunkBox) == 6 * sizeof(int32_t) && CHUNK_POINTS == INDEX_BOUNDS_CHUNK && CLASS_CHUNK == INDEX_CLASS_CHUNK,
+              "EmitIndex reads the boxes as {mn[3], mx[3]}");
 
 struct pcq_index {
     pcq_ctx *ctx = nullptr;
@@ -257,6 +289,8 @@ struct pcq_index {
     unsigned long long *d_stats = nullptr;
     pcq_index_stats last = {};
     hipStream_t stats_stream = nullptr;  // non-null: `last` must be completed from d_stats (fetched lazily)
+    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds count) · 1 / 2: a bounds / class buffer scan,
+    DevPred stats_pred = {};             //    classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
 };
 
 extern "C" int pcq_index_new(pcq_ctx *ctx, pcq_index **out) {
@@ -291,6 +325,15 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     PCQ_ON_DEVICE_OF_CTX(ix->ctx);
     if (ix->stats_stream) {  // the counters of the last indexed bounds scan are still on the device
         unsigned long long h[3] = {0, 0, 0};
+        if (ix->stats_kind) {
+            const uint64_t nch = ix->stats_kind == 1 ? ix->nchunks : ix->ncchunks;
+            const int grid = (int)((nch + BLOCK - 1) / BLOCK < (uint64_t)ix->ctx->num_cus ? (nch + BLOCK - 1) / BLOCK : (uint64_t)ix->ctx->num_cus);
+            PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), ix->stats_stream));
+            if (grid > 0)
+                hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream, ix->stats_kind == 1 ? ix->d_boxes : nullptr,
+                                   ix->stats_kind == 2 ? ix->d_hist : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
+            PCQ_HIP(hipGetLastError());
+        }
         PCQ_HIP(hipStreamSynchronize(ix->stats_stream));
         PCQ_HIP(hipMemcpy(h, ix->d_stats, sizeof h, hipMemcpyDeviceToHost));
         ix->last.skipped = h[0];
@@ -302,11 +345,84 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     return PCQ_OK;
 }
 
+// A buffer collector: the emit's count pass takes each tile's state from the index (scan_generic.hip, k_tile_counts with IDX),
+// then the records are written as by pcq_scan_dev.  The first scan of a block builds the index first.
+static int scan_buffer_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix, pcq_collector *c, void *stream) {
+    int rc = pcq_validate_scan(cols, pred, c);
+    if (rc) return rc;
+    const bool bounds = pred->kind == PCQ_PRED_BOUNDS;
+    const bool covered = bounds ? cols->xyz_stride == 12 && ((uintptr_t)cols->xyz & 15) == 0 && cols->n >= CHUNK_POINTS
+                                : pred->kind == PCQ_PRED_CLASS && cols->cls && cols->cls_stride == 1 && cols->n > 0;
+    if (!covered) return pcq_scan_dev(ctx, cols, pred, c, stream);  // layout the index does not cover: plain scan
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    DevPred dp;
+    rc = pcq_make_dev_pred(pred, &dp);
+    if (rc) return rc;
+    rc = pcq_scratch_stream(ctx, s);
+    if (rc) return rc;
+    const int max_blocks = ctx->num_cus * 8;
+    EmitIndex eix = {};
+    bool built;
+    uint64_t chunks;
+    if (bounds) {
+        chunks = cols->n / CHUNK_POINTS;
+        built = ix->d_boxes && ix->xyz == cols->xyz && ix->n_xyz == cols->n;
+        if (!built) {
+            const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+            rc = pcq_ensure_partials(ctx, (size_t)grid);
+            if (rc) return rc;
+            if (ix->d_boxes) PCQ_HIP(hipFree(ix->d_boxes));
+            ix->d_boxes = nullptr;
+            PCQ_HIP(hipMalloc((void **)&ix->d_boxes, chunks * sizeof(ChunkBox)));
+            DevPred boxes_only = dp;
+            boxes_only.empty = 1;  // the boxes alone: the emit below counts
+            hipLaunchKernelGGL(k_index_build_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), chunks, boxes_only,
+                               ix->d_boxes, ctx->d_partials);
+            PCQ_HIP(hipGetLastError());
+            ix->xyz = cols->xyz;
+            ix->n_xyz = cols->n;
+            ix->nchunks = chunks;
+        }
+        eix.boxes = reinterpret_cast<const int32_t *>(ix->d_boxes);
+        eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
+    } else {
+        chunks = (cols->n + CLASS_CHUNK - 1) / CLASS_CHUNK;
+        built = ix->d_hist && ix->cls == cols->cls && ix->n_cls == cols->n;
+        if (!built) {
+            if (ix->d_hist) PCQ_HIP(hipFree(ix->d_hist));
+            ix->d_hist = nullptr;
+            PCQ_HIP(hipMalloc((void **)&ix->d_hist, chunks * 256 * sizeof(uint32_t)));
+            const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+            hipLaunchKernelGGL(k_index_build_class, dim3(grid), dim3(BLOCK), 0, s, (const uint8_t *)cols->cls, cols->n, chunks, ix->d_hist);
+            PCQ_HIP(hipGetLastError());
+            ix->cls = cols->cls;
+            ix->n_cls = cols->n;
+            ix->ncchunks = chunks;
+        }
+        eix.hist = ix->d_hist;
+        eix.covered_tiles = cols->n / EMIT_TILE_POINTS;  // whole tiles
+    }
+    ix->last = pcq_index_stats{};
+    ix->last.chunks = chunks;
+    if (!built) {  // the build read every chunk
+        ix->last.built = 1;
+        ix->last.scanned = chunks;
+        ix->stats_stream = nullptr;
+        ix->stats_kind = 0;
+    } else {
+        ix->stats_stream = s;  // classified and fetched by pcq_index_get_stats: nothing on the scan path
+        ix->stats_kind = bounds ? 1 : 2;
+        ix->stats_pred = dp;
+    }
+    return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+}
+
 extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
                                     pcq_collector *c, void *stream) {
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: null argument");
-    if (c->kind != COLL_COUNT) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count collectors only");
+    if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count and buffer collectors only");
+    if (c->kind == COLL_BUFFER) return scan_buffer_indexed(ctx, cols, pred, ix, c, stream);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     c->last_stream = s;
     DevPred dp;
@@ -345,6 +461,7 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
         hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
         PCQ_HIP(hipGetLastError());
         ix->stats_stream = built ? s : nullptr;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
+        ix->stats_kind = 0;
         if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned
             pcq_columns tail = *cols;
             tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
@@ -361,6 +478,7 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
     if (ncc == 0) return PCQ_OK;
     const bool built = ix->d_hist && ix->cls == cols->cls && ix->n_cls == cols->n;
     ix->stats_stream = nullptr;
+    ix->stats_kind = 0;
     ix->last = pcq_index_stats{};
     ix->last.chunks = ncc;
     if (!built) {

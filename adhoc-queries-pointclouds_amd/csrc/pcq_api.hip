@@ -763,7 +763,7 @@ extern "C" int pcq_collector_grid_params(const pcq_collector *c, uint64_t dims[3
 // ---------------------------------------------------------------------------------------------
 // scan over device-resident columns
 // ---------------------------------------------------------------------------------------------
-static int validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c) {
+int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c) {
     if (!cols || !pred || !c) return pcq_fail(PCQ_ERR_ARG, "scan: null argument");
     if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS && pred->kind != PCQ_PRED_BOUNDS_F64)
         return pcq_fail(PCQ_ERR_ARG, "scan: bad predicate kind %d", pred->kind);
@@ -856,8 +856,8 @@ int pcq_scratch_stream(pcq_ctx *ctx, hipStream_t s) {
     return PCQ_OK;
 }
 
-static int scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, hipStream_t s) {
-    int rc = validate_scan(cols, pred, c);
+int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, hipStream_t s, const EmitIndex *ix) {
+    int rc = pcq_validate_scan(cols, pred, c);
     if (rc) return rc;
     if (cols->n == 0) return PCQ_OK;
     rc = pcq_scratch_stream(ctx, s);
@@ -874,7 +874,7 @@ static int scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predic
         if (dp.kind == PCQ_PRED_BOUNDS && dp.empty) return PCQ_OK;
         rc = buffer_reserve(c, dc.n, s);
         if (rc) return rc;
-        rc = pcq_launch_emit_points(ctx, dc, dp, c->d_points, c->d_count + c->count_slot, c->d_count + (c->count_slot ^ 1), s);  // asynchronous: one pass, no count first
+        rc = pcq_launch_emit_points(ctx, dc, dp, c->d_points, c->d_count + c->count_slot, c->d_count + (c->count_slot ^ 1), s, ix);  // asynchronous: one pass, no count first
         if (rc) return rc;
         c->count_slot ^= 1;
         c->n_upper += dc.n;
@@ -891,7 +891,7 @@ static int scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predic
 extern "C" int pcq_scan_dev(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, void *stream) {
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev: null context");
-    return scan_dev_impl(ctx, cols, pred, c, stream ? (hipStream_t)stream : ctx->stream);
+    return pcq_scan_dev_impl(ctx, cols, pred, c, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1050,7 +1050,7 @@ static int fetch(pcq_ctx *ctx, int fd, uint8_t *dst, const uint8_t *src, size_t 
 
 static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, bool wait) {
     if (!ctx) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_host: null context");
-    int rc = validate_scan(cols, pred, c);
+    int rc = pcq_validate_scan(cols, pred, c);
     if (rc) return rc;
     if (cols->n == 0) return PCQ_OK;
     PCQ_HIP(hipSetDevice(ctx->device));
@@ -1219,7 +1219,7 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
         }
         dcols.n = cnt;
         dcols.first_index = cols->first_index + first;
-        rc = scan_dev_impl(ctx, &dcols, pred, c, s);
+        rc = pcq_scan_dev_impl(ctx, &dcols, pred, c, s);
         if (rc) return fail(rc);
         PCQ_HIP_OR_FAIL(hipEventRecord(ctx->consumed[b], s));
         ctx->stage_busy[b] = true;

@@ -111,6 +111,32 @@ struct DevGrid {
     uint32_t keys_wide;   // 1: a key can have more than 32 bits (grid_common.h cell_hash)
 };
 
+// The chunk index (chunk_index.hip) as the buffer emit's count pass sees it: the state of the index chunk a tile of 2048
+// points lies in.  Bounds chunks hold 4096 points (tiles 2c, 2c + 1), class chunks 65536 (tiles 32c .. 32c + 31); both start
+// at point 0.  Tiles from `covered_tiles` on (the ragged tail) are always counted.
+struct EmitIndex {
+    const int32_t *boxes;    // bounds: {mn[3], mx[3]} per chunk (integer AABB), or nullptr
+    const uint32_t *hist;    // class: 256 bins per chunk, or nullptr
+    uint64_t covered_tiles;
+};
+enum { CHUNK_SCAN = 0, CHUNK_NONE = 1, CHUNK_ALL = 2 };  // straddling: read it · disjoint: no match · contained: every point matches
+constexpr uint64_t INDEX_BOUNDS_CHUNK = 4096, INDEX_CLASS_CHUNK = 65536, EMIT_TILE_POINTS = 2048;
+// A chunk's integer AABB against the predicate's inclusive i64 box [lo, lo + width] (pred.empty: nothing matches).
+__device__ __forceinline__ int index_box_state(const int32_t (&mn)[3], const int32_t (&mx)[3], const DevPred &pr) {
+    bool disjoint = pr.empty != 0, inside = !pr.empty;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const int64_t hi = (int64_t)pr.lo[a] + (int64_t)pr.width[a];
+        disjoint |= (int64_t)mx[a] < (int64_t)pr.lo[a] || (int64_t)mn[a] > hi;
+        inside &= (int64_t)mn[a] >= (int64_t)pr.lo[a] && (int64_t)mx[a] <= hi;
+    }
+    return disjoint ? CHUNK_NONE : (inside ? CHUNK_ALL : CHUNK_SCAN);
+}
+// A class chunk of `points` points whose histogram bin for the predicate's class is `bin`.
+__device__ __forceinline__ int index_class_state(uint32_t bin, uint64_t points) {
+    return bin == 0 ? CHUNK_NONE : ((uint64_t)bin == points ? CHUNK_ALL : CHUNK_SCAN);
+}
+
 constexpr uint64_t PCQ_EMPTY_KEY = ~0ull;
 constexpr uint64_t PCQ_NO_INDEX = ~0ull;
 
@@ -249,8 +275,13 @@ int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8
 // scan_generic.hip
 int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred,
                              uint64_t *d_count, hipStream_t s);
+// ix (optional): the count pass takes each tile's state from the chunk index first (bounds or class predicates)
 int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint8_t *d_out31, const uint64_t *d_npoints_in,
-                           uint64_t *d_npoints_out, hipStream_t s);
+                           uint64_t *d_npoints_out, hipStream_t s, const EmitIndex *ix = nullptr);
+// pcq_api.hip: pcq_scan_dev on stream s; ix (optional) is handed to the buffer collector's emit
+int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c);
+int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, hipStream_t s,
+                      const EmitIndex *ix = nullptr);
 // grid_host.hip (kernels: grid_pass0.hip, grid_dir.hip, grid_level2.hip, grid_fold.hip, grid_finish.hip; shared: grid_common.h)
 int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols, const DevPred &pred, hipStream_t s);
 void pcq_grid_release(pcq_collector *c);

@@ -71,6 +71,7 @@ __global__ __launch_bounds__(BLOCK) void k_sum_partials(const uint64_t *__restri
 // neighbouring blocks never write the same 16-byte chunk.
 constexpr int EMIT_ITEMS = 8;                                   // points per thread and tile: 2048-point tiles
 constexpr int EMIT_TILE = BLOCK * EMIT_ITEMS;
+static_assert(EMIT_TILE == EMIT_TILE_POINTS && INDEX_BOUNDS_CHUNK == 2 * EMIT_TILE && INDEX_CLASS_CHUNK == 32 * EMIT_TILE, "tile <-> index chunk");
 constexpr int FLUSH_ITEMS = 4;                                  // input rows of 256 points per LDS flush
 constexpr int STAGE_BYTES = FLUSH_ITEMS * BLOCK * 31 + 16;      // 31,760 B: five blocks per CU fit in LDS
 constexpr int STAGE_WORDS = (STAGE_BYTES + 3) / 4 + 9;          // + the dwords a record's last OR may touch
@@ -157,12 +158,39 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
 // predicates on the positions (park == nullptr otherwise): a class predicate would have to read positions it does not need.
 // RGB: the file has a colour block — a second word {red | green << 16, blue, 0, 0} per match, the colours of the tile asked for
 // with the class bytes.
-template <int KIND, bool RGB>
+// IDX (the chunk index, chunk_index.hip): 0 = none; INDEX_BOUNDS / INDEX_CLASS = the tile first takes the state of its index
+// chunk — block-uniform, from one box or one histogram bin, in front of every other load.  A disjoint tile leaves count 0 and
+// empty match bits, a contained one 2048 and full bits (only whole tiles are covered), neither reads a position or class byte
+// nor parks anything; the emit pass then skips the first and builds the records of the second as always.  Every other tile is
+// counted as without the index.
+enum { INDEX_NONE = 0, INDEX_BOUNDS = 1, INDEX_CLASS = 2 };
+template <int IDX>
+__device__ __forceinline__ int tile_index_state(const EmitIndex &ix, const DevPred &pr, uint64_t n, uint64_t tile) {
+    if (tile >= ix.covered_tiles) return CHUNK_SCAN;
+    if (IDX == INDEX_BOUNDS) {
+        const int32_t *b = ix.boxes + (tile >> 1) * 6;  // 4096-point chunk = tiles 2c, 2c + 1
+        const int32_t mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
+        return index_box_state(mn, mx, pr);
+    }
+    const uint64_t ch = tile >> 5, first = ch * INDEX_CLASS_CHUNK;  // 65536-point chunk = tiles 32c .. 32c + 31
+    return index_class_state(ix.hist[ch * 256 + (pr.cls & 255u)], n - first < INDEX_CLASS_CHUNK ? n - first : INDEX_CLASS_CHUNK);
+}
+
+template <int KIND, bool RGB, int IDX = INDEX_NONE>
 __global__ __launch_bounds__(BLOCK) void k_tile_counts(DevCols c, DevPred pr, uint64_t *__restrict__ counts, uint64_t *__restrict__ bits,
-                                                       uint4 *__restrict__ park, uint32_t park_max) {
+                                                       uint4 *__restrict__ park, uint32_t park_max, EmitIndex ix) {
     __shared__ uint32_t s_w[WAVES];
     __shared__ uint64_t s_bits[EMIT_ITEMS * WAVES];
     __shared__ uint32_t s_front[EMIT_ITEMS * WAVES];
+    if (IDX != INDEX_NONE) {
+        const int st = tile_index_state<IDX>(ix, pr, c.n, blockIdx.x);
+        if (st != CHUNK_SCAN) {
+            const bool all = st == CHUNK_ALL;
+            if (threadIdx.x < EMIT_ITEMS * WAVES) bits[(uint64_t)blockIdx.x * (EMIT_ITEMS * WAVES) + threadIdx.x] = all ? ~0ull : 0ull;
+            if (threadIdx.x == 0) counts[blockIdx.x] = all ? (uint64_t)EMIT_TILE : 0ull;
+            return;
+        }
+    }
     TileIn<KIND, false> T;
     tile_load_and_test<KIND, false, false>(c, pr, (uint64_t)blockIdx.x * EMIT_TILE, T);
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -492,8 +520,9 @@ int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &p
 
 // Appends the matches of `cols` to the packed records at d_out31, in file order.  *d_npoints_in (device) is the number
 // of records in front of them; the emit stores the new count in *d_npoints_out.  Asynchronous: five launches, no copy.
+// ix: the count pass consults the chunk index (k_tile_counts with IDX); the records are the same, byte for byte.
 int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint8_t *d_out31, const uint64_t *d_npoints_in,
-                           uint64_t *d_npoints_out, hipStream_t s) {
+                           uint64_t *d_npoints_out, hipStream_t s, const EmitIndex *ix) {
     if (cols.n == 0) return PCQ_OK;
     const uint64_t ntiles = (cols.n + EMIT_TILE - 1) / EMIT_TILE;
     const uint64_t npieces = (ntiles + SCAN_PIECE - 1) / SCAN_PIECE;
@@ -514,11 +543,16 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     const uint32_t sparse_max = ctx->emit_sparse_max < 0 ? 0u : (uint32_t)ctx->emit_sparse_max;
     const dim3 g((unsigned)ntiles), b(BLOCK);
     const bool park_rgb = park_max && cols.rgb;
-    if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max);
-    else if (pred.kind == PCQ_PRED_BOUNDS && park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max);
-    else if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max);
-    else if (park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max);
-    else hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max);
+    if (ix && pred.kind == PCQ_PRED_BOUNDS && ix->boxes) {
+        if (park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, true, INDEX_BOUNDS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
+        else hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false, INDEX_BOUNDS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
+    } else if (ix && pred.kind == PCQ_PRED_CLASS && ix->hist)
+        hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false, INDEX_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
+    else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (pred.kind == PCQ_PRED_BOUNDS && park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     hipLaunchKernelGGL(k_scan_piece_sums, dim3((unsigned)npieces), dim3(1024), 0, s, counts, (uint32_t)ntiles, pieces);
     hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, pieces, (uint32_t)npieces);
     hipLaunchKernelGGL(k_scan_pieces, dim3((unsigned)npieces), dim3(1024), 0, s, counts, (uint32_t)ntiles, pieces, offsets);

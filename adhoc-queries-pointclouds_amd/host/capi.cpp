@@ -11,6 +11,7 @@ using namespace pcq;
 
 struct pcq_host_collector {
     std::unique_ptr<ResultCollector> c;
+    int device = -1;  // the device whose context the collector lives in
 };
 
 static thread_local std::string g_msg;
@@ -83,6 +84,7 @@ static int make_collector(int device, pcq_host_collector **out, F &&create) {
     Status st = thread_context(device, &ctx);
     if (!st.ok()) return done(st);
     auto hc = std::make_unique<pcq_host_collector>();
+    hc->device = device;
     st = create(ctx, nullptr, &hc->c);
     if (!st.ok()) return done(st);
     *out = hc.release();
@@ -213,20 +215,54 @@ extern "C" int pcq_query_simulate_schedule(const uint64_t *cost, size_t nfiles, 
 // ---- resident dataset -------------------------------------------------------------------------------------
 struct pcq_host_resident {
     std::unique_ptr<ResidentDataset> ds;
+    int device = -1;
 };
-extern "C" int pcq_query_resident_load(int device, const char *const *files, size_t nfiles, pcq_host_resident **out) {
+static int resident_load(int device, const char *const *files, size_t nfiles, pcq_host_resident **out, bool with_points) {
     if (!out || (!files && nfiles)) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     *out = nullptr;
+    for (size_t i = 0; i < nfiles; i++)
+        if (!files[i]) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     pcq_ctx *ctx = nullptr;
     Status st = thread_context(device, &ctx);
     if (!st.ok()) return done(st);
     std::vector<std::string> v;
     for (size_t i = 0; i < nfiles; i++) v.emplace_back(files[i]);
     auto h = std::make_unique<pcq_host_resident>();
-    st = ResidentDataset::load(ctx, v, &h->ds);
+    h->device = device;
+    st = ResidentDataset::load(ctx, v, &h->ds, with_points);
     if (!st.ok()) return done(st);
     *out = h.release();
     return PCQ_OK;
+}
+extern "C" int pcq_query_resident_load(int device, const char *const *files, size_t nfiles, pcq_host_resident **out) {
+    return resident_load(device, files, nfiles, out, false);
+}
+extern "C" int pcq_query_resident_load_points(int device, const char *const *files, size_t nfiles, pcq_host_resident **out) {
+    return resident_load(device, files, nfiles, out, true);
+}
+static Status resident_collector_ok(const pcq_host_resident *r, const pcq_host_collector *c) {
+    if (c->device != r->device)
+        return Status::Err(PCQ_ERR_ARG, "collector of device " + std::to_string(c->device) + ", resident dataset of device " + std::to_string(r->device));
+    return Status::Ok();
+}
+extern "C" int pcq_query_resident_search_bounds(pcq_host_resident *r, const double bmin[3], const double bmax[3], pcq_host_collector *c) {
+    if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);  // PCQ_ERR_PANIC for min > max, as pcq_query_search_file_bounds
+    if (!st.ok()) return done(st);
+    st = resident_collector_ok(r, c);
+    if (!st.ok()) return done(st);
+    return done(r->ds->search_bounds(b, *c->c));
+}
+extern "C" int pcq_query_resident_search_class(pcq_host_resident *r, uint8_t cls, pcq_host_collector *c) {
+    if (!r || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    Status st = resident_collector_ok(r, c);
+    if (!st.ok()) return done(st);
+    return done(r->ds->search_class(cls, *c->c));
+}
+extern "C" int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out) {
+    if (!r || !out) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    return done(r->ds->last_stats(out));
 }
 extern "C" int pcq_query_resident_free(pcq_host_resident *r) {
     delete r;

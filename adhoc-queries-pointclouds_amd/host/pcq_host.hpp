@@ -328,22 +328,33 @@ struct ResidentFile {
     std::string path;
     LasHeader header;
     void *xyz = nullptr, *cls = nullptr;  // device blocks
+    void *rgb = nullptr;                  // colour block (load with points, formats with colour)
+    pcq_index *index = nullptr;           // chunk index of the blocks (first search_* of the file)
 };
 class ResidentDataset {
 public:
     ~ResidentDataset();
     ResidentDataset(const ResidentDataset &) = delete;
     ResidentDataset &operator=(const ResidentDataset &) = delete;
-    static Status load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out);
+    // with_points: the colour blocks too, so that buffer and grid collectors can be served
+    static Status load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points = false);
     Status count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
+    // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
+    Status search_bounds(const AABB &bounds, ResultCollector &rc);
+    Status search_class(uint8_t cls, ResultCollector &rc);
+    // chunk-index statistics of the last search_*, summed over the files it scanned through the index
+    Status last_stats(pcq_index_stats *out);
     size_t files() const { return files_.size(); }
     uint64_t points() const { return points_; }
 
 private:
     ResidentDataset() = default;
     Status run(const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches);
+    Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     pcq_ctx *ctx_ = nullptr;
+    bool with_points_ = false;
+    std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
     uint64_t points_ = 0;

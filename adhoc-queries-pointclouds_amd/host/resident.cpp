@@ -6,6 +6,11 @@
 // pcq_scan_dev_count_batch: one segment per surviving file, the total added into one device counter.  A per-file launch
 // of the class kernel over one 163 MB block is launch-bound (5.0-5.7 TB/s, profiles/r01_k2_file_rate.log); the batched
 // launch reaches the streaming rate (7.1 TB/s) because 15 of 16 launch tails disappear.
+//
+// Point and density queries (search_bounds / search_class) are the per-file searches of search.cpp over the resident blocks,
+// file by file into one collector.  A count or buffer collector goes through each file's chunk index (pcq_scan_dev_indexed):
+// its first query of a kind builds the index, later ones read only the chunks that straddle the box.  A grid collector goes
+// through pcq_scan_dev; its pass 0 does not consult the index.
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -16,14 +21,18 @@ ResidentDataset::~ResidentDataset() {
     for (auto &f : files_) {
         if (f.xyz) pcq_device_free(ctx_, f.xyz);
         if (f.cls) pcq_device_free(ctx_, f.cls);
+        if (f.rgb) pcq_device_free(ctx_, f.rgb);
+        if (f.index) pcq_index_free(f.index);
     }
     if (counter_) pcq_device_free(ctx_, counter_);
 }
 
 // Loads the positions and classification blocks of every .last file (last.rs:68-90 for the offsets) into HBM.
-Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out) {
+// with_points: the colour block as well (last.rs:83-90), for the records of buffer and grid collectors.
+Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points) {
     auto ds = std::unique_ptr<ResidentDataset>(new ResidentDataset());
     ds->ctx_ = ctx;
+    ds->with_points_ = with_points;
     void *p = nullptr;
     Status st = Status::FromLib(pcq_device_alloc(ctx, 16, &p));
     if (!st.ok()) return st;
@@ -43,12 +52,18 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
         const uint64_t cls_block = otp + n * (fmt <= 5 ? 15 : 16);  // last.rs:69-81
         if (otp > file.size() || n * 12 > file.size() - otp || cls_block > file.size() || n > file.size() - cls_block)
             return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer");
+        const uint64_t col_in_point = fmt == 2 ? 20 : (fmt == 3 || fmt == 5 ? 28 : 0);  // last.rs:83-88
+        const uint64_t col_block = otp + n * col_in_point;
+        const bool colours = with_points && col_in_point;
+        if (colours && (col_block > file.size() || n * 6 > file.size() - col_block)) return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer");
         rf.path = path;
         if (n) {
             st = Status::FromLib(pcq_device_alloc(ctx, n * 12, &rf.xyz));
             if (st.ok()) st = Status::FromLib(pcq_device_alloc(ctx, n, &rf.cls));
+            if (st.ok() && colours) st = Status::FromLib(pcq_device_alloc(ctx, n * 6, &rf.rgb));
             if (st.ok()) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), otp, n * 12, rf.xyz));
             if (st.ok()) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), cls_block, n, rf.cls));
+            if (st.ok() && colours) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), col_block, n * 6, rf.rgb));
         }
         ds->files_.push_back(rf);
         if (!st.ok()) return st;
@@ -106,6 +121,77 @@ Status ResidentDataset::count_class(uint8_t cls, uint64_t *matches, uint64_t *po
     }
     if (points_scanned) *points_scanned = scanned;
     return run(cols, preds, matches);
+}
+
+// One file of search_bounds / search_class: execute_plan (search.cpp) with the resident blocks in place of the file.
+Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc) {
+    const uint64_t n = f.header.number_of_points;
+    pcq_columns c{};
+    c.xyz = f.xyz, c.xyz_stride = 12;  // last.rs:114-121
+    c.cls = f.cls, c.cls_stride = 1;   // :138-142
+    c.rgb = f.rgb, c.rgb_stride = 6;   // :145-153
+    c.n = n;
+    c.first_index = rc.next_index;
+    for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];  // :156-160
+    int r;
+    if (dynamic_cast<GridSampledCollector *>(&rc)) {
+        r = pcq_scan_dev(ctx_, &c, &pred, rc.handle(), nullptr);
+    } else {
+        if (!f.index) {
+            r = pcq_index_new(ctx_, &f.index);
+            if (r) return Status::FromLib(r);
+        }
+        r = pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
+        if (!r) last_indices_.push_back(f.index);
+    }
+    rc.next_index += n;
+    return Status::FromLib(r);
+}
+
+// search_last_file_by_bounds_optimized (last.rs:46-166) for every file: the header early-out (:92-94) skips a file without
+// moving the collector's file-order index, as the per-file search does.
+Status ResidentDataset::search_bounds(const AABB &bounds, ResultCollector &rc) {
+    if (!with_points_ && rc.has_points())
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
+    last_indices_.clear();
+    for (auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_BOUNDS;
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
+        Status st = scan(f, pred, rc);
+        if (!st.ok()) return st;
+    }
+    return Status::Ok();
+}
+
+// search_last_file_by_classification_optimized (last.rs:213-293) for every file: no file-level early-out.
+Status ResidentDataset::search_class(uint8_t cls, ResultCollector &rc) {
+    if (!with_points_ && rc.has_points())
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
+    last_indices_.clear();
+    for (auto &f : files_) {
+        if (f.header.number_of_points == 0) continue;
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_CLASS;
+        pred.cls = cls;  // :259-262 whole byte
+        Status st = scan(f, pred, rc);
+        if (!st.ok()) return st;
+    }
+    return Status::Ok();
+}
+
+Status ResidentDataset::last_stats(pcq_index_stats *out) {
+    *out = pcq_index_stats{};
+    for (pcq_index *ix : last_indices_) {
+        pcq_index_stats st;
+        const int r = pcq_index_get_stats(ix, &st);  // (waits for that file's scan)
+        if (r) return Status::FromLib(r);
+        out->chunks += st.chunks, out->skipped += st.skipped, out->whole += st.whole, out->scanned += st.scanned, out->built += st.built;
+    }
+    return Status::Ok();
 }
 
 }  // namespace pcq

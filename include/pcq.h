@@ -217,12 +217,21 @@ int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_pr
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step
- * (improvements.md:3-10), SURVEY.md §8f-3.  The first bounds (class) count scan of a file through
+ * (improvements.md:3-10), SURVEY.md §8f-3.  The first bounds (class) scan of a file through
  * pcq_scan_dev_indexed also records the integer AABB of every 4096-point chunk (a 256-bin class
- * histogram per 65536-point chunk); later scans of the SAME columns consult it: chunks disjoint from
- * the box are skipped, chunks inside it are counted without being read, only straddling chunks are
- * scanned (class counts are answered from the histograms alone).  Results are identical to
- * pcq_scan_dev; count collectors only; layouts the index does not cover fall through to pcq_scan_dev.
+ * histogram per 65536-point chunk); later scans of the SAME columns (same pointer and n) consult it:
+ * chunks disjoint from the box are skipped, chunks inside it are counted without being read, only
+ * straddling chunks are scanned (class counts are answered from the histograms alone).
+ * Count and buffer collectors; grid collectors are refused (PCQ_ERR_ARG).  A buffer collector gets
+ * exactly the records pcq_scan_dev appends, in the same order, after those it already holds: the
+ * emit's count pass reads neither the positions nor the class bytes of a disjoint or contained
+ * chunk (a disjoint one is then skipped by the emit as well; a contained one is read once, for its
+ * records), and the ragged tail behind the last whole bounds chunk is always read.  Results are
+ * identical to pcq_scan_dev; layouts the index does not cover fall through to it: strided / LAS
+ * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).
+ * Statistics of the last scan, in index chunks: for a count scan what it read; for a buffer scan the
+ * chunks its count pass skipped (disjoint), took whole (contained) and read (straddling); after a
+ * build, every chunk was read.  They are collected on the device and fetched (one wait) when asked.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pcq_index pcq_index;
 typedef struct pcq_index_stats {

@@ -79,6 +79,22 @@ int pcq_query_resident_free(pcq_host_resident *r);
 int pcq_query_resident_count_bounds(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint64_t *matches,
                                     uint64_t *points_scanned);
 int pcq_query_resident_count_class(pcq_host_resident *r, uint8_t cls, uint64_t *matches, uint64_t *points_scanned);
+/* Point and density queries over a resident dataset: the per-file searches over every loaded file, in load order, into ONE
+ * collector.  Count and buffer collectors go through each file's chunk index (pcq_scan_dev_indexed: the first query of a
+ * kind builds it, later ones read only the chunks that straddle the box); grid collectors through pcq_scan_dev, unpruned.
+ * A dataset from pcq_query_resident_load (no colour blocks) refuses buffer and grid collectors, and a collector of another
+ * device than the dataset's is refused (PCQ_ERR_ARG).
+ * Like pcq_query_resident_load, and also the colour blocks (formats with colour): what point queries need. */
+int pcq_query_resident_load_points(int device, const char *const *files, size_t nfiles, pcq_host_resident **out);
+/* == pcq_query_search_file_bounds(path, bmin, bmax, optimized=1, c) for every loaded file, in load order, into ONE collector:
+ * the same count, records in the same order, grid cells and winners — the header early-out (last.rs:92-94) included, which
+ * leaves the collector's file-order index where it was; PCQ_ERR_PANIC for min > max. */
+int pcq_query_resident_search_bounds(pcq_host_resident *r, const double bmin[3], const double bmax[3], pcq_host_collector *c);
+/* == pcq_query_search_file_class(path, cls, optimized=1, c) for every loaded file, in load order. */
+int pcq_query_resident_search_class(pcq_host_resident *r, uint8_t cls, pcq_host_collector *c);
+/* Index statistics of the last resident search, summed over its files (those it scanned through an index; none for a grid
+ * collector).  Waits for the search's scans. */
+int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out);
 
 /* The whole CLI in-process (main.rs:191-319); returns the exit code. */
 int pcq_query_main(int argc, const char *const *argv);

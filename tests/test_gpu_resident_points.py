@@ -1,0 +1,304 @@
+"""host/resident.cpp: point and density queries over a dataset kept in HBM.  pcq_query_resident_search_{bounds,class} into
+one collector must equal the per-file searches (pcq_query_search_file_*, --optimized) over the same files, in load order,
+into one collector — the count, the records byte for byte and in order, the grid cells and their winners — and the oracle
+fed the same files.  Count and buffer collectors go through each file's chunk index; on a file whose point blocks are in
+x order most chunks of a thin x slab are skipped."""
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+specs = importlib.import_module("adhoc-queries-pointclouds_amd.synth_specs")
+POINT_DTYPE = pkg.POINT_DTYPE
+PCQ_ERR_ARG, PCQ_ERR_PANIC, PCQ_ERR_EXTENSION = -8, -7, -4
+
+
+class IndexStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("skipped", C.c_uint64), ("whole", C.c_uint64), ("scanned", C.c_uint64), ("built", C.c_uint64)]
+
+
+class Q:
+    """ctypes view of the parts of include/pcq_query.h used here"""
+
+    def __init__(self):
+        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
+        dd = P(C.c_double)
+        lib.pcq_query_last_error.restype = C.c_char_p
+        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
+        lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, P(vp)]
+        lib.pcq_query_collector_new_grid.argtypes = [C.c_int, dd, dd, C.c_double, P(vp)]
+        lib.pcq_query_collector_free.argtypes = [vp]
+        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
+        lib.pcq_query_collector_points.argtypes = [vp, vp, u64, P(u64)]
+        lib.pcq_query_collector_grid_cells.argtypes = [vp, vp, u64, P(u64)]
+        lib.pcq_query_search_file_bounds.argtypes = [C.c_char_p, dd, dd, C.c_int, vp, P(C.c_int)]
+        lib.pcq_query_search_file_class.argtypes = [C.c_char_p, C.c_uint8, C.c_int, vp]
+        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
+        lib.pcq_query_resident_load_points.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
+        lib.pcq_query_resident_free.argtypes = [vp]
+        lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
+        lib.pcq_query_resident_search_class.argtypes = [vp, C.c_uint8, vp]
+        lib.pcq_query_resident_last_stats.argtypes = [vp, P(IndexStats)]
+
+    @staticmethod
+    def d3(v):
+        return (C.c_double * 3)(*[float(x) for x in v])
+
+    def err(self):
+        return self.lib.pcq_query_last_error()
+
+    def collector(self, kind, grid=None, device=0):
+        h = C.c_void_p()
+        if kind == "count":
+            rc = self.lib.pcq_query_collector_new_count(device, C.byref(h))
+        elif kind == "buffer":
+            rc = self.lib.pcq_query_collector_new_buffer(device, C.byref(h))
+        else:
+            rc = self.lib.pcq_query_collector_new_grid(device, self.d3(grid[0]), self.d3(grid[1]), grid[2], C.byref(h))
+        assert rc == 0, self.err()
+        return h
+
+    def result(self, h, kind):
+        """count, or the records (buffer: file order), or (sorted cell keys, winners in key order)"""
+        n = C.c_uint64()
+        assert self.lib.pcq_query_collector_point_count(h, C.byref(n)) == 0, self.err()
+        if kind == "count":
+            return n.value
+        assert self.lib.pcq_query_collector_points(h, None, 0, C.byref(n)) == 0
+        pts = np.zeros(n.value, dtype=POINT_DTYPE)
+        if n.value:
+            assert self.lib.pcq_query_collector_points(h, pts.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
+        if kind == "buffer":
+            return pts.tobytes()
+        assert self.lib.pcq_query_collector_grid_cells(h, None, 0, C.byref(n)) == 0
+        keys = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            assert self.lib.pcq_query_collector_grid_cells(h, keys.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
+        order = np.argsort(keys, kind="stable")
+        return keys[order].tobytes(), pts[order].tobytes()
+
+    def load(self, paths, points=True, device=0):
+        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+        h = C.c_void_p()
+        fn = self.lib.pcq_query_resident_load_points if points else self.lib.pcq_query_resident_load
+        rc = fn(device, arr, len(paths), C.byref(h))
+        return rc, h
+
+    def stats(self, r):
+        st = IndexStats()
+        assert self.lib.pcq_query_resident_last_stats(r, C.byref(st)) == 0, self.err()
+        return {k: getattr(st, k) for k, _ in IndexStats._fields_}
+
+
+def oracle_result(oracle, paths, kind, query, grid=None):
+    if kind == "count":
+        oc = oracle.count_collector()
+    elif kind == "buffer":
+        oc = oracle.buffer_collector()
+    else:
+        oc = oracle.grid_collector(*grid)
+    for path in paths:
+        if query[0] == "bounds":
+            assert oracle.search_file(path, 0, query[1], query[2], 0, oc)[0] == 0
+        else:
+            assert oracle.search_file(path, 1, None, None, query[1], oc)[0] == 0
+    if kind == "count":
+        out = oc.point_count()
+    elif kind == "buffer":
+        out = oc.points().tobytes()
+    else:
+        out = (oc.grid_cells().tobytes(), oc.points().tobytes())
+    oc.free()
+    return out
+
+
+# LAST field blocks of formats 0-3 (offset in the record, bytes): each is n x size bytes at offset_to_point_data + n x offset
+FIELDS = {0: [(0, 12), (12, 2), (14, 1), (15, 1), (16, 1), (17, 1), (18, 2)]}
+FIELDS[1] = FIELDS[0] + [(20, 8)]
+FIELDS[2] = FIELDS[0] + [(20, 6)]
+FIELDS[3] = FIELDS[0] + [(20, 8), (28, 6)]
+
+
+@pytest.fixture(scope="module")
+def q():
+    return Q()
+
+
+@pytest.fixture(scope="module")
+def files(oracle, tmp_path_factory):
+    """LAST files of formats 0-3, and one (format 2, with colour) whose point blocks are permuted into x order."""
+    d = tmp_path_factory.mktemp("resident")
+    out = []
+    for fmt in (0, 1, 2, 3):
+        spec = specs._spec(9100 + fmt, 70_001 + 13 * fmt, fmt, (0.01, 0.02, 0.05), (100.0, -200.0, 7.5), (-5000, -5000, -1000),
+                           (10001, 10001, 2001), classes=[(1, 0.4), (2, 0.3), (6, 0.2), (134, 0.1)])
+        p = str(d / f"f{fmt}.last")
+        oracle.synth_write(spec, p)
+        out.append(p)
+    spec = specs._spec(9200, 400_009, 2, (0.01, 0.02, 0.05), (100.0, -200.0, 7.5), (-5000, -5000, -1000), (10001, 10001, 2001),
+                       classes=[(1, 0.4), (2, 0.3), (6, 0.2), (134, 0.1)])
+    img = oracle.synth_image(spec, transposed=True).copy()
+    hdr = oracle.parse_header(img[:400].tobytes())
+    n, otp = hdr.number_of_points, hdr.offset_to_point_data
+    xyz = img[otp:otp + 12 * n].view(np.int32).reshape(n, 3)
+    order = np.argsort(xyz[:, 0], kind="stable")
+    for off, size in FIELDS[2]:
+        blk = img[otp + n * off: otp + n * (off + size)].reshape(n, size)
+        img[otp + n * off: otp + n * (off + size)] = blk[order].reshape(-1)
+    p = str(d / "sorted_x.last")
+    img.tofile(p)
+    out.append(p)
+    return out
+
+
+BOXES = [((90.0, -250.0, 0.0), (120.0, -150.0, 20.0)), ((0.0, -400.0, -100.0), (200.0, 0.0, 100.0)),
+         ((149.99, -400.0, -100.0), (150.0, 0.0, 100.0)), ((500.0, 500.0, 500.0), (600.0, 600.0, 600.0)),
+         ((60.0, -300.0, -100.0), (61.0, -100.0, 200.0)),        # a thin x slab
+         ((-1e12, -1e12, -1e12), (1e12, 1e12, 1e12))]
+CLASSES = [1, 2, 6, 134, 19]
+GRID = ((40.0, -320.0, -60.0), (160.0, -80.0, 120.0))
+
+
+def per_file(q, paths, kind, query, grid=None):
+    h = q.collector(kind, grid)
+    for path in paths:
+        if query[0] == "bounds":
+            rc = q.lib.pcq_query_search_file_bounds(path.encode(), q.d3(query[1]), q.d3(query[2]), 1, h, None)
+        else:
+            rc = q.lib.pcq_query_search_file_class(path.encode(), query[1], 1, h)
+        assert rc == 0, q.err()
+    out = q.result(h, kind)
+    q.lib.pcq_query_collector_free(h)
+    return out
+
+
+def resident(q, r, kind, query, grid=None):
+    h = q.collector(kind, grid)
+    if query[0] == "bounds":
+        rc = q.lib.pcq_query_resident_search_bounds(r, q.d3(query[1]), q.d3(query[2]), h)
+    else:
+        rc = q.lib.pcq_query_resident_search_class(r, query[1], h)
+    assert rc == 0, q.err()
+    out = q.result(h, kind)
+    q.lib.pcq_query_collector_free(h)
+    return out
+
+
+def queries():
+    return [("bounds", bmin, bmax) for bmin, bmax in BOXES] + [("class", c) for c in CLASSES]
+
+
+def test_resident_search_equals_per_file_searches_and_oracle(oracle, q, files):
+    rc, r = q.load(files)
+    assert rc == 0, q.err()
+    try:
+        for query in queries():
+            for kind, grid in [("count", None), ("buffer", None), ("grid", GRID + (2.0,)), ("grid", GRID + (0.5,))]:
+                for rep in range(2):  # the second time through the built indices
+                    got = resident(q, r, kind, query, grid)
+                    assert got == per_file(q, files, kind, query, grid), (query, kind, grid, rep)
+                    assert got == oracle_result(oracle, files, kind, query, grid), (query, kind, grid, rep)
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_grid_ties_across_files_follow_the_early_out(oracle, q, files):
+    """A file the header early-out skips does not move the collector's file-order index: the winners of cells shared by
+    files are those of the per-file loop (first seen wins in file order)."""
+    paths = [files[4], files[0], files[2], files[4]]  # the same file twice: every cell of it is tied
+    rc, r = q.load(paths)
+    assert rc == 0, q.err()
+    try:
+        for bmin, bmax in BOXES:
+            for cell in (2.0, 0.5):
+                query, grid = ("bounds", bmin, bmax), GRID + (cell,)
+                got = resident(q, r, "grid", query, grid)
+                assert got == per_file(q, paths, "grid", query, grid), (bmin, cell)
+                assert got == oracle_result(oracle, paths, "grid", query, grid), (bmin, cell)
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_resident_stats_show_skipped_chunks_on_the_x_ordered_file(q, files):
+    rc, r = q.load([files[4]])
+    assert rc == 0, q.err()
+    try:
+        slab = ("bounds",) + BOXES[4]
+        first = resident(q, r, "buffer", slab)
+        st = q.stats(r)
+        assert st["built"] == 1 and st["chunks"] == 400_009 // 4096
+        assert resident(q, r, "buffer", slab) == first
+        st = q.stats(r)
+        assert st["built"] == 0 and st["skipped"] + st["whole"] + st["scanned"] == st["chunks"]
+        assert st["skipped"] >= 0.9 * st["chunks"], st
+        resident(q, r, "count", slab)
+        st2 = q.stats(r)
+        assert st2["skipped"] == st["skipped"] and st2["whole"] == st["whole"] and st2["scanned"] == st["scanned"], (st, st2)
+        # grid collectors do not consult the index: no statistics
+        resident(q, r, "grid", slab, GRID + (2.0,))
+        assert q.stats(r)["chunks"] == 0
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_resident_search_errors(q, files):
+    rc, r = q.load(files)
+    assert rc == 0, q.err()
+    rc2, r2 = q.load(files, points=False)
+    assert rc2 == 0, q.err()
+    try:
+        hb = q.collector("buffer")
+        hg = q.collector("grid", GRID + (2.0,))
+        hc = q.collector("count")
+        # min > max panics like AABB::from_min_max (main.rs:80-91)
+        assert q.lib.pcq_query_resident_search_bounds(r, q.d3((1, 1, 1)), q.d3((0, 2, 2)), hb) == PCQ_ERR_PANIC
+        # a dataset loaded for counts only serves count collectors
+        for h in (hb, hg):
+            assert q.lib.pcq_query_resident_search_bounds(r2, q.d3(BOXES[1][0]), q.d3(BOXES[1][1]), h) == PCQ_ERR_ARG
+            assert q.lib.pcq_query_resident_search_class(r2, 6, h) == PCQ_ERR_ARG
+        assert q.lib.pcq_query_resident_search_bounds(r2, q.d3(BOXES[1][0]), q.d3(BOXES[1][1]), hc) == 0, q.err()
+        assert q.result(hc, "count") == per_file(q, files, "count", ("bounds",) + BOXES[1])
+        assert q.lib.pcq_query_resident_search_class(r2, 6, hc) == 0, q.err()
+        for h in (hb, hg, hc):
+            q.lib.pcq_query_collector_free(h)
+        # a non-LAST file at load
+        d = os.path.dirname(files[0])
+        las = os.path.join(d, "not_last.las")
+        with open(las, "wb") as f:
+            f.write(open(files[0], "rb").read())
+        rc3, _ = q.load([files[0], las])
+        assert rc3 == PCQ_ERR_EXTENSION
+    finally:
+        q.lib.pcq_query_resident_free(r)
+        q.lib.pcq_query_resident_free(r2)
+
+
+def device_count():
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    pkg.load_library()  # (the one HIP runtime of the process)
+    hip = C.CDLL(binding.hip_runtime_path() or "libamdhip64.so")
+    n = C.c_int(0)
+    return n.value if hip.hipGetDeviceCount(C.byref(n)) == 0 else 0
+
+
+def test_collector_of_another_device_is_refused(q, files):
+    if device_count() < 2:
+        pytest.skip("one GPU: no collector of another device")
+    rc, r = q.load(files[:1])
+    assert rc == 0, q.err()
+    try:
+        h = q.collector("buffer", device=1)
+        assert q.lib.pcq_query_resident_search_bounds(r, q.d3(BOXES[1][0]), q.d3(BOXES[1][1]), h) == PCQ_ERR_ARG
+        assert q.lib.pcq_query_resident_search_class(r, 6, h) == PCQ_ERR_ARG
+        q.lib.pcq_query_collector_free(h)
+    finally:
+        q.lib.pcq_query_resident_free(r)

@@ -1,6 +1,11 @@
 """Developer tool: effect of the chunk index on repeated bounds counts over one
 163 M-point file whose points are in a spatially coherent order (sorted by x, then y within x slabs —
-a stand-in for LiDAR scan-line order) versus the uniform-random order of the synthetic files."""
+a stand-in for LiDAR scan-line order) versus the uniform-random order of the synthetic files.
+
+--buffer: the same two orders with a buffer collector (the emit of the matching records): boxes that keep about 0.1 %, 1 %
+and 10 % of the chunks of the coherent order (x slabs over the whole y and z range), plain pcq_scan_dev against
+pcq_scan_dev_indexed, alternated, timed with device events after warm-up; the records of the two are compared byte for
+byte, and the positions the count pass read per the index statistics are printed next to the times."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,21 +14,62 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 specs = importlib.import_module("adhoc-queries-pointclouds_amd.synth_specs")
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 163_000_000
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+BUFFER = "--buffer" in sys.argv
+n = int(args[0]) if args else 163_000_000
 dev = torch.device("cuda:0")
 ts = torch.cuda.Stream(); torch.cuda.set_stream(ts); stream = ts.cuda_stream
 with pkg.Context(0) as ctx:
     spec = specs.synth_ca13(points_per_file=n)[5]
     raw = torch.empty(n * 3, dtype=torch.int32, device=dev)
-    ctx.synth_fill(spec, 0, n, raw.data_ptr(), None, stream)
+    cls = torch.empty(n, dtype=torch.uint8, device=dev)
+    ctx.synth_fill(spec, 0, n, raw.data_ptr(), cls.data_ptr() if BUFFER else None, stream)
     torch.cuda.synchronize()
     pts = raw.view(n, 3)
     # coherent order: bucket x into 2048 slabs, sort by (slab, y)
     key = ((pts[:, 0].long() - int(spec.lo[0])) * 2048 // int(spec.span[0])) * (1 << 32) + (pts[:, 1].long() - int(spec.lo[1]))
     order = torch.argsort(key)
     coh = pts[order].contiguous()
+    coh_cls = cls[order].contiguous() if BUFFER else None
     del key, order
     torch.cuda.synchronize()
+    if BUFFER:
+        res_all = {}
+        for label, t, c in (("random_order", pts, cls), ("coherent_order", coh, coh_cls)):
+            cols = binding.make_columns(xyz=t.data_ptr(), cls=c.data_ptr(), n=n, scale=list(spec.scale), offset=list(spec.offset))
+            ix = ctx.index_new()
+            res = {}
+            for frac in (0.001, 0.01, 0.1):
+                x0 = int(spec.lo[0] + spec.span[0] * 0.37)
+                lmin = [x0, -2 ** 31, -2 ** 31]
+                lmax = [x0 + int(spec.span[0] * frac), 2 ** 31 - 1, 2 ** 31 - 1]
+                pred = pkg.Predicate.bounds(lmin, lmax)
+                gb = {False: ctx.buffer_collector(), True: ctx.buffer_collector()}
+                times = {False: [], True: []}
+                for it in range(14):  # alternating; the first two of each are warm-up (the first indexed scan builds the index)
+                    for indexed in (False, True):
+                        gb[indexed].reset()
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        if indexed: ctx.scan_dev_indexed(cols, pred, ix, gb[indexed], stream)
+                        else: ctx.scan_dev(cols, pred, gb[indexed], stream)
+                        e1.record(); e1.synchronize()
+                        if it >= 2: times[indexed].append(e0.elapsed_time(e1))
+                st = ctx.index_stats(ix)
+                a, b = gb[False].points(), gb[True].points()
+                assert a.tobytes() == b.tobytes(), (label, frac)
+                for g in gb.values(): g.free()
+                med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+                tail = n - st["chunks"] * 4096
+                res[f"x{frac}"] = {"records": len(a), "plain_ms": med[False], "indexed_ms": med[True], "speedup": med[False] / med[True],
+                                   "chunks": st["chunks"], "skipped": st["skipped"], "whole": st["whole"], "scanned": st["scanned"],
+                                   "count_pass_position_bytes_plain": 12 * n,
+                                   "count_pass_position_bytes_indexed": 12 * (st["scanned"] * 4096 + tail)}
+                print(label, f"x{frac}", json.dumps(res[f"x{frac}"]), flush=True)
+            ctx.index_free(ix)
+            res_all[label] = res
+        sys.exit(0)
     counter = torch.zeros(2, dtype=torch.int64, device=dev)
     cc = ctx.count_collector(device_counter=counter.data_ptr())
     out = {}
