@@ -422,6 +422,12 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: null argument");
     if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count and buffer collectors only");
+    if (pred->kind == PCQ_PRED_TIME) {  // no time index: the plain scan, and statistics that claim nothing
+        ix->last = pcq_index_stats{};
+        ix->stats_stream = nullptr;
+        ix->stats_kind = 0;
+        return pcq_scan_dev(ctx, cols, pred, c, stream);
+    }
     if (c->kind == COLL_BUFFER) return scan_buffer_indexed(ctx, cols, pred, ix, c, stream);
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     c->last_stream = s;

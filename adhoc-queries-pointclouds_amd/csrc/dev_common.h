@@ -18,6 +18,14 @@ __device__ __forceinline__ int32_t ld_i32(const uint8_t *p) {
     return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
 }
 __device__ __forceinline__ uint16_t ld_u16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
+// A little-endian f64 at any byte alignment (a LAS GPS time sits at record + 20 / + 22: never 8-byte aligned in general).
+__device__ __forceinline__ double ld_f64(const uint8_t *p) {
+    if (((uintptr_t)p & 7) == 0) return *reinterpret_cast<const double *>(p);
+    const uint64_t lo = (uint32_t)ld_i32(p), hi = (uint32_t)ld_i32(p + 4);
+    return __longlong_as_double((long long)(lo | (hi << 32)));
+}
+// Range<f64>::contains (las.rs:336): start <= t && t < end, IEEE — a NaN time or bound is no match, start >= end matches nothing.
+__device__ __forceinline__ bool time_in(double t, const DevPred &pr) { return (t >= pr.wmin[0]) & (t < pr.wmax[0]); }
 
 struct RawPoint {
     int32_t x, y, z;
@@ -77,6 +85,7 @@ __device__ __forceinline__ bool eval_pred(const DevCols &c, const DevPred &pr, u
                  (wz > pr.wmax[2]));
     }
     have_xyz = false;
+    if (pr.kind == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
 }
 
@@ -85,6 +94,7 @@ __device__ __forceinline__ bool eval_pred(const DevCols &c, const DevPred &pr, u
 template <int KIND>
 __device__ __forceinline__ bool eval_pred_kind(const DevCols &c, const DevPred &pr, uint64_t i) {
     if (KIND == PCQ_PRED_CLASS) return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
+    if (KIND == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);  // (the time column rides in cls)
     const RawPoint rp = ld_xyz(c, i);
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
@@ -98,6 +108,7 @@ __device__ __forceinline__ bool eval_pred_kind(const DevCols &c, const DevPred &
 template <int KIND>
 __device__ __forceinline__ bool eval_pred_kind(const DevCols &c, const DevPred &pr, uint64_t i, RawPoint &rp) {
     if (KIND == PCQ_PRED_CLASS) return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
+    if (KIND == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     rp = ld_xyz(c, i);
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &

@@ -5,21 +5,24 @@ namespace pcqgrid {
 // ---------------------------------------------------------------------------------------------------------------
 // pass 0: one reading of a scan's points -> per tile one block of tuples sorted by level-1 bin + a directory row
 // ---------------------------------------------------------------------------------------------------------------
-// What the predicate reads of a point: its position (bounds kinds) or its class byte.
+// What the predicate reads of a point: its position (bounds kinds), its class byte or its GPS time (TIME: in c.cls).
 template <int KIND>
 struct P0In {
     RawPoint rp;
     uint32_t cls;
+    double t;
 };
 template <int KIND>
 __device__ __forceinline__ P0In<KIND> p0_load(const DevCols &c, uint64_t i) {
     P0In<KIND> in;
     if (KIND == PCQ_PRED_CLASS) in.cls = c.cls[i * c.cls_stride];
+    else if (KIND == PCQ_PRED_TIME) in.t = ld_f64(c.cls + i * c.cls_stride);
     else in.rp = ld_xyz_stream(c, i);
     return in;
 }
 // The same for point `li` of the tile that starts at point `base` (li clamped to the tile's last point).  PACKED: the
-// columns are LAST blocks — 12-byte positions at a 4-byte aligned address, one class byte per point, 6-byte colours — so
+// columns are LAST blocks — 12-byte positions at a 4-byte aligned address, one class byte per point (TIME: one f64 per
+// point at an 8-byte aligned address), 6-byte colours — so
 // that a point's address is the tile's (the same for the whole workgroup, scalar registers) plus a 32-bit offset, instead
 // of a 64-bit multiply-add and an alignment test per point and column.
 template <int KIND, bool PACKED>
@@ -29,6 +32,8 @@ __device__ __forceinline__ P0In<KIND> p0_load_tile(const DevCols &c, uint64_t ba
     P0In<KIND> in;
     if (KIND == PCQ_PRED_CLASS) {
         in.cls = *(const PCQ_GLOBAL uint8_t *)(c.cls + base + lc);
+    } else if (KIND == PCQ_PRED_TIME) {
+        in.t = *(const PCQ_GLOBAL double *)(c.cls + base * 8 + lc * 8u);
     } else {
         const i32x3_a4 v = __builtin_nontemporal_load(reinterpret_cast<const i32x3_a4 *>(c.xyz + base * 12 + lc * 12u));  // (sizeof(i32x3) is 16: bytes, not elements)
         in.rp.x = v.x, in.rp.y = v.y, in.rp.z = v.z;
@@ -38,6 +43,7 @@ __device__ __forceinline__ P0In<KIND> p0_load_tile(const DevCols &c, uint64_t ba
 template <int KIND>
 __device__ __forceinline__ bool p0_pass(const DevCols &c, const DevPred &pr, const P0In<KIND> &in) {
     if (KIND == PCQ_PRED_CLASS) return in.cls == pr.cls;
+    if (KIND == PCQ_PRED_TIME) return time_in(in.t, pr);
     const RawPoint &rp = in.rp;
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
@@ -120,6 +126,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
 #pragma unroll
     for (int j = 0; j < ITEMS; j++) {  // (arrived: inside the loop nothing is pending at its head)
         if (KIND == PCQ_PRED_CLASS) asm volatile("" ::"v"(cur[j].cls));
+        else if (KIND == PCQ_PRED_TIME) asm volatile("" ::"v"(cur[j].t));
         else asm volatile("" ::"v"(cur[j].rp.x), "v"(cur[j].rp.y), "v"(cur[j].rp.z));
     }
     for (; tile < ntiles; tile += gridDim.x, parity ^= 1) {
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
             rg[j] = 0, bb[j] = 0, cl[j] = KIND == PCQ_PRED_CLASS ? cur[j].cls : 0;
             pk[j] = 0, metas[j] = 0, ranks[j] = 0;
             if (!passes[j]) continue;
-            if (KIND == PCQ_PRED_CLASS) {
+            if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME) {  // positions only of the matches (las.rs:340-344)
                 if (PACKED) {
                     const i32x3_a4 v = *(const PCQ_GLOBAL i32x3_a4 *)(c.xyz + base * 12 + li * 12u);
                     cur[j].rp.x = v.x, cur[j].rp.y = v.y, cur[j].rp.z = v.z;
@@ -158,7 +165,8 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
                 rg[j] = ld_u16(q) | (ld_u16(q + 2) << 16);
                 bb[j] = ld_u16(q + 4);
             }
-            if (KIND != PCQ_PRED_CLASS && c.cls) cl[j] = PACKED ? *(const PCQ_GLOBAL uint8_t *)(c.cls + base + li) : c.cls[i * c.cls_stride];  // last.rs:138-142
+            // last.rs:138-142 (TIME: c.cls is the time column; a time record's class is 0, las.rs:345-355)
+            if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME && c.cls) cl[j] = PACKED ? *(const PCQ_GLOBAL uint8_t *)(c.cls + base + li) : c.cls[i * c.cls_stride];
         }
         if (agg)
             for (uint32_t k = tid; k < (uint32_t)AGG_SLOTS; k += NT) s_atab[k] = ~0ull;
@@ -271,6 +279,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
         for (int j = 0; j < ITEMS; j++) {  // the next tile's inputs have arrived (asked for a whole tile ago) — before the stores below
             cur[j] = nxt[j];
             if (KIND == PCQ_PRED_CLASS) asm volatile("" ::"v"(cur[j].cls));
+            else if (KIND == PCQ_PRED_TIME) asm volatile("" ::"v"(cur[j].t));
             else asm volatile("" ::"v"(cur[j].rp.x), "v"(cur[j].rp.y), "v"(cur[j].rp.z));
         }
         if (tid == 0) s_npass[parity ^ 1] = 0;
@@ -312,5 +321,8 @@ PCQ_P0_INST(PCQ_PRED_BOUNDS)
 PCQ_P0_INST(PCQ_PRED_CLASS)
 PCQ_P0_INST(PCQ_PRED_BOUNDS_F64)
 #undef PCQ_P0_INST
+// a time record has no colour and class 0: always the 16-byte tuple
+template __global__ void k_p0_part<PCQ_PRED_TIME, false, true, false>(P0Args);
+template __global__ void k_p0_part<PCQ_PRED_TIME, false, false, false>(P0Args);
 
 }  // namespace pcqgrid

@@ -525,6 +525,11 @@ int pcq_make_dev_pred(const pcq_predicate *p, DevPred *out) {
         for (int a = 0; a < 3; a++) out->wmin[a] = p->wmin[a], out->wmax[a] = p->wmax[a];
         return PCQ_OK;
     }
+    if (p->kind == PCQ_PRED_TIME) {  // [start, end): an empty or NaN range is legal and matches nothing
+        out->wmin[0] = p->wmin[0];
+        out->wmax[0] = p->wmax[0];
+        return PCQ_OK;
+    }
     if (p->kind != PCQ_PRED_BOUNDS) return pcq_fail(PCQ_ERR_ARG, "unknown predicate kind %d", p->kind);
     for (int a = 0; a < 3; a++) {
         const int64_t lo = p->lmin[a] < INT32_MIN ? (int64_t)INT32_MIN : p->lmin[a];
@@ -765,7 +770,7 @@ extern "C" int pcq_collector_grid_params(const pcq_collector *c, uint64_t dims[3
 // ---------------------------------------------------------------------------------------------
 int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c) {
     if (!cols || !pred || !c) return pcq_fail(PCQ_ERR_ARG, "scan: null argument");
-    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS && pred->kind != PCQ_PRED_BOUNDS_F64)
+    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS && pred->kind != PCQ_PRED_BOUNDS_F64 && pred->kind != PCQ_PRED_TIME)
         return pcq_fail(PCQ_ERR_ARG, "scan: bad predicate kind %d", pred->kind);
     if (cols->n == 0) return PCQ_OK;
     // index arithmetic (n * stride, first_index + n) must stay far from 2^64: a LAS record length is a u16
@@ -775,6 +780,12 @@ int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const 
                         (unsigned long long)cols->first_index);
     if (cols->xyz_stride > 65535 || cols->cls_stride > 65535 || cols->rgb_stride > 65535)
         return pcq_fail(PCQ_ERR_ARG, "scan: column stride above 65535");
+    if (pred->kind == PCQ_PRED_TIME) {  // cls = the time column (always read); positions for the records of buffer and grid collectors
+        if (c->kind != COLL_COUNT && (!cols->xyz || cols->xyz_stride < 12))
+            return pcq_fail(PCQ_ERR_ARG, "scan: positions column missing or stride < 12");
+        if (!cols->cls || cols->cls_stride < 8) return pcq_fail(PCQ_ERR_ARG, "scan: time column missing or stride < 8");
+        return PCQ_OK;  // (rgb is ignored: a time record has no colour)
+    }
     const bool need_xyz = pred->kind != PCQ_PRED_CLASS || c->kind != COLL_COUNT;
     const bool need_cls = pred->kind == PCQ_PRED_CLASS || c->kind != COLL_COUNT;
     if (need_xyz && (!cols->xyz || cols->xyz_stride < 12)) return pcq_fail(PCQ_ERR_ARG, "scan: positions column missing or stride < 12");
@@ -817,6 +828,10 @@ static int count_into(pcq_ctx *ctx, const DevCols &dc, const DevPred &dp, uint64
         return pcq_launch_generic_count(ctx, dc, dp, d_count, s);
     }
     if (dp.kind == PCQ_PRED_BOUNDS_F64) return pcq_launch_generic_count(ctx, dc, dp, d_count, s);
+    if (dp.kind == PCQ_PRED_TIME) {  // K3 over a packed, 8-byte aligned column; LAS records and unaligned blocks: the strided kernel
+        if (dc.cls_stride == 8 && ((uintptr_t)dc.cls & 7) == 0) return pcq_launch_time_count_f64(ctx, dc.cls, dc.n, dp, d_count, s);
+        return pcq_launch_generic_count(ctx, dc, dp, d_count, s);
+    }
     if (dc.cls_stride == 1) return pcq_launch_class_count_u8(ctx, dc.cls, dc.n, (uint8_t)dp.cls, d_count, s);
     return pcq_launch_generic_count(ctx, dc, dp, d_count, s);
 }
@@ -866,6 +881,7 @@ int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate
     rc = pcq_make_dev_pred(pred, &dp);
     if (rc) return rc;
     DevCols dc = to_dev_cols(cols);
+    if (dp.kind == PCQ_PRED_TIME) dc.rgb = nullptr, dc.rgb_stride = 0;  // a time record's colour is (0,0,0) (las.rs:345-355)
     c->last_stream = s;
     switch (c->kind) {
     case COLL_COUNT:
@@ -1056,14 +1072,18 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
     PCQ_HIP(hipSetDevice(ctx->device));
 
     StagePlan pl{};
-    pl.need_xyz = pred->kind != PCQ_PRED_CLASS || c->kind != COLL_COUNT;
-    pl.need_cls = pred->kind == PCQ_PRED_CLASS || c->kind != COLL_COUNT;
-    pl.need_rgb = c->kind != COLL_COUNT && cols->rgb != nullptr;
+    // the predicate's own column ("cls"): a class byte, or an f64 GPS time (PCQ_PRED_TIME) — read by every scan of that kind
+    const bool time = pred->kind == PCQ_PRED_TIME;
+    const bool pred_col = pred->kind == PCQ_PRED_CLASS || time;
+    const uint64_t w = time ? 8 : 1;  // bytes per point of that column
+    pl.need_xyz = !pred_col || c->kind != COLL_COUNT;
+    pl.need_cls = pred_col || c->kind != COLL_COUNT;
+    pl.need_rgb = c->kind != COLL_COUNT && cols->rgb != nullptr && !time;
     const uint8_t *hx = (const uint8_t *)cols->xyz, *hc = (const uint8_t *)cols->cls, *hr = (const uint8_t *)cols->rgb;
     // AoS (LAS): every needed column has the same stride and lives inside one record
     {
         const uint64_t st = pl.need_xyz ? cols->xyz_stride : cols->cls_stride;
-        bool same = st > 12 || (!pl.need_xyz && st > 1);
+        bool same = st > 12 || (!pl.need_xyz && st > w);
         if (pl.need_xyz && cols->xyz_stride != st) same = false;
         if (pl.need_cls && cols->cls_stride != st) same = false;
         if (pl.need_rgb && cols->rgb_stride != st) same = false;
@@ -1073,7 +1093,7 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
             if (!hi || p + sz > hi) hi = p + sz;
         };
         if (pl.need_xyz) upd(hx, 12);
-        if (pl.need_cls) upd(hc, 1);
+        if (pl.need_cls) upd(hc, w);
         if (pl.need_rgb) upd(hr, 6);
         if (same && lo && (uint64_t)(hi - lo) <= st && st > 1) {
             pl.aos = true;
@@ -1084,15 +1104,15 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
         }
     }
     if (!pl.aos) {
-        if ((pl.need_xyz && cols->xyz_stride != 12) || (pl.need_cls && cols->cls_stride != 1) ||
+        if ((pl.need_xyz && cols->xyz_stride != 12) || (pl.need_cls && cols->cls_stride != w) ||
             (pl.need_rgb && cols->rgb_stride != 6))
             return pcq_fail(PCQ_ERR_ARG, "pcq_scan_host: columns must be packed blocks (LAST) or one interleaved record (LAS)");
-        pl.bytes_per_point = (pl.need_xyz ? 12 : 0) + (pl.need_cls ? 1 : 0) + (pl.need_rgb ? 6 : 0);
+        pl.bytes_per_point = (pl.need_xyz ? 12 : 0) + (pl.need_cls ? w : 0) + (pl.need_rgb ? 6 : 0);
     }
 
     // "chunk_points" is given in points of a positions column (12 B each); what matters to the pipeline is the BYTES per
-    // chunk, so a class-only scan (1 B per point) takes 12 x as many points per chunk and a record scan of a wide LAS
-    // format fewer — otherwise a class query would move 2 MB per chunk and drown in per-chunk overhead
+    // chunk, so a class-only scan (1 B per point) takes 12 x as many points per chunk, a time count (8 B) 1.5 x, and a
+    // record scan of a wide LAS format fewer — otherwise a class query would move 2 MB per chunk and drown in per-chunk overhead
     uint64_t chunk = ctx->chunk_points * 12 / (pl.bytes_per_point ? pl.bytes_per_point : 1);
     if (chunk < 4) chunk = 4;
     if (chunk > cols->n) chunk = cols->n;
@@ -1116,10 +1136,10 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
     hipStream_t s = ctx->stream, cs = ctx->copy_stream;
     const uint64_t nchunks = (cols->n + chunk - 1) / chunk;
 
-    // region offsets inside a staging buffer (SoA case)
+    // region offsets inside a staging buffer (SoA case); every region starts 16-byte aligned (a time column: K3's fast path)
     const size_t off_xyz = 0;
     const size_t off_cls = pl.need_xyz ? align16((size_t)chunk * 12) : 0;
-    const size_t off_rgb = off_cls + (pl.need_cls ? align16((size_t)chunk) : 0);
+    const size_t off_rgb = off_cls + (pl.need_cls ? align16((size_t)chunk * w) : 0);
 
     // A scan that reads every byte ONCE — count and grid collectors — reads the pinned ring in place: the kernels stream host
     // memory over PCIe at the rate the copy engine moves it (59 against 54.5 GB/s for a count, 56.5 against 50.1 for a grid
@@ -1153,11 +1173,11 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
         } else {
             int frc = PCQ_OK;
             if (pl.need_xyz) frc = fetch(ctx, fd, h + off_xyz, hx + first * 12, (size_t)cnt * 12);
-            if (!frc && pl.need_cls) frc = fetch(ctx, fd, h + off_cls, hc + first, (size_t)cnt);
+            if (!frc && pl.need_cls) frc = fetch(ctx, fd, h + off_cls, hc + first * w, (size_t)cnt * w);
             if (!frc && pl.need_rgb) frc = fetch(ctx, fd, h + off_rgb, hr + first * 6, (size_t)cnt * 6);
             if (frc) return frc;
             bytes = off_rgb + (pl.need_rgb ? (size_t)cnt * 6 : 0);
-            if (!pl.need_rgb) bytes = off_cls + (pl.need_cls ? (size_t)cnt : 0);
+            if (!pl.need_rgb) bytes = off_cls + (pl.need_cls ? (size_t)cnt * w : 0);
             if (!pl.need_cls && !pl.need_rgb) bytes = (size_t)cnt * 12;
         }
         if (k == 0) stamp("first chunk read into the staging buffer");

@@ -62,7 +62,7 @@ struct DevPred {
     uint32_t width[3];
     uint32_t cls;
     uint32_t _pad;
-    double wmin[3], wmax[3];  // PCQ_PRED_BOUNDS_F64
+    double wmin[3], wmax[3];  // PCQ_PRED_BOUNDS_F64; PCQ_PRED_TIME: [wmin[0], wmax[0])
 };
 
 struct DevCols {
@@ -272,6 +272,8 @@ int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, c
                                   uint64_t *d_count, hipStream_t s);
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls,
                               uint64_t *d_count, hipStream_t s);
+// scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)
+int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s);
 // scan_generic.hip
 int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred,
                              uint64_t *d_count, hipStream_t s);

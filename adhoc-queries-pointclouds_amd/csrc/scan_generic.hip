@@ -1,6 +1,6 @@
 // scan_generic.hip — layout-generic scan kernels (any column strides: LAST column blocks or LAS
 // AoS records), used where the count-only fast paths of scan_count.hip do not apply:
-//   * strided count            — LAS bounds/class count (las.rs:101-119, :221-231), unaligned LAST
+//   * strided count            — LAS bounds/class/time count (las.rs:101-119, :221-231, :328-338), unaligned LAST
 //                                (one record per lane: 4.1-5.9 TB/s of record bytes; an LDS-tiled variant
 //                                with 16-byte coalesced loads was measured and was NOT faster,
 //                                profiles/r01_las_aos_count_rate.log)
@@ -98,6 +98,7 @@ __device__ __forceinline__ void or_point31(uint32_t *image, uint32_t byte_offset
 template <int KIND, bool ATTRS>
 struct TileIn {
     RawPoint rps[EMIT_ITEMS];
+    double t[EMIT_ITEMS];  // PCQ_PRED_TIME: the GPS times (the predicate's column, in c.cls)
     bool passes[EMIT_ITEMS];
     uint32_t attr_cls[EMIT_ITEMS], attr_rg[EMIT_ITEMS], attr_b[EMIT_ITEMS];
 };
@@ -110,7 +111,8 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
     // No branch around a load: with `c.cls ? c.cls[i] : 0` in the unrolled loop every load sat in its own block and was
     // waited for at the block's end (eight serial round trips per tile).  A missing column is read from a valid address
     // with stride 0 and masked instead.
-    const bool has_cls = (ATTRS || KIND == PCQ_PRED_CLASS) && c.cls, has_rgb = ATTRS && RGB && c.rgb;
+    // (TIME: c.cls is the time column, and a time record's class is 0 — las.rs:345-355 `..Default::default()`)
+    const bool has_cls = (ATTRS || KIND == PCQ_PRED_CLASS) && c.cls && KIND != PCQ_PRED_TIME, has_rgb = ATTRS && RGB && c.rgb;
     const uint8_t *fallback = c.xyz ? c.xyz : c.cls;  // (one of the two exists: the predicate reads it)
     const uint8_t *clsp = has_cls ? c.cls : fallback, *rgbp = has_rgb ? c.rgb : fallback;
     const uint64_t cls_stride = has_cls ? c.cls_stride : 0, rgb_stride = has_rgb ? c.rgb_stride : 0;
@@ -126,7 +128,8 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
             raw_rg[j] = (uint32_t)ld_u16(q) | ((uint32_t)ld_u16(q + 2) << 16);
             raw_b[j] = ld_u16(q + 4);
         }
-        if (KIND != PCQ_PRED_CLASS) T.rps[j] = ld_xyz_stream(c, i);
+        if (KIND == PCQ_PRED_TIME) T.t[j] = ld_f64(c.cls + i * c.cls_stride);  // las.rs:334
+        else if (KIND != PCQ_PRED_CLASS) T.rps[j] = ld_xyz_stream(c, i);
     }
 #pragma unroll
     for (int j = 0; j < EMIT_ITEMS; j++) T.attr_cls[j] = raw_cls[j] & cls_mask, T.attr_rg[j] = raw_rg[j] & rg_mask, T.attr_b[j] = raw_b[j] & b_mask;
@@ -135,6 +138,7 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
         const uint64_t i = base + (uint64_t)j * BLOCK + threadIdx.x;
         bool pass;
         if (KIND == PCQ_PRED_CLASS) pass = T.attr_cls[j] == pr.cls;
+        else if (KIND == PCQ_PRED_TIME) pass = time_in(T.t[j], pr);
         else if (KIND == PCQ_PRED_BOUNDS)
             pass = (pr.empty == 0) & ((uint32_t)(T.rps[j].x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(T.rps[j].y - pr.lo[1]) <= pr.width[1]) &
                    ((uint32_t)(T.rps[j].z - pr.lo[2]) <= pr.width[2]);
@@ -155,7 +159,7 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
 // themselves behind, {x, y, z, class} as one 16-byte word each, in file order, at park[tile * park_max ..): the emit then reads
 // 16 bytes per MATCH instead of the tile's 13 bytes per POINT a second time (k_emit_parked).  The class bytes of all eight points
 // are asked for together (no load in a branch); the ranks come from the tile's 32 mask words, summed by one wave.  Only for
-// predicates on the positions (park == nullptr otherwise): a class predicate would have to read positions it does not need.
+// predicates on the positions (park == nullptr otherwise): a class or time predicate would have to read positions it does not need.
 // RGB: the file has a colour block — a second word {red | green << 16, blue, 0, 0} per match, the colours of the tile asked for
 // with the class bytes.
 // IDX (the chunk index, chunk_index.hip): 0 = none; INDEX_BOUNDS / INDEX_CLASS = the tile first takes the state of its index
@@ -209,7 +213,7 @@ __global__ __launch_bounds__(BLOCK) void k_tile_counts(DevCols c, DevPred pr, ui
 #pragma unroll
     for (int w = 0; w < WAVES; w++) total += s_w[w];
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
-    if (KIND == PCQ_PRED_CLASS || !park || total == 0 || total > park_max) return;  // (the same for the whole workgroup)
+    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME || !park || total == 0 || total > park_max) return;  // (the same for the whole workgroup)
     uint32_t cls[EMIT_ITEMS], rg[EMIT_ITEMS], bl[EMIT_ITEMS];
     {
         const uint8_t *clsp = c.cls ? c.cls : c.xyz;
@@ -340,7 +344,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_points(DevCols c, DevPred pr, co
         RawPoint (&rps)[EMIT_ITEMS] = T.rps;
         bool (&passes)[EMIT_ITEMS] = T.passes;
         uint32_t (&attr_cls)[EMIT_ITEMS] = T.attr_cls, (&attr_rg)[EMIT_ITEMS] = T.attr_rg, (&attr_b)[EMIT_ITEMS] = T.attr_b;
-        if (KIND == PCQ_PRED_CLASS) {  // positions only of the matches (last.rs:265-269), all requested together
+        if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME) {  // positions only of the matches (last.rs:265-269, las.rs:340-344), all requested together
 #pragma unroll
             for (int j = 0; j < EMIT_ITEMS; j++)
                 if (passes[j]) rps[j] = ld_xyz(c, base + (uint64_t)j * BLOCK + threadIdx.x);
@@ -468,7 +472,8 @@ __global__ __launch_bounds__(BLOCK) void k_emit_parked(DevCols c, const uint64_t
 // image: 0.72 ms for 1.6 M records against 0.29 ms for the count pass alone.  Here ONE WAVE takes a tile and only its match
 // bits (launch 1 left them): lane L owns points 32 L .. 32 L + 31, ranks come from a scan of the lanes' popcounts, and a
 // match's position and attributes are loaded and its 31 bytes stored straight from registers.  Nothing else of the tile is read.
-template <bool RGB>
+// CLS: the record carries the class byte of c.cls; false for a time predicate (c.cls is the time column, the class is 0).
+template <bool RGB, bool CLS = true>
 __global__ __launch_bounds__(BLOCK) void k_emit_sparse(DevCols c, const uint64_t *__restrict__ offsets, const uint64_t *__restrict__ bits,
                                                        const uint64_t *__restrict__ d_npoints_in, uint8_t *__restrict__ out31, uint32_t ntiles,
                                                        uint32_t parked_max, uint32_t sparse_max) {
@@ -494,6 +499,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_sparse(DevCols c, const uint64_t
         pcq_point pt;
         make_point(c, i, ld_xyz(c, i), pt);  // last.rs:137-163
         if (!RGB) pt.r = pt.g = pt.b = 0;
+        if (!CLS) pt.classification = 0;  // las.rs:345-355
         store_point31(out31 + rec * 31ull, pt);
         rec++;
     }
@@ -512,6 +518,7 @@ int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &p
     if (rc) return rc;
     if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_CLASS>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
+    else if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_TIME>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     else hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS_F64>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, d_count);
     PCQ_HIP(hipGetLastError());
@@ -528,7 +535,7 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     const uint64_t npieces = (ntiles + SCAN_PIECE - 1) / SCAN_PIECE;
     if (npieces > 1024) return pcq_fail(PCQ_ERR_ARG, "scan chunk too large (%llu points)", (unsigned long long)cols.n);
     // thin tiles park their matches (k_tile_counts): positions predicate; 16 (with a colour block: 32) bytes x park_max per tile, a sixth of the input
-    uint32_t park_max = pred.kind != PCQ_PRED_CLASS && cols.xyz && ctx->emit_park_max > 0 ? (uint32_t)ctx->emit_park_max : 0u;
+    uint32_t park_max = pred.kind != PCQ_PRED_CLASS && pred.kind != PCQ_PRED_TIME && cols.xyz && ctx->emit_park_max > 0 ? (uint32_t)ctx->emit_park_max : 0u;
     const size_t base_words = (size_t)(2 * ntiles + npieces + 2 + ntiles * (EMIT_ITEMS * WAVES));  // counts | offsets (+ total) | piece sums | match bits
     int rc = pcq_ensure_partials(ctx, base_words + 2 + (size_t)ntiles * park_max * (cols.rgb ? 4 : 2));  // | parked matches (16-byte aligned)
     if (rc && park_max) {  // no room for the parked matches (a sixth of the input): the thin tiles are read a second time instead
@@ -549,6 +556,7 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     } else if (ix && pred.kind == PCQ_PRED_CLASS && ix->hist)
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false, INDEX_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_TIME, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_BOUNDS && park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
@@ -564,6 +572,7 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     } while (0)
     if (pred.kind == PCQ_PRED_BOUNDS) PCQ_EMIT(PCQ_PRED_BOUNDS);
     else if (pred.kind == PCQ_PRED_CLASS) PCQ_EMIT(PCQ_PRED_CLASS);
+    else if (pred.kind == PCQ_PRED_TIME) PCQ_EMIT(PCQ_PRED_TIME);
     else PCQ_EMIT(PCQ_PRED_BOUNDS_F64);
 #undef PCQ_EMIT
     if (park_max) {  // tiles with 1 .. park_max matches: from the 16-byte words the count pass left
@@ -572,7 +581,8 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     }
     if (sparse_max > park_max) {  // tiles with 1 .. sparse_max matches: a wave each, from the match bits (same stream: behind the scan of the offsets)
         const dim3 gs((unsigned)((ntiles + WAVES - 1) / WAVES));
-        if (cols.rgb) hipLaunchKernelGGL(k_emit_sparse<true>, gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
+        if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL((k_emit_sparse<false, false>), gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
+        else if (cols.rgb) hipLaunchKernelGGL(k_emit_sparse<true>, gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
         else hipLaunchKernelGGL(k_emit_sparse<false>, gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
     }
     PCQ_HIP(hipGetLastError());

@@ -143,6 +143,21 @@ extern "C" int pcq_query_search_file_class(const char *path, uint8_t cls, int op
     return done(ClassSearcher(cls).search_file(path, optimized ? SearchImplementation::Optimized : SearchImplementation::Regular, *c->c));
 }
 
+extern "C" int pcq_query_search_file_time(const char *path, double start, double end, int optimized, pcq_host_collector *c) {
+    if (!path || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    return done(TimeSearcher(start, end).search_file(path, optimized ? SearchImplementation::Optimized : SearchImplementation::Regular, *c->c));
+}
+
+extern "C" int pcq_query_test_plan_time(const char *path, double start, double end, pcq_columns *cols, pcq_predicate *pred, int *needs_gpu) {
+    if (!path || !cols || !pred || !needs_gpu) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    std::optional<FilePlan> plan = TimeSearcher(start, end).plan_file(path, SearchImplementation::Optimized);
+    if (!plan) return done(Status::Err(PCQ_ERR_ARG, "no host plan for this file"));
+    *needs_gpu = plan->needs_gpu ? 1 : 0;
+    *cols = plan->cols;
+    *pred = plan->pred;
+    return done(plan->status);
+}
+
 extern "C" int pcq_query_test_plan_replace_execute(const char *path, const char *replacement, const double bmin[3], const double bmax[3],
                                                    pcq_host_collector *c) {
     if (!path || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

@@ -11,6 +11,8 @@
 //   search_{last,las}_file_by_{bounds,classification}_optimized
 //                                                    query/src/search/last.rs:46-166, 213-293
 //                                                    query/src/search/las.rs:52-148, 192-261
+//   search_{las,last}_file_by_time_range_optimized  query/src/search/las.rs:297-358 (LAST: last.rs:339-400 is a
+//                                                    todo!() stub; the LAST form here is DESIGN.md §8)
 //   search_lazer_file_by_{bounds,classification}     query/src/search/lazer.rs:34-116
 //   trait PointDumper, IgnoreDumper, FileDumper      query/src/dump_points.rs:13-121
 //   get_all_input_files, parse_aabb, get_total_bounds, run_search_sequential,
@@ -180,6 +182,11 @@ Status search_last_file_by_bounds_optimized(const std::string &path, const AABB 
 Status search_last_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
 Status search_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc, SearchLog *log);
 Status search_las_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
+// GPS time in [start, end) (Range<f64>::contains): las.rs:297-358; the LAST form reads the transposed time block
+FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end);
+FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end);
+Status search_las_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
+Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
 // search/lazer.rs:34-116 over readers/src/lazer_reader.rs (one implementation for both --optimized settings)
 Status search_lazer_file_by_bounds(const std::string &path, const AABB &bounds, ResultCollector &rc);
 Status search_lazer_file_by_classification(const std::string &path, uint8_t cls, ResultCollector &rc);
@@ -215,6 +222,17 @@ public:
 
 private:
     uint8_t class_;
+};
+// Not wired into the reference's searcher.rs (its time searches are unused there): GPS time in [start, end)
+class TimeSearcher : public Searcher {
+public:
+    TimeSearcher(double start, double end) : start_(start), end_(end) {}
+    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
+                       SearchLog *log = nullptr) const override;
+    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
+
+private:
+    double start_, end_;
 };
 
 // ---- dump_points.rs ----------------------------------------------------------------------------------

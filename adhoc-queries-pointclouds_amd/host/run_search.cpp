@@ -414,7 +414,7 @@ Status run_search_parallel(const std::vector<std::string> &files, const Searcher
         const char *policy = getenv("PCQ_MERGE");
         double planned_bytes = 0;
         for (size_t w : work)
-            if (plans[w]) planned_bytes += (double)plans[w]->cols.n * (plans[w]->pred.kind == PCQ_PRED_CLASS ? 1.0 : 12.0);
+            if (plans[w]) planned_bytes += (double)plans[w]->cols.n * (plans[w]->pred.kind == PCQ_PRED_CLASS ? 1.0 : plans[w]->pred.kind == PCQ_PRED_TIME ? 8.0 : 12.0);
         const double scan_seconds = planned_bytes / (40e9 * (double)devices.size());
         merge_rccl = opt.test_allreduce_fail != 0 || (policy && !strcmp(policy, "rccl"));
         // RCCL's NCCL_DEBUG output belongs on stderr (collective.hip); the environment is written HERE, before any other thread
@@ -567,7 +567,7 @@ Status run_search_parallel(const std::vector<std::string> &files, const Searcher
 // ---- main.rs:191-319 ---------------------------------------------------------------------------------------------
 int query_main(int argc, const char *const *argv, const PrintFn &out, const PrintFn &err, const RunOptions *test_hooks) {
     const auto t_start = std::chrono::steady_clock::now();  // :192
-    std::optional<std::string> input, bounds_s, class_s, output, density_s, stats_json;
+    std::optional<std::string> input, bounds_s, class_s, time_s, output, density_s, stats_json;
     std::vector<FileStat> file_stats;
     bool parallel = false, optimized = false;
     RunOptions opt;
@@ -581,6 +581,7 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
         if (a == "-i" || a == "--input") dst = &input;
         else if (a == "--bounds") dst = &bounds_s;
         else if (a == "--class") dst = &class_s;
+        else if (a == "--time") dst = &time_s;  // not in the reference's CLI: its time searches are not wired
         else if (a == "-o" || a == "--output") dst = &output;
         else if (a == "--density") dst = &density_s;
         else if (a == "--parallel") { parallel = true; continue; }
@@ -591,6 +592,7 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
             out("I/O experiments 0.1\nLAS I/O experiments (MI355X-native predicate path)\n\nUSAGE:\n    query [FLAGS] [OPTIONS] --input <FILE>\n\n"
                 "FLAGS:\n        --optimized    Run search with optimized implementation\n        --parallel     Run search in parallel\n\n"
                 "OPTIONS:\n        --bounds <BOUNDS>    \"minX;minY;minZ;maxX;maxY;maxZ\"\n        --class <CLASS>      object class (u8)\n"
+                "        --time <TIME>        \"start;end\": GPS time range, start <= t < end\n"
                 "        --density <DENSITY>  maximum density (grid cell size)\n    -i, --input <FILE>       file or directory\n"
                 "    -o, --output <OUTPUT>    output directory\n        --gpus <N>           (extra) number of GPUs to shard files over\n"
                 "        --device <D>         (extra) first GPU to use\n        --threads-per-gpu <T> (extra) host threads feeding each GPU (default: 1; 2 for many small files with --density)\n"
@@ -673,6 +675,18 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
         }
         maybe_class = (uint8_t)v;
     }
+    std::optional<std::pair<double, double>> maybe_time;
+    if (time_s) {  // "START;END", each component parsed like those of --bounds
+        const std::string &s = *time_s;
+        const size_t semi = s.find(';');
+        double t0 = 0, t1 = 0;
+        if (semi == std::string::npos || s.find(';', semi + 1) != std::string::npos || !parse_f64(s.substr(0, semi), &t0) ||
+            !parse_f64(s.substr(semi + 1), &t1)) {
+            err("Could not prase argument TIME");
+            return 101;
+        }
+        maybe_time = std::make_pair(t0, t1);
+    }
     std::optional<double> maybe_density;
     if (density_s) {  // :237
         double d;
@@ -686,14 +700,19 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
         err("Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify either BOUNDS or CLASS argument!");
         return 1;
     }
-    if (!maybe_bounds && !maybe_class) {  // :242-244
+    if (maybe_time && (maybe_bounds || maybe_class)) {
+        err("Error: Specifying TIME together with BOUNDS or CLASS is invalid! Specify exactly one of BOUNDS, CLASS or TIME!");
+        return 1;
+    }
+    if (!maybe_bounds && !maybe_class && !maybe_time) {  // :242-244
         err("Error: Found neither BOUNDS nor CLASS argument but exactly one of these arguments is required!");
         return 1;
     }
 
     std::unique_ptr<Searcher> searcher;  // :246-251
     if (maybe_bounds) searcher = std::make_unique<BoundsSearcher>(*maybe_bounds);
-    else searcher = std::make_unique<ClassSearcher>(*maybe_class);
+    else if (maybe_class) searcher = std::make_unique<ClassSearcher>(*maybe_class);
+    else searcher = std::make_unique<TimeSearcher>(maybe_time->first, maybe_time->second);
 
     CollectorFactoryFn factory;  // :253-273
     if (maybe_density) {

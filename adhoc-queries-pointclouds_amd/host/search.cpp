@@ -329,6 +329,85 @@ Status search_las_file_by_classification_optimized(const std::string &path, uint
     return execute_plan(plan, rc);
 }
 
+// ---- las.rs:297-358 (and its LAST counterpart, a todo!() stub at last.rs:339-400) -------------------------------
+namespace {
+// The prologue of _search_las_file_by_time_range_optimized: header (raw format, las.rs:302-303) and the GPS time's offset in
+// a record by format (:305-330).  A format above 10 is reported as the reference's match arm does — "Invalid LAS format"
+// (:324-329) — not as the header parser's error.
+Status time_prologue(const MappedFile &file, const std::string &path, LasHeader *h, uint64_t *time_in_point) {
+    Status st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, h);
+    if (!st.ok()) {
+        if (st.message.rfind("invalid point format number: ", 0) == 0) return invalid_format(file.data()[104], path);  // (the format byte)
+        return st;
+    }
+    const uint8_t fmt = h->point_data_record_format;
+    if (fmt == 0 || fmt == 2) return Status::Err(PCQ_ERR_FORMAT, "File " + path + " does not contain GPS times!");  // :306-318
+    *time_in_point = fmt <= 5 ? 20 : 22;  // :313, :319-320
+    return Status::Ok();
+}
+pcq_predicate time_predicate(double start, double end) {
+    pcq_predicate pred{};
+    pred.kind = PCQ_PRED_TIME;
+    pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (:336)
+    pred.wmax[0] = end;
+    return pred;
+}
+}  // namespace
+
+FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end) {
+    auto holder = std::make_unique<MappedFile>();
+    MappedFile &file = *holder;
+    Status st = file.open(path);  // :302
+    if (!st.ok()) return done(st);
+    LasHeader h;
+    uint64_t t_in_point = 0;
+    st = time_prologue(file, path, &h, &t_in_point);
+    if (!st.ok()) return done(st);
+    const uint64_t n = h.number_of_points, rl = h.point_data_record_length, otp = h.offset_to_point_data;
+    if (n == 0) return done();  // (no file-level early-out: the header has no time bounds, :332)
+    if (!block_ok(file, otp, (n - 1) * rl + t_in_point + 8)) return done(eof());
+    pcq_columns cols{};
+    cols.xyz = file.data() + otp;               // :340-344
+    cols.cls = file.data() + otp + t_in_point;  // :333-334 — the predicate's column: the GPS time
+    cols.xyz_stride = cols.cls_stride = rl;
+    cols.n = n;
+    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :347-351
+    return gpu(path, file, cols, time_predicate(start, end));
+}
+Status search_las_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc) {
+    FilePlan plan = plan_las_file_by_time_range_optimized(path, start, end);
+    return execute_plan(plan, rc);
+}
+
+// LAST: the record transposed by attribute (last_reader.rs:83-144) — the times are one block of n f64 at
+// offset_to_point_data + n * 20 (formats 1, 3-5) or + n * 22 (6-10); records as in las.rs:345-355.
+FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end) {
+    auto holder = std::make_unique<MappedFile>();
+    MappedFile &file = *holder;
+    Status st = file.open(path);
+    if (!st.ok()) return done(st);
+    LasHeader h;
+    uint64_t t_in_point = 0;
+    st = time_prologue(file, path, &h, &t_in_point);
+    if (!st.ok()) return done(st);
+    const uint64_t n = h.number_of_points, otp = h.offset_to_point_data;
+    const uint64_t time_block = otp + n * t_in_point;
+    if (n == 0) return done();
+    if (!block_ok(file, otp, n * 12) || !block_ok(file, time_block, n * 8)) return done(eof());
+    pcq_columns cols{};
+    cols.xyz = file.data() + otp;
+    cols.xyz_stride = 12;
+    cols.cls = file.data() + time_block;
+    cols.cls_stride = 8;
+    cols.n = n;
+    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];
+    return gpu(path, file, cols, time_predicate(start, end));
+}
+Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc) {
+    FilePlan plan = plan_last_file_by_time_range_optimized(path, start, end);
+    return execute_plan(plan, rc);
+}
+
 // ---- searcher.rs ---------------------------------------------------------------------------------------------
 namespace {
 std::optional<std::string> extension_of(const std::string &path) {  // Path::extension().and_then(OsStr::to_str)
@@ -360,6 +439,14 @@ std::optional<FilePlan> ClassSearcher::plan_file(const std::string &path, Search
     return std::nullopt;
 }
 
+std::optional<FilePlan> TimeSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
+    const auto ext = extension_of(path);
+    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
+    if (*ext == "las") return plan_las_file_by_time_range_optimized(path, start_, end_);
+    if (*ext == "last") return plan_last_file_by_time_range_optimized(path, start_, end_);
+    return std::nullopt;
+}
+
 Status BoundsSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
                                    SearchLog *log) const {  // searcher.rs:43-90
     const auto ext = extension_of(path);
@@ -384,6 +471,20 @@ Status ClassSearcher::search_file(const std::string &path, SearchImplementation 
                              : search_last_file_by_classification_optimized(path, class_, collector);
     }
     if (*ext == "lazer") return search_lazer_file_by_classification(path, class_, collector);  // searcher.rs:144
+    if (*ext == "laz") return out_of_scope("compressed format .laz", path);
+    return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
+}
+
+Status TimeSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
+    const auto ext = extension_of(path);
+    if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
+    if (*ext == "las" || *ext == "last") {
+        if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
+        return *ext == "las" ? search_las_file_by_time_range_optimized(path, start_, end_, collector)
+                             : search_last_file_by_time_range_optimized(path, start_, end_, collector);
+    }
+    // the reference's LAZ / LAZER time searches are todo!() stubs (laz.rs:131-146, lazer.rs:115-122)
+    if (*ext == "lazer") return out_of_scope("time search in .lazer files", path);
     if (*ext == "laz") return out_of_scope("compressed format .laz", path);
     return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
 }

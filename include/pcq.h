@@ -93,10 +93,15 @@ int pcq_ctx_synchronize(pcq_ctx *ctx);
  * record (xyz +0, cls +15/+16, rgb +20/+28).
  * scale/offset are the header's (last.rs:156-160); `first_index` is the file-order index of the
  * first point of this view (used to keep "first seen wins" across chunks and files).
+ * For PCQ_PRED_TIME, `cls` / `cls_stride` name the PREDICATE'S column instead: n little-endian f64 GPS times at any
+ * byte alignment, stride >= 8 — LAST: the time block at offset_to_point_data + n*20 (formats 1, 3-5) or + n*22
+ * (6-10), stride 8; LAS: the record + 20 / + 22, stride = record length.  A time record carries no class byte.  The time
+ * column is always required; the positions only for buffer and grid collectors.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pcq_columns {
     const void *xyz;            /* n records of {i32 x, i32 y, i32 z}, little endian            */
-    const void *cls;            /* n classification bytes; may be NULL for count-only bounds scan */
+    const void *cls;            /* n classification bytes; may be NULL for count-only bounds scan
+                                   (PCQ_PRED_TIME: n f64 GPS times)                                */
     const void *rgb;            /* n records of {u16 r, u16 g, u16 b}; NULL = no colour (0,0,0)  */
     uint64_t xyz_stride;
     uint64_t cls_stride;
@@ -107,7 +112,7 @@ typedef struct pcq_columns {
     double offset[3];
 } pcq_columns;
 
-typedef enum pcq_predicate_kind { PCQ_PRED_BOUNDS = 0, PCQ_PRED_CLASS = 1, PCQ_PRED_BOUNDS_F64 = 2 } pcq_predicate_kind;
+typedef enum pcq_predicate_kind { PCQ_PRED_BOUNDS = 0, PCQ_PRED_CLASS = 1, PCQ_PRED_BOUNDS_F64 = 2, PCQ_PRED_TIME = 3 } pcq_predicate_kind;
 
 /* The predicate.
  * BOUNDS:     in the file's local integer space: lmin <= (x,y,z) <= lmax, inclusive, compared as i64
@@ -117,7 +122,12 @@ typedef enum pcq_predicate_kind { PCQ_PRED_BOUNDS = 0, PCQ_PRED_CLASS = 1, PCQ_P
  * BOUNDS_F64: in world space, the reference's non-integer form used by the LAZER scan
  *             (query/src/search/lazer.rs:65-69 on positions rebuilt as offset + scale * x,
  *             readers/src/lazer_reader.rs:600-607): wmin <= world <= wmax per axis, inclusive
- *             (pasture AABB::contains). */
+ *             (pasture AABB::contains).
+ * TIME:       GPS time in [wmin[0], wmax[0]), half-open, IEEE compares on f64 (Range<f64>::contains of
+ *             query/src/search/las.rs:297-358): a NaN time or bound matches nothing, wmin[0] >= wmax[0] is an empty
+ *             range (no error), -0.0 == 0.0.  The other fields are ignored.  The time column is passed in
+ *             pcq_columns.cls (see there); a match's record is the position with class 0 and colour (0,0,0)
+ *             (`..Default::default()`, las.rs:345-355), so `rgb` is ignored. */
 typedef struct pcq_predicate {
     int32_t kind;               /* pcq_predicate_kind */
     uint8_t cls;
@@ -211,7 +221,7 @@ int pcq_prepare_host_scans(pcq_ctx *ctx);
 /* Count-only scan of many device-resident LAST files in ONE launch (files = independent units,
  * main.rs:153-161): segment i is scanned with preds[i] (all bounds, over 16-byte aligned positions
  * blocks — or all class, over classification blocks of any alignment); the total is ADDED to
- * *device_total. */
+ * *device_total.  PCQ_PRED_TIME is refused (PCQ_ERR_ARG). */
 int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
                              size_t nsegments, uint64_t *device_total, void *stream);
 
@@ -228,7 +238,8 @@ int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_pr
  * chunk (a disjoint one is then skipped by the emit as well; a contained one is read once, for its
  * records), and the ragged tail behind the last whole bounds chunk is always read.  Results are
  * identical to pcq_scan_dev; layouts the index does not cover fall through to it: strided / LAS
- * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).
+ * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME
+ * has no index: it is served by pcq_scan_dev, and the statistics of such a scan are all zero.
  * Statistics of the last scan, in index chunks: for a count scan what it read; for a buffer scan the
  * chunks its count pass skipped (disjoint), took whole (contained) and read (straddling); after a
  * build, every chunk was read.  They are collected on the device and fetched (one wait) when asked.

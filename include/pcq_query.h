@@ -3,6 +3,7 @@
  * can call the file-level operators of the reference by name:
  *
  *   Searcher::search_file for BoundsSearcher / ClassSearcher     query/src/search/searcher.rs:24-152
+ *   ... and TimeSearcher (GPS time range)                         query/src/search/las.rs:297-358
  *   CountCollector / BufferCollector / GridSampledCollector      query/src/collect_points.rs:14-127
  *   parse_aabb, get_all_input_files, is_valid_file, get_total_bounds   query/src/main.rs:29-120, 185-189
  *
@@ -68,6 +69,10 @@ int pcq_query_collector_grid_cells(pcq_host_collector *c, uint64_t *out, uint64_
 int pcq_query_search_file_bounds(const char *path, const double bmin[3], const double bmax[3], int optimized,
                                  pcq_host_collector *c, int *las_record_size);
 int pcq_query_search_file_class(const char *path, uint8_t cls, int optimized, pcq_host_collector *c);
+/* TimeSearcher::search_file: GPS time in [start, end) (query/src/search/las.rs:297-358; not wired into the reference's
+ * searcher.rs).  .las / .last with optimized = 1; matches are recorded with class 0 and colour (0,0,0).  A file of format 0
+ * or 2, or above 10, is PCQ_ERR_FORMAT; .laz / .lazer and the Regular implementation are PCQ_ERR_UNSUPPORTED. */
+int pcq_query_search_file_time(const char *path, double start, double end, int optimized, pcq_host_collector *c);
 
 /* A dataset resident in HBM (host/resident.cpp; not in the reference, which re-reads the files for every query): the
  * positions and classification blocks of LAST files are loaded into `device`'s HBM once; every count query over them
@@ -109,6 +114,10 @@ int pcq_query_main(int argc, const char *const *argv);
 int pcq_query_main_with_hooks(int argc, const char *const *argv, const char *device_slots, int allreduce_fail);
 int pcq_query_simulate_schedule(const uint64_t *cost, size_t nfiles, const double *ready_ms, int nslots, double ms_per_unit,
                                 int *slot_of_file, int *home_slot, double *makespan_ms);
+/* Test entry: the host-only plan of a time search (TimeSearcher, optimized) of a .las / .last file — what search_file decides
+ * before any GPU work.  Returns the plan's status; *needs_gpu = 1 when a scan would follow, with its columns (the pointers are
+ * BYTE OFFSETS into the file) and predicate.  Wakes no GPU. */
+int pcq_query_test_plan_time(const char *path, double start, double end, pcq_columns *cols, pcq_predicate *pred, int *needs_gpu);
 /* Test entry: the two halves of a LAST bounds search with something in between — the file's plan is made (header, offsets,
  * box: the host prologue of run_search_parallel), then, if `replacement` is not NULL, that file is renamed over `path`, then the
  * plan is executed.  A plan must not be executed on another file under the same name. */
