@@ -19,7 +19,7 @@ PCQ_OK = 0
 PCQ_ERR_IO, PCQ_ERR_HEADER, PCQ_ERR_FORMAT, PCQ_ERR_EXTENSION, PCQ_ERR_EOF = -1, -2, -3, -4, -5
 PCQ_ERR_GRID, PCQ_ERR_PANIC, PCQ_ERR_ARG, PCQ_ERR_HIP, PCQ_ERR_CAPACITY = -6, -7, -8, -9, -10
 PCQ_ERR_UNSUPPORTED, PCQ_ERR_NOMEM = -11, -12
-PRED_BOUNDS, PRED_CLASS, PRED_BOUNDS_F64, PRED_TIME = 0, 1, 2, 3
+PRED_BOUNDS, PRED_CLASS, PRED_BOUNDS_F64, PRED_TIME, PRED_BOUNDS_CLASS, PRED_BOUNDS_TIME = 0, 1, 2, 3, 4, 5
 
 # readers/src/lib.rs:10-19 — packed 31-byte result record
 POINT_DTYPE = np.dtype(
@@ -81,6 +81,23 @@ class Predicate(C.Structure):
         """GPS time in [start, end) (Range<f64>::contains); the time column goes in Columns.cls (cls_stride >= 8)."""
         p = Predicate()
         p.kind = PRED_TIME
+        p.wmin[0] = float(start)
+        p.wmax[0] = float(end)
+        return p
+
+    @staticmethod
+    def bounds_class(lmin, lmax, cls: int) -> "Predicate":
+        """The local box AND the class byte (PCQ_PRED_BOUNDS_CLASS): positions and class bytes are both read, even for a count."""
+        p = Predicate.bounds(lmin, lmax)
+        p.kind = PRED_BOUNDS_CLASS
+        p.cls = int(cls)
+        return p
+
+    @staticmethod
+    def bounds_time(lmin, lmax, start: float, end: float) -> "Predicate":
+        """The local box AND GPS time in [start, end) (PCQ_PRED_BOUNDS_TIME); the time column goes in Columns.cls (cls_stride >= 8)."""
+        p = Predicate.bounds(lmin, lmax)
+        p.kind = PRED_BOUNDS_TIME
         p.wmin[0] = float(start)
         p.wmax[0] = float(end)
         return p

@@ -422,7 +422,7 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: null argument");
     if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count and buffer collectors only");
-    if (pred->kind == PCQ_PRED_TIME) {  // no time index: the plain scan, and statistics that claim nothing
+    if (pred->kind == PCQ_PRED_TIME || pred_is_combined(pred->kind)) {  // no index of these: the plain scan, statistics that claim nothing
         ix->last = pcq_index_stats{};
         ix->stats_stream = nullptr;
         ix->stats_kind = 0;

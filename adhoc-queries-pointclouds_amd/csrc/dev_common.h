@@ -30,6 +30,11 @@ __device__ __forceinline__ bool time_in(double t, const DevPred &pr) { return (t
 struct RawPoint {
     int32_t x, y, z;
 };
+// The integer box of last.rs:122-135 (BOUNDS, and the box half of the combined kinds).
+__device__ __forceinline__ bool box_in(const RawPoint &rp, const DevPred &pr) {
+    return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
+           ((uint32_t)(rp.z - pr.lo[2]) <= pr.width[2]);
+}
 
 struct __attribute__((packed, aligned(4))) PackedXYZ {
     int32_t x, y, z;
@@ -84,6 +89,13 @@ __device__ __forceinline__ bool eval_pred(const DevCols &c, const DevPred &pr, u
         return !((wx < pr.wmin[0]) | (wy < pr.wmin[1]) | (wz < pr.wmin[2]) | (wx > pr.wmax[0]) | (wy > pr.wmax[1]) |
                  (wz > pr.wmax[2]));
     }
+    if (pr.kind == PCQ_PRED_BOUNDS_CLASS || pr.kind == PCQ_PRED_BOUNDS_TIME) {  // the box AND the attribute in c.cls
+        rp = ld_xyz(c, i);
+        have_xyz = true;
+        const bool attr = pr.kind == PCQ_PRED_BOUNDS_TIME ? time_in(ld_f64(c.cls + i * c.cls_stride), pr)
+                                                          : (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
+        return (int)box_in(rp, pr) & (int)attr;
+    }
     have_xyz = false;
     if (pr.kind == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
@@ -96,6 +108,8 @@ __device__ __forceinline__ bool eval_pred_kind(const DevCols &c, const DevPred &
     if (KIND == PCQ_PRED_CLASS) return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
     if (KIND == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);  // (the time column rides in cls)
     const RawPoint rp = ld_xyz(c, i);
+    if (KIND == PCQ_PRED_BOUNDS_CLASS) return (int)box_in(rp, pr) & (int)((uint32_t)c.cls[i * c.cls_stride] == pr.cls);
+    if (KIND == PCQ_PRED_BOUNDS_TIME) return (int)box_in(rp, pr) & (int)time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
                ((uint32_t)(rp.z - pr.lo[2]) <= pr.width[2]);
@@ -110,6 +124,8 @@ __device__ __forceinline__ bool eval_pred_kind(const DevCols &c, const DevPred &
     if (KIND == PCQ_PRED_CLASS) return (uint32_t)c.cls[i * c.cls_stride] == pr.cls;
     if (KIND == PCQ_PRED_TIME) return time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     rp = ld_xyz(c, i);
+    if (KIND == PCQ_PRED_BOUNDS_CLASS) return (int)box_in(rp, pr) & (int)((uint32_t)c.cls[i * c.cls_stride] == pr.cls);
+    if (KIND == PCQ_PRED_BOUNDS_TIME) return (int)box_in(rp, pr) & (int)time_in(ld_f64(c.cls + i * c.cls_stride), pr);
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
                ((uint32_t)(rp.z - pr.lo[2]) <= pr.width[2]);

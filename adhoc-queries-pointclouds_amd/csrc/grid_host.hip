@@ -135,10 +135,10 @@ int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols_in, const 
         for (int a = 0; a < 3; a++) e.scale[a] = cols.scale[a], e.offset[a] = cols.offset[a], e.lo[a] = 0, e.cmask[a] = 0xffffffffu;
         e.fmt = FMT_NONE | FMT_NONE << 8 | FMT_NONE << 16;
         bool narrow = !wide && ctx->grid_tuple16 != 0;
-        if (pred.kind == PCQ_PRED_TIME) {
+        if (pred_tests_time(pred.kind)) {
             narrow = true;  // a time record is colourless with class 0 (las.rs:345-355): the 16-byte tuple, whatever grid_tuple16 says
             e.cls_const = 0;
-        } else if (narrow && pred.kind == PCQ_PRED_CLASS) {
+        } else if (narrow && (pred.kind == PCQ_PRED_CLASS || pred.kind == PCQ_PRED_BOUNDS_CLASS)) {  // every match has class pred.cls
             e.cls_const = pred.cls & 0xffu;
         } else if (narrow && pred.kind == PCQ_PRED_BOUNDS) {
             int axis = 0;
@@ -213,7 +213,7 @@ int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols_in, const 
         // LAST blocks (12-byte positions at an aligned address, a class byte per point, 6-byte colours): the short index arithmetic
         // (TIME: the time column in cls, 8-byte aligned f64s)
         const bool packed = cols.xyz_stride == 12 && ((uintptr_t)cols.xyz & 3) == 0 && (!cols.rgb || cols.rgb_stride == 6) &&
-                            (pred.kind == PCQ_PRED_TIME ? cols.cls_stride == 8 && ((uintptr_t)cols.cls & 7) == 0 : (!cols.cls || cols.cls_stride == 1));
+                            (pred_tests_time(pred.kind) ? cols.cls_stride == 8 && ((uintptr_t)cols.cls & 7) == 0 : (!cols.cls || cols.cls_stride == 1));
 #define PCQ_P0_LAUNCH(KIND, RGB, PACKED, WIDE) \
     hipLaunchKernelGGL((k_p0_part<KIND, RGB, PACKED, WIDE>), dim3(nblocks), dim3(P0_NT), 0, s, (P0Args{cols, pred, g, pk16, run.tuples, run.dir, ntiles, tile0, agg}))
 #define PCQ_P0(KIND)                                                          \
@@ -227,9 +227,13 @@ int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols_in, const 
     } while (0)
         if (pred.kind == PCQ_PRED_BOUNDS) PCQ_P0(PCQ_PRED_BOUNDS);
         else if (pred.kind == PCQ_PRED_CLASS) PCQ_P0(PCQ_PRED_CLASS);
+        else if (pred.kind == PCQ_PRED_BOUNDS_CLASS) PCQ_P0(PCQ_PRED_BOUNDS_CLASS);
         else if (pred.kind == PCQ_PRED_TIME) {
             if (packed) PCQ_P0_LAUNCH(PCQ_PRED_TIME, false, true, false);
             else PCQ_P0_LAUNCH(PCQ_PRED_TIME, false, false, false);
+        } else if (pred.kind == PCQ_PRED_BOUNDS_TIME) {
+            if (packed) PCQ_P0_LAUNCH(PCQ_PRED_BOUNDS_TIME, false, true, false);
+            else PCQ_P0_LAUNCH(PCQ_PRED_BOUNDS_TIME, false, false, false);
         } else PCQ_P0(PCQ_PRED_BOUNDS_F64);
 #undef PCQ_P0
 #undef PCQ_P0_LAUNCH

@@ -5,7 +5,8 @@ namespace pcqgrid {
 // ---------------------------------------------------------------------------------------------------------------
 // pass 0: one reading of a scan's points -> per tile one block of tuples sorted by level-1 bin + a directory row
 // ---------------------------------------------------------------------------------------------------------------
-// What the predicate reads of a point: its position (bounds kinds), its class byte or its GPS time (TIME: in c.cls).
+// What the predicate reads of a point: its position (bounds kinds), its class byte or its GPS time (TIME: in c.cls); the
+// combined kinds read the position and the attribute.
 template <int KIND>
 struct P0In {
     RawPoint rp;
@@ -15,9 +16,9 @@ struct P0In {
 template <int KIND>
 __device__ __forceinline__ P0In<KIND> p0_load(const DevCols &c, uint64_t i) {
     P0In<KIND> in;
-    if (KIND == PCQ_PRED_CLASS) in.cls = c.cls[i * c.cls_stride];
-    else if (KIND == PCQ_PRED_TIME) in.t = ld_f64(c.cls + i * c.cls_stride);
-    else in.rp = ld_xyz_stream(c, i);
+    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_BOUNDS_CLASS) in.cls = c.cls[i * c.cls_stride];
+    if (pred_tests_time(KIND)) in.t = ld_f64(c.cls + i * c.cls_stride);
+    if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME) in.rp = ld_xyz_stream(c, i);
     return in;
 }
 // The same for point `li` of the tile that starts at point `base` (li clamped to the tile's last point).  PACKED: the
@@ -30,11 +31,9 @@ __device__ __forceinline__ P0In<KIND> p0_load_tile(const DevCols &c, uint64_t ba
     const uint32_t lc = li < nvalid ? li : nvalid - 1;
     if (!PACKED) return p0_load<KIND>(c, base + lc);
     P0In<KIND> in;
-    if (KIND == PCQ_PRED_CLASS) {
-        in.cls = *(const PCQ_GLOBAL uint8_t *)(c.cls + base + lc);
-    } else if (KIND == PCQ_PRED_TIME) {
-        in.t = *(const PCQ_GLOBAL double *)(c.cls + base * 8 + lc * 8u);
-    } else {
+    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_BOUNDS_CLASS) in.cls = *(const PCQ_GLOBAL uint8_t *)(c.cls + base + lc);
+    if (pred_tests_time(KIND)) in.t = *(const PCQ_GLOBAL double *)(c.cls + base * 8 + lc * 8u);
+    if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME) {
         const i32x3_a4 v = __builtin_nontemporal_load(reinterpret_cast<const i32x3_a4 *>(c.xyz + base * 12 + lc * 12u));  // (sizeof(i32x3) is 16: bytes, not elements)
         in.rp.x = v.x, in.rp.y = v.y, in.rp.z = v.z;
     }
@@ -44,6 +43,8 @@ template <int KIND>
 __device__ __forceinline__ bool p0_pass(const DevCols &c, const DevPred &pr, const P0In<KIND> &in) {
     if (KIND == PCQ_PRED_CLASS) return in.cls == pr.cls;
     if (KIND == PCQ_PRED_TIME) return time_in(in.t, pr);
+    if (KIND == PCQ_PRED_BOUNDS_CLASS) return (int)box_in(in.rp, pr) & (int)(in.cls == pr.cls);
+    if (KIND == PCQ_PRED_BOUNDS_TIME) return (int)box_in(in.rp, pr) & (int)time_in(in.t, pr);
     const RawPoint &rp = in.rp;
     if (KIND == PCQ_PRED_BOUNDS)
         return (pr.empty == 0) & ((uint32_t)(rp.x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(rp.y - pr.lo[1]) <= pr.width[1]) &
@@ -51,6 +52,13 @@ __device__ __forceinline__ bool p0_pass(const DevCols &c, const DevPred &pr, con
     const double wx = c.offset[0] + c.scale[0] * (double)rp.x, wy = c.offset[1] + c.scale[1] * (double)rp.y,
                  wz = c.offset[2] + c.scale[2] * (double)rp.z;
     return !((wx < pr.wmin[0]) | (wy < pr.wmin[1]) | (wz < pr.wmin[2]) | (wx > pr.wmax[0]) | (wy > pr.wmax[1]) | (wz > pr.wmax[2]));
+}
+// The inputs are used here: every load of them has landed (the wait stands where this is called).
+template <int KIND>
+__device__ __forceinline__ void p0_arrived(P0In<KIND> &in) {
+    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_BOUNDS_CLASS) asm volatile("" ::"v"(in.cls));
+    if (pred_tests_time(KIND)) asm volatile("" ::"v"(in.t));
+    if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME) asm volatile("" ::"v"(in.rp.x), "v"(in.rp.y), "v"(in.rp.z));
 }
 __device__ __forceinline__ uint64_t key_only(const DevGrid &g, double px, double py, double pz) {
     const CellFast cf = cell_fast(g, px, py, pz);
@@ -125,9 +133,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
     }
 #pragma unroll
     for (int j = 0; j < ITEMS; j++) {  // (arrived: inside the loop nothing is pending at its head)
-        if (KIND == PCQ_PRED_CLASS) asm volatile("" ::"v"(cur[j].cls));
-        else if (KIND == PCQ_PRED_TIME) asm volatile("" ::"v"(cur[j].t));
-        else asm volatile("" ::"v"(cur[j].rp.x), "v"(cur[j].rp.y), "v"(cur[j].rp.z));
+        p0_arrived<KIND>(cur[j]);
     }
     for (; tile < ntiles; tile += gridDim.x, parity ^= 1) {
         const DevCols c = karg<DevCols>(karg_base(), offsetof(P0Args, c));
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
             const uint32_t li = (uint32_t)j * NT + tid;
             const uint64_t i = base + li;
             passes[j] = li < nvalid && p0_pass<KIND>(c, pr, cur[j]);
-            rg[j] = 0, bb[j] = 0, cl[j] = KIND == PCQ_PRED_CLASS ? cur[j].cls : 0;
+            rg[j] = 0, bb[j] = 0, cl[j] = KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_BOUNDS_CLASS ? cur[j].cls : 0;
             pk[j] = 0, metas[j] = 0, ranks[j] = 0;
             if (!passes[j]) continue;
             if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME) {  // positions only of the matches (las.rs:340-344)
@@ -166,7 +172,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
                 bb[j] = ld_u16(q + 4);
             }
             // last.rs:138-142 (TIME: c.cls is the time column; a time record's class is 0, las.rs:345-355)
-            if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME && c.cls) cl[j] = PACKED ? *(const PCQ_GLOBAL uint8_t *)(c.cls + base + li) : c.cls[i * c.cls_stride];
+            if ((KIND == PCQ_PRED_BOUNDS || KIND == PCQ_PRED_BOUNDS_F64) && c.cls) cl[j] = PACKED ? *(const PCQ_GLOBAL uint8_t *)(c.cls + base + li) : c.cls[i * c.cls_stride];
         }
         if (agg)
             for (uint32_t k = tid; k < (uint32_t)AGG_SLOTS; k += NT) s_atab[k] = ~0ull;
@@ -278,9 +284,7 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
 #pragma unroll
         for (int j = 0; j < ITEMS; j++) {  // the next tile's inputs have arrived (asked for a whole tile ago) — before the stores below
             cur[j] = nxt[j];
-            if (KIND == PCQ_PRED_CLASS) asm volatile("" ::"v"(cur[j].cls));
-            else if (KIND == PCQ_PRED_TIME) asm volatile("" ::"v"(cur[j].t));
-            else asm volatile("" ::"v"(cur[j].rp.x), "v"(cur[j].rp.y), "v"(cur[j].rp.z));
+            p0_arrived<KIND>(cur[j]);
         }
         if (tid == 0) s_npass[parity ^ 1] = 0;
         __syncthreads();
@@ -320,9 +324,12 @@ __global__ __launch_bounds__(P0_NT, 4) void k_p0_part(P0Args A) {
 PCQ_P0_INST(PCQ_PRED_BOUNDS)
 PCQ_P0_INST(PCQ_PRED_CLASS)
 PCQ_P0_INST(PCQ_PRED_BOUNDS_F64)
+PCQ_P0_INST(PCQ_PRED_BOUNDS_CLASS)
 #undef PCQ_P0_INST
 // a time record has no colour and class 0: always the 16-byte tuple
 template __global__ void k_p0_part<PCQ_PRED_TIME, false, true, false>(P0Args);
 template __global__ void k_p0_part<PCQ_PRED_TIME, false, false, false>(P0Args);
+template __global__ void k_p0_part<PCQ_PRED_BOUNDS_TIME, false, true, false>(P0Args);
+template __global__ void k_p0_part<PCQ_PRED_BOUNDS_TIME, false, false, false>(P0Args);
 
 }  // namespace pcqgrid

@@ -970,6 +970,16 @@ int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, c
     return PCQ_OK;
 }
 
+// (the combined kinds are not swept here: the strided count)
+int pcq_launch_bounds_count_xyz12_col(pcq_ctx *ctx, const void *d_xyz, const void *d_col, uint64_t n, const DevPred &pred, uint64_t *d_count,
+                                      hipStream_t s) {
+    DevCols c{};
+    c.xyz = (const uint8_t *)d_xyz, c.cls = (const uint8_t *)d_col;
+    c.xyz_stride = 12, c.cls_stride = pred.kind == PCQ_PRED_BOUNDS_TIME ? 8 : 1;
+    c.n = n;
+    return pcq_launch_generic_count(ctx, c, pred, d_count, s);
+}
+
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls, uint64_t *d_count,
                               hipStream_t s) {
     if (n == 0) return PCQ_OK;

@@ -525,12 +525,13 @@ int pcq_make_dev_pred(const pcq_predicate *p, DevPred *out) {
         for (int a = 0; a < 3; a++) out->wmin[a] = p->wmin[a], out->wmax[a] = p->wmax[a];
         return PCQ_OK;
     }
-    if (p->kind == PCQ_PRED_TIME) {  // [start, end): an empty or NaN range is legal and matches nothing
+    if (pred_tests_time(p->kind)) {  // [start, end): an empty or NaN range is legal and matches nothing
         out->wmin[0] = p->wmin[0];
         out->wmax[0] = p->wmax[0];
-        return PCQ_OK;
+        if (p->kind == PCQ_PRED_TIME) return PCQ_OK;
     }
-    if (p->kind != PCQ_PRED_BOUNDS) return pcq_fail(PCQ_ERR_ARG, "unknown predicate kind %d", p->kind);
+    if (p->kind == PCQ_PRED_BOUNDS_CLASS) out->cls = p->cls;  // (and the box below)
+    if (!pred_has_box(p->kind)) return pcq_fail(PCQ_ERR_ARG, "unknown predicate kind %d", p->kind);
     for (int a = 0; a < 3; a++) {
         const int64_t lo = p->lmin[a] < INT32_MIN ? (int64_t)INT32_MIN : p->lmin[a];
         const int64_t hi = p->lmax[a] > INT32_MAX ? (int64_t)INT32_MAX : p->lmax[a];
@@ -770,7 +771,8 @@ extern "C" int pcq_collector_grid_params(const pcq_collector *c, uint64_t dims[3
 // ---------------------------------------------------------------------------------------------
 int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c) {
     if (!cols || !pred || !c) return pcq_fail(PCQ_ERR_ARG, "scan: null argument");
-    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS && pred->kind != PCQ_PRED_BOUNDS_F64 && pred->kind != PCQ_PRED_TIME)
+    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS && pred->kind != PCQ_PRED_BOUNDS_F64 && pred->kind != PCQ_PRED_TIME &&
+        !pred_is_combined(pred->kind))
         return pcq_fail(PCQ_ERR_ARG, "scan: bad predicate kind %d", pred->kind);
     if (cols->n == 0) return PCQ_OK;
     // index arithmetic (n * stride, first_index + n) must stay far from 2^64: a LAS record length is a u16
@@ -785,6 +787,16 @@ int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const 
             return pcq_fail(PCQ_ERR_ARG, "scan: positions column missing or stride < 12");
         if (!cols->cls || cols->cls_stride < 8) return pcq_fail(PCQ_ERR_ARG, "scan: time column missing or stride < 8");
         return PCQ_OK;  // (rgb is ignored: a time record has no colour)
+    }
+    if (pred_is_combined(pred->kind)) {  // both columns are read by every scan, a count included
+        if (!cols->xyz || cols->xyz_stride < 12) return pcq_fail(PCQ_ERR_ARG, "scan: positions column missing or stride < 12");
+        if (pred->kind == PCQ_PRED_BOUNDS_TIME) {
+            if (!cols->cls || cols->cls_stride < 8) return pcq_fail(PCQ_ERR_ARG, "scan: time column missing or stride < 8");
+            return PCQ_OK;  // (rgb is ignored, as for TIME)
+        }
+        if (!cols->cls || cols->cls_stride < 1) return pcq_fail(PCQ_ERR_ARG, "scan: classification column missing");
+        if (cols->rgb && cols->rgb_stride < 6) return pcq_fail(PCQ_ERR_ARG, "scan: colour stride < 6");
+        return PCQ_OK;
     }
     const bool need_xyz = pred->kind != PCQ_PRED_CLASS || c->kind != COLL_COUNT;
     const bool need_cls = pred->kind == PCQ_PRED_CLASS || c->kind != COLL_COUNT;
@@ -811,9 +823,12 @@ static DevCols to_dev_cols(const pcq_columns *cols) {
 // Count of matches into *d_count (+=), choosing the fast kernels where the layout allows.
 static int count_into(pcq_ctx *ctx, const DevCols &dc, const DevPred &dp, uint64_t *d_count, hipStream_t s) {
     if (dc.n == 0) return PCQ_OK;
-    if (dp.kind == PCQ_PRED_BOUNDS) {
+    if (pred_has_box(dp.kind)) {  // BOUNDS, and the combined kinds: K1 (with a second column) over LAST blocks
         if (dp.empty) return PCQ_OK;
-        if (dc.xyz_stride == 12 && ((uintptr_t)dc.xyz & 3) == 0) {
+        // the combined kinds' second column: packed class bytes (any alignment) or packed, 8-byte aligned times
+        const uint64_t w = dp.kind == PCQ_PRED_BOUNDS_TIME ? 8 : 1;
+        const bool col_ok = dp.kind == PCQ_PRED_BOUNDS || (dc.cls_stride == w && ((uintptr_t)dc.cls & (w - 1)) == 0);
+        if (dc.xyz_stride == 12 && ((uintptr_t)dc.xyz & 3) == 0 && col_ok) {
             // peel the (at most 3) points in front of the first 16-byte aligned point boundary
             uint64_t head = ((uintptr_t)dc.xyz & 15) / 4;  // 12*head == -addr (mod 16)
             if (head > dc.n) head = dc.n;
@@ -823,7 +838,8 @@ static int count_into(pcq_ctx *ctx, const DevCols &dc, const DevPred &dp, uint64
                 int rc = pcq_launch_generic_count(ctx, h, dp, d_count, s);
                 if (rc) return rc;
             }
-            return pcq_launch_bounds_count_xyz12(ctx, dc.xyz + 12 * head, dc.n - head, dp, d_count, s);
+            if (dp.kind == PCQ_PRED_BOUNDS) return pcq_launch_bounds_count_xyz12(ctx, dc.xyz + 12 * head, dc.n - head, dp, d_count, s);
+            return pcq_launch_bounds_count_xyz12_col(ctx, dc.xyz + 12 * head, dc.cls + w * head, dc.n - head, dp, d_count, s);
         }
         return pcq_launch_generic_count(ctx, dc, dp, d_count, s);
     }
@@ -881,13 +897,13 @@ int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate
     rc = pcq_make_dev_pred(pred, &dp);
     if (rc) return rc;
     DevCols dc = to_dev_cols(cols);
-    if (dp.kind == PCQ_PRED_TIME) dc.rgb = nullptr, dc.rgb_stride = 0;  // a time record's colour is (0,0,0) (las.rs:345-355)
+    if (pred_tests_time(dp.kind)) dc.rgb = nullptr, dc.rgb_stride = 0;  // a time record's colour is (0,0,0) (las.rs:345-355)
     c->last_stream = s;
     switch (c->kind) {
     case COLL_COUNT:
         return count_into(ctx, dc, dp, c->d_count, s);
     case COLL_BUFFER: {
-        if (dp.kind == PCQ_PRED_BOUNDS && dp.empty) return PCQ_OK;
+        if (pred_has_box(dp.kind) && dp.empty) return PCQ_OK;
         rc = buffer_reserve(c, dc.n, s);
         if (rc) return rc;
         rc = pcq_launch_emit_points(ctx, dc, dp, c->d_points, c->d_count + c->count_slot, c->d_count + (c->count_slot ^ 1), s, ix);  // asynchronous: one pass, no count first
@@ -897,7 +913,7 @@ int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate
         return PCQ_OK;
     }
     case COLL_GRID: {
-        if (dp.kind == PCQ_PRED_BOUNDS && dp.empty) return PCQ_OK;
+        if (pred_has_box(dp.kind) && dp.empty) return PCQ_OK;
         return pcq_grid_scan(ctx, c, dc, dp, s);  // asynchronous: the matches are partitioned now and folded when a result is asked for
     }
     }
@@ -1072,11 +1088,12 @@ static int scan_host_impl(pcq_ctx *ctx, int fd, const pcq_columns *cols, const p
     PCQ_HIP(hipSetDevice(ctx->device));
 
     StagePlan pl{};
-    // the predicate's own column ("cls"): a class byte, or an f64 GPS time (PCQ_PRED_TIME) — read by every scan of that kind
-    const bool time = pred->kind == PCQ_PRED_TIME;
-    const bool pred_col = pred->kind == PCQ_PRED_CLASS || time;
+    // the predicate's own column ("cls"): a class byte, or an f64 GPS time (PCQ_PRED_TIME) — read by every scan of that kind;
+    // the combined kinds read it and the positions
+    const bool time = pred_tests_time(pred->kind);
+    const bool pred_col = pred->kind == PCQ_PRED_CLASS || time || pred_is_combined(pred->kind);
     const uint64_t w = time ? 8 : 1;  // bytes per point of that column
-    pl.need_xyz = !pred_col || c->kind != COLL_COUNT;
+    pl.need_xyz = !pred_col || pred_is_combined(pred->kind) || c->kind != COLL_COUNT;
     pl.need_cls = pred_col || c->kind != COLL_COUNT;
     pl.need_rgb = c->kind != COLL_COUNT && cols->rgb != nullptr && !time;
     const uint8_t *hx = (const uint8_t *)cols->xyz, *hc = (const uint8_t *)cols->cls, *hr = (const uint8_t *)cols->rgb;

@@ -62,8 +62,13 @@ struct DevPred {
     uint32_t width[3];
     uint32_t cls;
     uint32_t _pad;
-    double wmin[3], wmax[3];  // PCQ_PRED_BOUNDS_F64; PCQ_PRED_TIME: [wmin[0], wmax[0])
+    double wmin[3], wmax[3];  // PCQ_PRED_BOUNDS_F64; PCQ_PRED_TIME, PCQ_PRED_BOUNDS_TIME: [wmin[0], wmax[0])
 };
+// The kinds by what they test.  The combined kinds (PCQ_PRED_BOUNDS_CLASS / _TIME) test the integer box (lo, width, empty)
+// AND the attribute in pcq_columns.cls: a class byte or an f64 GPS time.
+__host__ __device__ constexpr bool pred_has_box(int k) { return k == PCQ_PRED_BOUNDS || k == PCQ_PRED_BOUNDS_CLASS || k == PCQ_PRED_BOUNDS_TIME; }
+__host__ __device__ constexpr bool pred_is_combined(int k) { return k == PCQ_PRED_BOUNDS_CLASS || k == PCQ_PRED_BOUNDS_TIME; }
+__host__ __device__ constexpr bool pred_tests_time(int k) { return k == PCQ_PRED_TIME || k == PCQ_PRED_BOUNDS_TIME; }
 
 struct DevCols {
     const uint8_t *xyz;
@@ -270,6 +275,10 @@ int pcq_ensure_partials(pcq_ctx *ctx, size_t n);
 // scan_count.hip
 int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,
                                   uint64_t *d_count, hipStream_t s);
+// K1 with a second column (PCQ_PRED_BOUNDS_CLASS: class bytes at any alignment; PCQ_PRED_BOUNDS_TIME: 8-byte aligned f64
+// times), both for the same n points; positions 16-byte aligned (+= into *d_count)
+int pcq_launch_bounds_count_xyz12_col(pcq_ctx *ctx, const void *d_xyz, const void *d_col, uint64_t n, const DevPred &pred, uint64_t *d_count,
+                                      hipStream_t s);
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls,
                               uint64_t *d_count, hipStream_t s);
 // scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)

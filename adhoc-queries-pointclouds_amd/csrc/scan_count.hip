@@ -19,6 +19,11 @@
 //    of the next step are in flight (inline-asm global_load_dwordx4 nt + counted s_waitcnt) while the
 //    current step is evaluated; per-workgroup partial counts are written with plain stores and folded by
 //    a 1-block finishing kernel, so no same-address atomic storm at the tail.
+// K1 also counts the combined kinds over LAST blocks (PCQ_PRED_BOUNDS_CLASS / _TIME): the same kernel with a compile-time
+//    second column (COL_U8: the class block, COL_F64: the time block), whose loads ride in the same software pipeline.  Each
+//    tile's 256 class bytes (one dword per lane) or 256 times (two dwordx4 per lane) are tested per lane into a verdict word;
+//    one ds_bpermute per (load, start phase) brings each point's verdict to the lane that holds its first dword, where it is
+//    ANDed into the mask algebra before the popcount.  13 / 20 B per point.
 // The kernel shapes these replaced (256-thread blocks, unpipelined one-wave forms, other tile counts) live
 // in csrc/lab/scan_count_lab.hip and are built only into libpcq_lab.so for the sweeps in tools/.
 #include <vector>
@@ -48,6 +53,99 @@ __device__ __forceinline__ constexpr uint64_t start_lanes(int s) {
 
 __device__ __forceinline__ v4i ld_nt(const v4i *p) { return __builtin_nontemporal_load(p); }
 
+// Bytes of a dword equal to zero -> 0x80 in that byte (exact, no borrow artefacts).
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {
+    const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+    return ~(t | x | 0x7f7f7f7fu);
+}
+template <int V>
+struct IntC {};
+
+// K1's second column (the combined kinds): none, class bytes, or f64 GPS times.
+enum { COL_NONE = 0, COL_U8 = 1, COL_F64 = 2 };
+
+// Per-lane constants of the second column.  A point p of a tile (0..255) has its verdict in bit vbit(p) of the verdict word
+// of lane vlane(p): COL_U8 — the class bytes of points 4l .. 4l + 3 in lane l (bits 7, 15, 23, 31: zero_bytes);
+// COL_F64 — the times of points 2l, 2l + 1 (bits 0, 1) and 128 + 2l, 129 + 2l (bits 2, 3) in lane l.  In load k of a
+// tile, lane l holds dwords 256 k + 4 l + j; the first point that starts there is pa = (256 k + 4 l + j0) / 3, and when
+// j0 == 0 a second one starts at j = 3: pa + 1.  sel_a[k] / sel_b[k]: the byte address (for ds_bpermute) of the lane
+// holding that point's verdict, and its bit in the word.
+template <int COL>
+struct Col2 {};
+template <>
+struct Col2<COL_U8> {
+    const uint8_t *base;      // the body's class bytes, rounded down to a dword (uniform)
+    uint32_t off_lo, off_hi;  // this lane's dword of a tile and the one behind it (lane 63 of an aligned column: itself)
+    uint32_t shift, pat;      // 8 x the misalignment; the class byte in every byte
+    uint32_t addr_a[3], bit_a[3], addr_b[3], bit_b[3];
+};
+template <>
+struct Col2<COL_F64> {
+    const uint8_t *base;  // the body's times (8-byte aligned)
+    double t0, t1;
+    uint32_t addr_a[3], bit_a[3], addr_b[3], bit_b[3];
+};
+template <int COL>
+__device__ __forceinline__ uint32_t vlane(uint32_t p) { return COL == COL_U8 ? p >> 2 : (p & 127) >> 1; }
+template <int COL>
+__device__ __forceinline__ uint32_t vbit(uint32_t p) { return COL == COL_U8 ? 8 * (p & 3) + 7 : 2 * (p >> 7) + (p & 1); }
+template <int COL>
+__device__ __forceinline__ void col2_lanes(Col2<COL> &c, int lane) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t j0 = (3 - (uint32_t)(k + lane) % 3) % 3;
+        const uint32_t pa = (256 * k + 4 * lane + j0) / 3, pb = (pa + 1) & 255;  // (pb: only lanes with j0 == 0 use it)
+        c.addr_a[k] = 4 * vlane<COL>(pa), c.bit_a[k] = vbit<COL>(pa);
+        c.addr_b[k] = 4 * vlane<COL>(pb), c.bit_b[k] = vbit<COL>(pb);
+    }
+}
+__device__ __forceinline__ Col2<COL_U8> col2_setup(const uint8_t *col, const DevPred &pred, int lane, IntC<COL_U8>) {
+    Col2<COL_U8> c;
+    const uint32_t mis = (uint32_t)((uintptr_t)col & 3);
+    c.base = col - mis;
+    c.off_lo = 4 * lane;
+    c.off_hi = lane == 63 && mis == 0 ? 4 * lane : 4 * lane + 4;  // (nothing of the tile lies behind an aligned column's dword 63)
+    c.shift = 8 * mis;
+    c.pat = 0x01010101u * (pred.cls & 0xffu);
+    col2_lanes<COL_U8>(c, lane);
+    return c;
+}
+__device__ __forceinline__ Col2<COL_F64> col2_setup(const uint8_t *col, const DevPred &pred, int lane, IntC<COL_F64>) {
+    Col2<COL_F64> c;
+    c.base = col;
+    c.t0 = pred.wmin[0], c.t1 = pred.wmax[0];
+    col2_lanes<COL_F64>(c, lane);
+    return c;
+}
+__device__ __forceinline__ Col2<COL_NONE> col2_setup(const uint8_t *, const DevPred &, int, IntC<COL_NONE>) { return {}; }
+
+// A tile's second-column registers.
+template <int COL>
+struct Col2Regs {};
+template <>
+struct Col2Regs<COL_U8> {
+    int lo, hi;
+};
+template <>
+struct Col2Regs<COL_F64> {
+    v4i a, b;
+};
+__device__ __forceinline__ bool t_in(int lo, int hi, double t0, double t1) {
+    const double t = __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+    return (t >= t0) & (t < t1);  // Range<f64>::contains: NaN is no match
+}
+__device__ __forceinline__ uint32_t verdict_word(const Col2Regs<COL_U8> &r, const Col2<COL_U8> &c) {
+    return zero_bytes(__builtin_amdgcn_alignbit((uint32_t)r.hi, (uint32_t)r.lo, c.shift) ^ c.pat);
+}
+__device__ __forceinline__ uint32_t verdict_word(const Col2Regs<COL_F64> &r, const Col2<COL_F64> &c) {
+    return (uint32_t)t_in(r.a[0], r.a[1], c.t0, c.t1) | (uint32_t)t_in(r.a[2], r.a[3], c.t0, c.t1) << 1 |
+           (uint32_t)t_in(r.b[0], r.b[1], c.t0, c.t1) << 2 | (uint32_t)t_in(r.b[2], r.b[3], c.t0, c.t1) << 3;
+}
+// the verdict of the point held at (addr, bit), brought to this lane
+__device__ __forceinline__ bool verdict_at(uint32_t V, uint32_t addr, uint32_t bit) {
+    return (((uint32_t)__builtin_amdgcn_ds_bpermute((int)addr, (int)V) >> bit) & 1u) != 0;
+}
+
 struct LaneBox {
     int lo[3];        // lo[(lane%3 + t) % 3], t = 0..2
     uint32_t w[3];
@@ -65,8 +163,10 @@ __device__ __forceinline__ LaneBox rotate_box(const int32_t (&lo)[3], const uint
     return b;
 }
 
-// Count of matching points in one 768-dword wave tile, mask-algebra form (wave-uniform result).
-__device__ __forceinline__ uint32_t tile_count_regs(const v4i (&v)[3], const LaneBox &b) {
+// Count of matching points in one 768-dword wave tile, mask-algebra form (wave-uniform result).  COL: the points' verdicts
+// of the second column (verdict word V) are ANDed into the start bits.
+template <int COL = COL_NONE>
+__device__ __forceinline__ uint32_t tile_count_regs(const v4i (&v)[3], const LaneBox &b, const Col2<COL> &c2 = {}, uint32_t V = 0) {
     uint64_t m[3][4];
 #pragma unroll
     for (int k = 0; k < 3; k++)
@@ -92,7 +192,12 @@ __device__ __forceinline__ uint32_t tile_count_regs(const v4i (&v)[3], const Lan
         const uint64_t t2 = m2 & bb;     // j=2,3 and next lane's 0
         const uint64_t t3 = bb & n1;     // j=3 and next lane's 0,1
         const uint64_t s012 = (t0 & start_lanes(k)) | (t1 & start_lanes(k + 1)) | (t2 & start_lanes(k + 2));
-        cnt += (uint32_t)__popcll(s012) + (uint32_t)__popcll(t3 & start_lanes(k + 3));
+        if constexpr (COL == COL_NONE) {
+            cnt += (uint32_t)__popcll(s012) + (uint32_t)__popcll(t3 & start_lanes(k + 3));
+        } else {  // one start among j = 0..2 per lane, and a second one at j = 3 where j0 == 0
+            const uint64_t va = __ballot(verdict_at(V, c2.addr_a[k], c2.bit_a[k])), vb = __ballot(verdict_at(V, c2.addr_b[k], c2.bit_b[k]));
+            cnt += (uint32_t)__popcll(s012 & va) + (uint32_t)__popcll(t3 & start_lanes(k + 3) & vb);
+        }
     }
     return cnt;
 }
@@ -107,12 +212,52 @@ __device__ __forceinline__ uint32_t tile_count_masks(const v4i *tile, int lane, 
 
 // Software pipeline: asm volatile statements keep their order; the empty asm behind each s_waitcnt re-defines the
 // registers it guards, so no use can be hoisted above the wait.
-template <int TILES>
+template <int TILES, int COL = COL_NONE>
 struct PipeRegs {
     v4i r[TILES][3];
+    Col2Regs<COL> c[TILES];
 };
 template <int TILES>
-__device__ __forceinline__ void pipe_load(PipeRegs<TILES> &R, const v4i *base, uint64_t step, int lane) {
+struct PipeRegs<TILES, COL_NONE> {
+    v4i r[TILES][3];
+};
+constexpr int col2_loads(int col) { return col == COL_NONE ? 0 : 2; }  // per tile
+// the second column of tile `tile` (two loads per lane, issued behind the positions: the waits count them)
+__device__ __forceinline__ void col2_load(Col2Regs<COL_U8> &r, const Col2<COL_U8> &c, uint64_t tile) {
+    const uint8_t *tb = c.base + tile * 256;
+    asm volatile("global_load_dword %0, %2, %4 nt\n\tglobal_load_dword %1, %3, %4 nt"
+                 : "=&v"(r.lo), "=&v"(r.hi)
+                 : "v"(c.off_lo), "v"(c.off_hi), "s"(tb)
+                 : "memory");
+}
+__device__ __forceinline__ void col2_load(Col2Regs<COL_F64> &r, const Col2<COL_F64> &c, uint64_t tile) {
+    const uint8_t *tb = c.base + tile * 2048;
+    asm volatile("global_load_dwordx4 %0, %2, %3 nt\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024 nt"
+                 : "=&v"(r.a), "=&v"(r.b)
+                 : "v"(16u * (uint32_t)__lane_id()), "s"(tb)
+                 : "memory");
+}
+// the same with plain loads (the leftover tiles, outside the pipeline)
+__device__ __forceinline__ void col2_load_plain(Col2Regs<COL_U8> &r, const Col2<COL_U8> &c, uint64_t tile) {
+    r.lo = *reinterpret_cast<const int *>(c.base + tile * 256 + c.off_lo);
+    r.hi = *reinterpret_cast<const int *>(c.base + tile * 256 + c.off_hi);
+}
+__device__ __forceinline__ void col2_load_plain(Col2Regs<COL_F64> &r, const Col2<COL_F64> &c, uint64_t tile) {
+    const v4i *q = reinterpret_cast<const v4i *>(c.base + tile * 2048) + __lane_id();
+    r.a = q[0];
+    r.b = q[64];
+}
+__device__ __forceinline__ void col2_guard(Col2Regs<COL_U8> &r) { asm volatile("" : "+v"(r.lo), "+v"(r.hi)::"memory"); }
+__device__ __forceinline__ void col2_guard(Col2Regs<COL_F64> &r) { asm volatile("" : "+v"(r.a), "+v"(r.b)::"memory"); }
+// second column of point p (0-based in the body), one lane at a time: the tail behind the last whole tile
+__device__ __forceinline__ bool col2_point(const Col2<COL_U8> &c, uint64_t p) { return c.base[c.shift / 8 + p] == (c.pat & 0xffu); }
+__device__ __forceinline__ bool col2_point(const Col2<COL_F64> &c, uint64_t p) {
+    const double t = reinterpret_cast<const double *>(c.base)[p];
+    return (t >= c.t0) & (t < c.t1);
+}
+
+template <int TILES, int COL>
+__device__ __forceinline__ void pipe_load(PipeRegs<TILES, COL> &R, const v4i *base, uint64_t step, int lane, const Col2<COL> &c2) {
 #pragma unroll
     for (int t = 0; t < TILES; t++) {
         const v4i *q = base + (step * TILES + t) * 192 + lane;
@@ -122,50 +267,108 @@ __device__ __forceinline__ void pipe_load(PipeRegs<TILES> &R, const v4i *base, u
                      : "v"(q)
                      : "memory");
     }
+    if constexpr (COL != COL_NONE) {
+#pragma unroll
+        for (int t = 0; t < TILES; t++) col2_load(R.c[t], c2, step * TILES + t);
+    }
 }
-template <int TILES, int PENDING>
-__device__ __forceinline__ void pipe_wait(PipeRegs<TILES> &R) {
+template <int TILES>
+__device__ __forceinline__ void pipe_load(PipeRegs<TILES> &R, const v4i *base, uint64_t step, int lane) {
+    pipe_load<TILES, COL_NONE>(R, base, step, lane, Col2<COL_NONE>{});
+}
+// PENDING: the loads of the other register set, which stay in flight
+template <int TILES, int PENDING, int COL>
+__device__ __forceinline__ void pipe_wait(PipeRegs<TILES, COL> &R) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
 #pragma unroll
     for (int t = 0; t < TILES; t++) asm volatile("" : "+v"(R.r[t][0]), "+v"(R.r[t][1]), "+v"(R.r[t][2])::"memory");
+    if constexpr (COL != COL_NONE) {
+#pragma unroll
+        for (int t = 0; t < TILES; t++) col2_guard(R.c[t]);
+    }
+}
+template <int TILES, int COL>
+__device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES, COL> &R, const LaneBox &lb, const Col2<COL> &c2) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int t = 0; t < TILES; t++) {
+        if constexpr (COL == COL_NONE) c += tile_count_regs(R.r[t], lb);
+        else c += tile_count_regs<COL>(R.r[t], lb, c2, verdict_word(R.c[t], c2));
+    }
+    return c;
 }
 template <int TILES>
 __device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES> &R, const LaneBox &lb) {
-    uint64_t c = 0;
-#pragma unroll
-    for (int t = 0; t < TILES; t++) c += tile_count_regs(R.r[t], lb);
-    return c;
+    return pipe_eval<TILES, COL_NONE>(R, lb, Col2<COL_NONE>{});
 }
 
-template <int TILES>
+// The second column as K1's last argument: none (the plain K1, k_bounds_count_w1_pipe<2>), ClassBytes (PCQ_PRED_BOUNDS_CLASS)
+// or GpsTimes (PCQ_PRED_BOUNDS_TIME), at the body's first point (class bytes: any alignment; times: 8-byte aligned).
+struct ClassBytes {
+    const uint8_t *p;
+};
+struct GpsTimes {
+    const uint8_t *p;
+};
+template <typename... Col>
+struct ColOf {
+    static constexpr int value = COL_NONE;
+};
+template <>
+struct ColOf<ClassBytes> {
+    static constexpr int value = COL_U8;
+};
+template <>
+struct ColOf<GpsTimes> {
+    static constexpr int value = COL_F64;
+};
+__device__ __forceinline__ const uint8_t *col_ptr() { return nullptr; }
+template <typename C>
+__device__ __forceinline__ const uint8_t *col_ptr(C c) { return c.p; }
+
+template <int TILES, typename... Col>
 __global__ __launch_bounds__(64) void k_bounds_count_w1_pipe(const v4i *__restrict__ base, uint64_t n, DevPred pred,
-                                                             uint64_t *__restrict__ partials) {
+                                                             uint64_t *__restrict__ partials, Col... col) {
+    constexpr int COL = ColOf<Col...>::value;
+    static_assert(sizeof...(Col) <= 1, "one second column at most");
     const int lane = threadIdx.x;
     const uint64_t tiles = n / TILE_POINTS, steps = tiles / TILES, stride = gridDim.x;
     const LaneBox lb = rotate_box(pred.lo, pred.width, lane);
+    const Col2<COL> c2 = col2_setup(col_ptr(col...), pred, lane, IntC<COL>{});
+    constexpr int LOADS = TILES * (3 + col2_loads(COL));  // per register set
     uint64_t total = 0;
     if (blockIdx.x < steps) {
-        PipeRegs<TILES> A, B;
+        PipeRegs<TILES, COL> A, B;
         uint64_t g = blockIdx.x;
-        pipe_load<TILES>(A, base, g, lane);
+        pipe_load<TILES, COL>(A, base, g, lane, c2);
         for (;;) {
             const uint64_t g1 = g + stride;
-            pipe_load<TILES>(B, base, g1 < steps ? g1 : g, lane);  // clamped at the tail: a re-read that hits L2
-            pipe_wait<TILES, 3 * TILES>(A);                       // A has landed, B's loads stay in flight
-            total += pipe_eval<TILES>(A, lb);
+            pipe_load<TILES, COL>(B, base, g1 < steps ? g1 : g, lane, c2);  // clamped at the tail: a re-read that hits L2
+            pipe_wait<TILES, LOADS, COL>(A);                                 // A has landed, B's loads stay in flight
+            total += pipe_eval<TILES, COL>(A, lb, c2);
             if (g1 >= steps) break;
             const uint64_t g2 = g1 + stride;
-            pipe_load<TILES>(A, base, g2 < steps ? g2 : g1, lane);
-            pipe_wait<TILES, 3 * TILES>(B);
-            total += pipe_eval<TILES>(B, lb);
+            pipe_load<TILES, COL>(A, base, g2 < steps ? g2 : g1, lane, c2);
+            pipe_wait<TILES, LOADS, COL>(B);
+            total += pipe_eval<TILES, COL>(B, lb, c2);
             if (g2 >= steps) break;
             g = g2;
         }
-        pipe_wait<TILES, 0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<TILES, 0>(B);
+        pipe_wait<TILES, 0, COL>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<TILES, 0, COL>(B);
     }
     if (blockIdx.x == 0) {
-        for (uint64_t t = steps * TILES; t < tiles; t++) total += tile_count_masks(base + t * 192, lane, lb);
+        for (uint64_t t = steps * TILES; t < tiles; t++) {
+            if constexpr (COL == COL_NONE) {
+                total += tile_count_masks(base + t * 192, lane, lb);
+            } else {
+                const v4i *tile = base + t * 192;
+                const v4i v[3] = {tile[lane], tile[64 + lane], tile[128 + lane]};
+                Col2Regs<COL> r;
+                col2_load_plain(r, c2, t);
+                total += tile_count_regs<COL>(v, lb, c2, verdict_word(r, c2));
+            }
+        }
         for (int k = 0; k < 4; k++) {
             const uint64_t p = tiles * TILE_POINTS + (uint64_t)(64 * k + lane);
             bool pass = false;
@@ -173,6 +376,7 @@ __global__ __launch_bounds__(64) void k_bounds_count_w1_pipe(const v4i *__restri
                 const int *q = reinterpret_cast<const int *>(base) + 3 * p;
                 pass = ((uint32_t)(q[0] - pred.lo[0]) <= pred.width[0]) & ((uint32_t)(q[1] - pred.lo[1]) <= pred.width[1]) &
                        ((uint32_t)(q[2] - pred.lo[2]) <= pred.width[2]);
+                if constexpr (COL != COL_NONE) pass = pass && col2_point(c2, p);
             }
             total += (uint64_t)__popcll(__ballot(pass));
         }
@@ -260,12 +464,6 @@ __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment
         }
     }
     if (lane == 0) partials[blockIdx.x] = total;
-}
-
-// Bytes of a dword equal to zero -> 0x80 in that byte (exact, no borrow artefacts).
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {
-    const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | x | 0x7f7f7f7fu);
 }
 
 // The class segments live in the same device table as the bounds segments, at DevSegment pitch.
@@ -439,8 +637,8 @@ __global__ __launch_bounds__(BLOCK) void k_finish_count(const uint64_t *__restri
 
 }  // namespace
 
-int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,
-                                  uint64_t *d_count, hipStream_t s) {
+template <typename... Col>
+static int launch_k1(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s, Col... col) {
     if (n == 0 || pred.empty) return PCQ_OK;
     if (((uintptr_t)d_xyz & 15) != 0) return pcq_fail(PCQ_ERR_ARG, "bounds_count_xyz12: positions block must be 16-byte aligned");
     const uint64_t units = n / ((uint64_t)K1_TILES * TILE_POINTS) + 1;
@@ -448,10 +646,24 @@ int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, c
     if (g > units) g = units;
     int rc = pcq_ensure_partials(ctx, (size_t)g);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_bounds_count_w1_pipe<K1_TILES>, dim3((unsigned)g), dim3(64), 0, s, reinterpret_cast<const v4i *>(d_xyz), n, pred, ctx->d_partials);
+    hipLaunchKernelGGL((k_bounds_count_w1_pipe<K1_TILES, Col...>), dim3((unsigned)g), dim3(64), 0, s, reinterpret_cast<const v4i *>(d_xyz), n, pred,
+                       ctx->d_partials, col...);
     hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, d_count);
     PCQ_HIP(hipGetLastError());
     return PCQ_OK;
+}
+
+int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,
+                                  uint64_t *d_count, hipStream_t s) {
+    return launch_k1(ctx, d_xyz, n, pred, d_count, s);
+}
+
+int pcq_launch_bounds_count_xyz12_col(pcq_ctx *ctx, const void *d_xyz, const void *d_col, uint64_t n, const DevPred &pred, uint64_t *d_count,
+                                      hipStream_t s) {
+    if (pred.kind == PCQ_PRED_BOUNDS_CLASS) return launch_k1(ctx, d_xyz, n, pred, d_count, s, ClassBytes{(const uint8_t *)d_col});
+    if (pred.kind != PCQ_PRED_BOUNDS_TIME) return pcq_fail(PCQ_ERR_ARG, "bounds_count_xyz12_col: predicate kind %d", pred.kind);
+    if (((uintptr_t)d_col & 7) != 0) return pcq_fail(PCQ_ERR_ARG, "bounds_count_xyz12_col: time block must be 8-byte aligned");
+    return launch_k1(ctx, d_xyz, n, pred, d_count, s, GpsTimes{(const uint8_t *)d_col});
 }
 
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls, uint64_t *d_count,

@@ -1,6 +1,7 @@
 // scan_generic.hip — layout-generic scan kernels (any column strides: LAST column blocks or LAS
 // AoS records), used where the count-only fast paths of scan_count.hip do not apply:
-//   * strided count            — LAS bounds/class/time count (las.rs:101-119, :221-231, :328-338), unaligned LAST
+//   * strided count            — LAS bounds/class/time count (las.rs:101-119, :221-231, :328-338), unaligned LAST,
+//                                the combined kinds (bounds AND class / time) wherever K1's column form does not apply
 //                                (one record per lane: 4.1-5.9 TB/s of record bytes; an LDS-tiled variant
 //                                with 16-byte coalesced loads was measured and was NOT faster,
 //                                profiles/r01_las_aos_count_rate.log)
@@ -98,7 +99,7 @@ __device__ __forceinline__ void or_point31(uint32_t *image, uint32_t byte_offset
 template <int KIND, bool ATTRS>
 struct TileIn {
     RawPoint rps[EMIT_ITEMS];
-    double t[EMIT_ITEMS];  // PCQ_PRED_TIME: the GPS times (the predicate's column, in c.cls)
+    double t[EMIT_ITEMS];  // PCQ_PRED_TIME / _BOUNDS_TIME: the GPS times (the predicate's column, in c.cls)
     bool passes[EMIT_ITEMS];
     uint32_t attr_cls[EMIT_ITEMS], attr_rg[EMIT_ITEMS], attr_b[EMIT_ITEMS];
 };
@@ -111,8 +112,9 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
     // No branch around a load: with `c.cls ? c.cls[i] : 0` in the unrolled loop every load sat in its own block and was
     // waited for at the block's end (eight serial round trips per tile).  A missing column is read from a valid address
     // with stride 0 and masked instead.
-    // (TIME: c.cls is the time column, and a time record's class is 0 — las.rs:345-355 `..Default::default()`)
-    const bool has_cls = (ATTRS || KIND == PCQ_PRED_CLASS) && c.cls && KIND != PCQ_PRED_TIME, has_rgb = ATTRS && RGB && c.rgb;
+    // (TIME, BOUNDS_TIME: c.cls is the time column, and a time record's class is 0 — las.rs:345-355 `..Default::default()`)
+    const bool has_cls = (ATTRS || KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_BOUNDS_CLASS) && c.cls && !pred_tests_time(KIND),
+               has_rgb = ATTRS && RGB && c.rgb;
     const uint8_t *fallback = c.xyz ? c.xyz : c.cls;  // (one of the two exists: the predicate reads it)
     const uint8_t *clsp = has_cls ? c.cls : fallback, *rgbp = has_rgb ? c.rgb : fallback;
     const uint64_t cls_stride = has_cls ? c.cls_stride : 0, rgb_stride = has_rgb ? c.rgb_stride : 0;
@@ -128,8 +130,8 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
             raw_rg[j] = (uint32_t)ld_u16(q) | ((uint32_t)ld_u16(q + 2) << 16);
             raw_b[j] = ld_u16(q + 4);
         }
-        if (KIND == PCQ_PRED_TIME) T.t[j] = ld_f64(c.cls + i * c.cls_stride);  // las.rs:334
-        else if (KIND != PCQ_PRED_CLASS) T.rps[j] = ld_xyz_stream(c, i);
+        if (pred_tests_time(KIND)) T.t[j] = ld_f64(c.cls + i * c.cls_stride);  // las.rs:334
+        if (KIND != PCQ_PRED_CLASS && KIND != PCQ_PRED_TIME) T.rps[j] = ld_xyz_stream(c, i);
     }
 #pragma unroll
     for (int j = 0; j < EMIT_ITEMS; j++) T.attr_cls[j] = raw_cls[j] & cls_mask, T.attr_rg[j] = raw_rg[j] & rg_mask, T.attr_b[j] = raw_b[j] & b_mask;
@@ -139,6 +141,8 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
         bool pass;
         if (KIND == PCQ_PRED_CLASS) pass = T.attr_cls[j] == pr.cls;
         else if (KIND == PCQ_PRED_TIME) pass = time_in(T.t[j], pr);
+        else if (KIND == PCQ_PRED_BOUNDS_CLASS) pass = (int)box_in(T.rps[j], pr) & (int)(T.attr_cls[j] == pr.cls);
+        else if (KIND == PCQ_PRED_BOUNDS_TIME) pass = (int)box_in(T.rps[j], pr) & (int)time_in(T.t[j], pr);
         else if (KIND == PCQ_PRED_BOUNDS)
             pass = (pr.empty == 0) & ((uint32_t)(T.rps[j].x - pr.lo[0]) <= pr.width[0]) & ((uint32_t)(T.rps[j].y - pr.lo[1]) <= pr.width[1]) &
                    ((uint32_t)(T.rps[j].z - pr.lo[2]) <= pr.width[2]);
@@ -213,7 +217,8 @@ __global__ __launch_bounds__(BLOCK) void k_tile_counts(DevCols c, DevPred pr, ui
 #pragma unroll
     for (int w = 0; w < WAVES; w++) total += s_w[w];
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
-    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME || !park || total == 0 || total > park_max) return;  // (the same for the whole workgroup)
+    if (KIND == PCQ_PRED_CLASS || KIND == PCQ_PRED_TIME || pred_is_combined(KIND) || !park || total == 0 || total > park_max)
+        return;  // (the same for the whole workgroup)
     uint32_t cls[EMIT_ITEMS], rg[EMIT_ITEMS], bl[EMIT_ITEMS];
     {
         const uint8_t *clsp = c.cls ? c.cls : c.xyz;
@@ -510,7 +515,7 @@ __global__ __launch_bounds__(BLOCK) void k_emit_sparse(DevCols c, const uint64_t
 int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint64_t *d_count,
                              hipStream_t s) {
     if (cols.n == 0) return PCQ_OK;
-    if (pred.kind == PCQ_PRED_BOUNDS && pred.empty) return PCQ_OK;
+    if (pred_has_box(pred.kind) && pred.empty) return PCQ_OK;
     uint64_t want = (cols.n + BLOCK * 4 - 1) / (BLOCK * 4);
     const uint64_t cap = (uint64_t)ctx->num_cus * (uint64_t)ctx->grid_blocks_per_cu;
     const int grid = (int)(want < cap ? want : cap);
@@ -519,6 +524,8 @@ int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &p
     if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_CLASS>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     else if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_TIME>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
+    else if (pred.kind == PCQ_PRED_BOUNDS_CLASS) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS_CLASS>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
+    else if (pred.kind == PCQ_PRED_BOUNDS_TIME) hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS_TIME>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     else hipLaunchKernelGGL(k_generic_count<PCQ_PRED_BOUNDS_F64>, dim3(grid), dim3(BLOCK), 0, s, cols, pred, ctx->d_partials);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, d_count);
     PCQ_HIP(hipGetLastError());
@@ -535,7 +542,9 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     const uint64_t npieces = (ntiles + SCAN_PIECE - 1) / SCAN_PIECE;
     if (npieces > 1024) return pcq_fail(PCQ_ERR_ARG, "scan chunk too large (%llu points)", (unsigned long long)cols.n);
     // thin tiles park their matches (k_tile_counts): positions predicate; 16 (with a colour block: 32) bytes x park_max per tile, a sixth of the input
-    uint32_t park_max = pred.kind != PCQ_PRED_CLASS && pred.kind != PCQ_PRED_TIME && cols.xyz && ctx->emit_park_max > 0 ? (uint32_t)ctx->emit_park_max : 0u;
+    uint32_t park_max = pred.kind != PCQ_PRED_CLASS && pred.kind != PCQ_PRED_TIME && !pred_is_combined(pred.kind) && cols.xyz && ctx->emit_park_max > 0
+                            ? (uint32_t)ctx->emit_park_max
+                            : 0u;
     const size_t base_words = (size_t)(2 * ntiles + npieces + 2 + ntiles * (EMIT_ITEMS * WAVES));  // counts | offsets (+ total) | piece sums | match bits
     int rc = pcq_ensure_partials(ctx, base_words + 2 + (size_t)ntiles * park_max * (cols.rgb ? 4 : 2));  // | parked matches (16-byte aligned)
     if (rc && park_max) {  // no room for the parked matches (a sixth of the input): the thin tiles are read a second time instead
@@ -557,6 +566,8 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false, INDEX_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_TIME, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (pred.kind == PCQ_PRED_BOUNDS_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
+    else if (pred.kind == PCQ_PRED_BOUNDS_TIME) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_TIME, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_BOUNDS && park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_BOUNDS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (park_rgb) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_F64, true>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
@@ -573,6 +584,8 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     if (pred.kind == PCQ_PRED_BOUNDS) PCQ_EMIT(PCQ_PRED_BOUNDS);
     else if (pred.kind == PCQ_PRED_CLASS) PCQ_EMIT(PCQ_PRED_CLASS);
     else if (pred.kind == PCQ_PRED_TIME) PCQ_EMIT(PCQ_PRED_TIME);
+    else if (pred.kind == PCQ_PRED_BOUNDS_CLASS) PCQ_EMIT(PCQ_PRED_BOUNDS_CLASS);
+    else if (pred.kind == PCQ_PRED_BOUNDS_TIME) PCQ_EMIT(PCQ_PRED_BOUNDS_TIME);
     else PCQ_EMIT(PCQ_PRED_BOUNDS_F64);
 #undef PCQ_EMIT
     if (park_max) {  // tiles with 1 .. park_max matches: from the 16-byte words the count pass left
@@ -581,7 +594,7 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
     }
     if (sparse_max > park_max) {  // tiles with 1 .. sparse_max matches: a wave each, from the match bits (same stream: behind the scan of the offsets)
         const dim3 gs((unsigned)((ntiles + WAVES - 1) / WAVES));
-        if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL((k_emit_sparse<false, false>), gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
+        if (pred_tests_time(pred.kind)) hipLaunchKernelGGL((k_emit_sparse<false, false>), gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
         else if (cols.rgb) hipLaunchKernelGGL(k_emit_sparse<true>, gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
         else hipLaunchKernelGGL(k_emit_sparse<false>, gs, b, 0, s, cols, offsets, bits, d_npoints_in, d_out31, (uint32_t)ntiles, park_max, sparse_max);
     }

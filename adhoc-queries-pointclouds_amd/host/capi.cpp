@@ -148,6 +148,40 @@ extern "C" int pcq_query_search_file_time(const char *path, double start, double
     return done(TimeSearcher(start, end).search_file(path, optimized ? SearchImplementation::Optimized : SearchImplementation::Regular, *c->c));
 }
 
+extern "C" int pcq_query_search_file_bounds_class(const char *path, const double bmin[3], const double bmax[3], uint8_t cls, int optimized,
+                                                  pcq_host_collector *c) {
+    if (!path || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    const Status st = AABB::from_min_max(bmin, bmax, &b);
+    if (!st.ok()) return done(st);
+    return done(BoundsClassSearcher(b, cls).search_file(path, optimized ? SearchImplementation::Optimized : SearchImplementation::Regular, *c->c));
+}
+
+extern "C" int pcq_query_search_file_bounds_time(const char *path, const double bmin[3], const double bmax[3], double start, double end, int optimized,
+                                                 pcq_host_collector *c) {
+    if (!path || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    const Status st = AABB::from_min_max(bmin, bmax, &b);
+    if (!st.ok()) return done(st);
+    return done(BoundsTimeSearcher(b, start, end).search_file(path, optimized ? SearchImplementation::Optimized : SearchImplementation::Regular, *c->c));
+}
+
+// cls 0..255: the plan of BOUNDS AND CLASS; cls < 0: that of BOUNDS AND TIME over [start, end)
+extern "C" int pcq_query_test_plan_combined(const char *path, const double bmin[3], const double bmax[3], int cls, double start, double end,
+                                            pcq_columns *cols, pcq_predicate *pred, int *needs_gpu) {
+    if (!path || !bmin || !bmax || !cols || !pred || !needs_gpu) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    const Status st = AABB::from_min_max(bmin, bmax, &b);
+    if (!st.ok()) return done(st);
+    std::optional<FilePlan> plan = cls >= 0 ? BoundsClassSearcher(b, (uint8_t)cls).plan_file(path, SearchImplementation::Optimized)
+                                            : BoundsTimeSearcher(b, start, end).plan_file(path, SearchImplementation::Optimized);
+    if (!plan) return done(Status::Err(PCQ_ERR_ARG, "no host plan for this file"));
+    *needs_gpu = plan->needs_gpu ? 1 : 0;
+    *cols = plan->cols;
+    *pred = plan->pred;
+    return done(plan->status);
+}
+
 extern "C" int pcq_query_test_plan_time(const char *path, double start, double end, pcq_columns *cols, pcq_predicate *pred, int *needs_gpu) {
     if (!path || !cols || !pred || !needs_gpu) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     std::optional<FilePlan> plan = TimeSearcher(start, end).plan_file(path, SearchImplementation::Optimized);

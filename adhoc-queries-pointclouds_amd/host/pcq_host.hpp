@@ -174,19 +174,26 @@ struct FilePlan {
     pcq_predicate pred{};
 };
 FilePlan plan_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds);
-FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls);
+// (header: when not NULL, the parsed header — valid when the plan's status is OK; the combined plans read its bounds)
+FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header = nullptr);
 FilePlan plan_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds);
-FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls);
+FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header = nullptr);
 Status execute_plan(FilePlan &plan, ResultCollector &rc);  // the per-point loop: pcq_scan_fd into the collector
 Status search_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc);
 Status search_last_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
 Status search_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc, SearchLog *log);
 Status search_las_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
 // GPS time in [start, end) (Range<f64>::contains): las.rs:297-358; the LAST form reads the transposed time block
-FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end);
-FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end);
+FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header = nullptr);
+FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header = nullptr);
 Status search_las_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
 Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
+// The box AND a class byte / a GPS time range (--combine; not in the reference): the attribute search's plan
+// and records, then the bounds search's header early-out and box
+FilePlan plan_las_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls);
+FilePlan plan_last_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls);
+FilePlan plan_las_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end);
+FilePlan plan_last_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end);
 // search/lazer.rs:34-116 over readers/src/lazer_reader.rs (one implementation for both --optimized settings)
 Status search_lazer_file_by_bounds(const std::string &path, const AABB &bounds, ResultCollector &rc);
 Status search_lazer_file_by_classification(const std::string &path, uint8_t cls, ResultCollector &rc);
@@ -232,6 +239,29 @@ public:
     std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
 
 private:
+    double start_, end_;
+};
+// --combine: a point matches when both single searches would match it (PCQ_PRED_BOUNDS_CLASS / PCQ_PRED_BOUNDS_TIME)
+class BoundsClassSearcher : public Searcher {
+public:
+    BoundsClassSearcher(const AABB &bounds, uint8_t cls) : bounds_(bounds), class_(cls) {}
+    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
+                       SearchLog *log = nullptr) const override;
+    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
+
+private:
+    AABB bounds_;
+    uint8_t class_;
+};
+class BoundsTimeSearcher : public Searcher {
+public:
+    BoundsTimeSearcher(const AABB &bounds, double start, double end) : bounds_(bounds), start_(start), end_(end) {}
+    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
+                       SearchLog *log = nullptr) const override;
+    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
+
+private:
+    AABB bounds_;
     double start_, end_;
 };
 

@@ -414,7 +414,11 @@ Status run_search_parallel(const std::vector<std::string> &files, const Searcher
         const char *policy = getenv("PCQ_MERGE");
         double planned_bytes = 0;
         for (size_t w : work)
-            if (plans[w]) planned_bytes += (double)plans[w]->cols.n * (plans[w]->pred.kind == PCQ_PRED_CLASS ? 1.0 : plans[w]->pred.kind == PCQ_PRED_TIME ? 8.0 : 12.0);
+            if (plans[w]) {
+                const int k = plans[w]->pred.kind;
+                const double bpp = k == PCQ_PRED_CLASS ? 1.0 : k == PCQ_PRED_TIME ? 8.0 : k == PCQ_PRED_BOUNDS_CLASS ? 13.0 : k == PCQ_PRED_BOUNDS_TIME ? 20.0 : 12.0;
+                planned_bytes += (double)plans[w]->cols.n * bpp;
+            }
         const double scan_seconds = planned_bytes / (40e9 * (double)devices.size());
         merge_rccl = opt.test_allreduce_fail != 0 || (policy && !strcmp(policy, "rccl"));
         // RCCL's NCCL_DEBUG output belongs on stderr (collective.hip); the environment is written HERE, before any other thread
@@ -569,7 +573,7 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
     const auto t_start = std::chrono::steady_clock::now();  // :192
     std::optional<std::string> input, bounds_s, class_s, time_s, output, density_s, stats_json;
     std::vector<FileStat> file_stats;
-    bool parallel = false, optimized = false;
+    bool parallel = false, optimized = false, combine = false;
     RunOptions opt;
     opt.devices = {0};
     opt.collectors_yield_points = true;
@@ -586,11 +590,13 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
         else if (a == "--density") dst = &density_s;
         else if (a == "--parallel") { parallel = true; continue; }
         else if (a == "--optimized") { optimized = true; continue; }
+        else if (a == "--combine") { combine = true; continue; }  // not in the reference: BOUNDS AND (CLASS or TIME), DESIGN.md §8
         else if (a == "--stats-json") dst = &stats_json;  // extra flag: machine-readable timing sidecar
         else if (a == "--gpus" || a == "--device" || a == "--threads-per-gpu") dst = &ext_val;  // extra flags (not in the reference)
         else if (a == "-h" || a == "--help") {
             out("I/O experiments 0.1\nLAS I/O experiments (MI355X-native predicate path)\n\nUSAGE:\n    query [FLAGS] [OPTIONS] --input <FILE>\n\n"
-                "FLAGS:\n        --optimized    Run search with optimized implementation\n        --parallel     Run search in parallel\n\n"
+                "FLAGS:\n        --optimized    Run search with optimized implementation\n        --parallel     Run search in parallel\n"
+                "        --combine            with --bounds, also require --class or --time (a point must match both)\n\n"
                 "OPTIONS:\n        --bounds <BOUNDS>    \"minX;minY;minZ;maxX;maxY;maxZ\"\n        --class <CLASS>      object class (u8)\n"
                 "        --time <TIME>        \"start;end\": GPS time range, start <= t < end\n"
                 "        --density <DENSITY>  maximum density (grid cell size)\n    -i, --input <FILE>       file or directory\n"
@@ -696,13 +702,20 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
         }
         maybe_density = d;
     }
-    if (maybe_bounds && maybe_class) {  // :238-240
-        err("Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify either BOUNDS or CLASS argument!");
-        return 1;
-    }
-    if (maybe_time && (maybe_bounds || maybe_class)) {
-        err("Error: Specifying TIME together with BOUNDS or CLASS is invalid! Specify exactly one of BOUNDS, CLASS or TIME!");
-        return 1;
+    if (combine) {  // BOUNDS may join CLASS or TIME; CLASS and TIME share the one attribute column of a scan
+        if (maybe_class && maybe_time) {
+            err("Error: --combine joins BOUNDS with CLASS or with TIME; CLASS and TIME cannot be combined!");
+            return 1;
+        }
+    } else {
+        if (maybe_bounds && maybe_class) {  // :238-240
+            err("Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify either BOUNDS or CLASS argument!");
+            return 1;
+        }
+        if (maybe_time && (maybe_bounds || maybe_class)) {
+            err("Error: Specifying TIME together with BOUNDS or CLASS is invalid! Specify exactly one of BOUNDS, CLASS or TIME!");
+            return 1;
+        }
     }
     if (!maybe_bounds && !maybe_class && !maybe_time) {  // :242-244
         err("Error: Found neither BOUNDS nor CLASS argument but exactly one of these arguments is required!");
@@ -710,7 +723,9 @@ int query_main(int argc, const char *const *argv, const PrintFn &out, const Prin
     }
 
     std::unique_ptr<Searcher> searcher;  // :246-251
-    if (maybe_bounds) searcher = std::make_unique<BoundsSearcher>(*maybe_bounds);
+    if (maybe_bounds && maybe_class) searcher = std::make_unique<BoundsClassSearcher>(*maybe_bounds, *maybe_class);  // (--combine)
+    else if (maybe_bounds && maybe_time) searcher = std::make_unique<BoundsTimeSearcher>(*maybe_bounds, maybe_time->first, maybe_time->second);
+    else if (maybe_bounds) searcher = std::make_unique<BoundsSearcher>(*maybe_bounds);
     else if (maybe_class) searcher = std::make_unique<ClassSearcher>(*maybe_class);
     else searcher = std::make_unique<TimeSearcher>(maybe_time->first, maybe_time->second);
 

@@ -208,7 +208,7 @@ Status search_last_file_by_bounds_optimized(const std::string &path, const AABB 
 }
 
 // ---- last.rs:213-293 -------------------------------------------------------------------------------------
-FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls) {
+FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header) {
     auto holder = std::make_unique<MappedFile>();
     MappedFile &file = *holder;
     Status st = file.open(path);  // :218
@@ -216,6 +216,7 @@ FilePlan plan_last_file_by_classification_optimized(const std::string &path, uin
     LasHeader h;
     st = parse_las_header(file.data(), file.size(), /*mask_format=*/true, &h);  // :220-223
     if (!st.ok()) return done(st);
+    if (header) *header = h;
     const uint8_t fmt = h.point_data_record_format;  // :225
     uint64_t cls_in_point;
     if (fmt <= 5) cls_in_point = 15;  // :226-236
@@ -294,7 +295,7 @@ Status search_las_file_by_bounds_optimized(const std::string &path, const AABB &
 }
 
 // ---- las.rs:192-261 --------------------------------------------------------------------------------------
-FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls) {
+FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header) {
     auto holder = std::make_unique<MappedFile>();
     MappedFile &file = *holder;
     Status st = file.open(path);  // :197
@@ -302,6 +303,7 @@ FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint
     LasHeader h;
     st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, &h);  // :199-200
     if (!st.ok()) return done(st);
+    if (header) *header = h;
     const uint8_t fmt = h.point_data_record_format;  // raw, unmasked (:202)
     uint64_t cls_in_point;
     if (fmt <= 5) cls_in_point = 15;
@@ -354,7 +356,7 @@ pcq_predicate time_predicate(double start, double end) {
 }
 }  // namespace
 
-FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end) {
+FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header) {
     auto holder = std::make_unique<MappedFile>();
     MappedFile &file = *holder;
     Status st = file.open(path);  // :302
@@ -363,6 +365,7 @@ FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double s
     uint64_t t_in_point = 0;
     st = time_prologue(file, path, &h, &t_in_point);
     if (!st.ok()) return done(st);
+    if (header) *header = h;
     const uint64_t n = h.number_of_points, rl = h.point_data_record_length, otp = h.offset_to_point_data;
     if (n == 0) return done();  // (no file-level early-out: the header has no time bounds, :332)
     if (!block_ok(file, otp, (n - 1) * rl + t_in_point + 8)) return done(eof());
@@ -381,7 +384,7 @@ Status search_las_file_by_time_range_optimized(const std::string &path, double s
 
 // LAST: the record transposed by attribute (last_reader.rs:83-144) — the times are one block of n f64 at
 // offset_to_point_data + n * 20 (formats 1, 3-5) or + n * 22 (6-10); records as in las.rs:345-355.
-FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end) {
+FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header) {
     auto holder = std::make_unique<MappedFile>();
     MappedFile &file = *holder;
     Status st = file.open(path);
@@ -390,6 +393,7 @@ FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double 
     uint64_t t_in_point = 0;
     st = time_prologue(file, path, &h, &t_in_point);
     if (!st.ok()) return done(st);
+    if (header) *header = h;
     const uint64_t n = h.number_of_points, otp = h.offset_to_point_data;
     const uint64_t time_block = otp + n * t_in_point;
     if (n == 0) return done();
@@ -406,6 +410,44 @@ FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double 
 Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc) {
     FilePlan plan = plan_last_file_by_time_range_optimized(path, start, end);
     return execute_plan(plan, rc);
+}
+
+// ---- combined searches: the box AND a class byte or a GPS time range (not in the reference) -----------
+namespace {
+// The plan of a combined search, in this order: the attribute search's prologue as it stands (header, format, GPS and EOF
+// errors; its columns, predicate and records), then the bounds search's header early-out (last.rs:92-94: a disjoint file is
+// resolved on the host, 0 matches), then its box (last.rs:98-109).  The bounds search's own format check is not repeated and
+// no record size is printed.
+FilePlan with_box(FilePlan plan, const LasHeader &h, const AABB &bounds, int kind) {
+    if (!plan.status.ok()) return plan;
+    if (!h.bounds.intersects(bounds)) return done();
+    const int brc = pcq_box_to_local(bounds.min, bounds.max, h.scale, h.offset, plan.pred.lmin, plan.pred.lmax);
+    if (brc) return done(Status::FromLib(brc));
+    if (!plan.needs_gpu) return plan;  // (no points)
+    plan.pred.kind = kind;
+    return plan;
+}
+}  // namespace
+
+FilePlan plan_las_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls) {
+    LasHeader h;
+    FilePlan plan = plan_las_file_by_classification_optimized(path, cls, &h);
+    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_CLASS);
+}
+FilePlan plan_last_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls) {
+    LasHeader h;
+    FilePlan plan = plan_last_file_by_classification_optimized(path, cls, &h);
+    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_CLASS);
+}
+FilePlan plan_las_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end) {
+    LasHeader h;
+    FilePlan plan = plan_las_file_by_time_range_optimized(path, start, end, &h);
+    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_TIME);
+}
+FilePlan plan_last_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end) {
+    LasHeader h;
+    FilePlan plan = plan_last_file_by_time_range_optimized(path, start, end, &h);
+    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_TIME);
 }
 
 // ---- searcher.rs ---------------------------------------------------------------------------------------------
@@ -444,6 +486,21 @@ std::optional<FilePlan> TimeSearcher::plan_file(const std::string &path, SearchI
     if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
     if (*ext == "las") return plan_las_file_by_time_range_optimized(path, start_, end_);
     if (*ext == "last") return plan_last_file_by_time_range_optimized(path, start_, end_);
+    return std::nullopt;
+}
+
+std::optional<FilePlan> BoundsClassSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
+    const auto ext = extension_of(path);
+    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
+    if (*ext == "las") return plan_las_file_by_bounds_and_class_optimized(path, bounds_, class_);
+    if (*ext == "last") return plan_last_file_by_bounds_and_class_optimized(path, bounds_, class_);
+    return std::nullopt;
+}
+std::optional<FilePlan> BoundsTimeSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
+    const auto ext = extension_of(path);
+    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
+    if (*ext == "las") return plan_las_file_by_bounds_and_time_optimized(path, bounds_, start_, end_);
+    if (*ext == "last") return plan_last_file_by_bounds_and_time_optimized(path, bounds_, start_, end_);
     return std::nullopt;
 }
 
@@ -487,6 +544,32 @@ Status TimeSearcher::search_file(const std::string &path, SearchImplementation i
     if (*ext == "lazer") return out_of_scope("time search in .lazer files", path);
     if (*ext == "laz") return out_of_scope("compressed format .laz", path);
     return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
+}
+
+}  // namespace pcq
+
+namespace pcq {
+namespace {
+// search_file of the combined searchers: the LAS / LAST plan (optimized only), as the other searchers dispatch
+Status combined_search_file(const Searcher &searcher, const std::string &path, SearchImplementation impl, ResultCollector &collector) {
+    const auto ext = extension_of(path);
+    if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
+    if (*ext == "las" || *ext == "last") {
+        if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
+        FilePlan plan = *searcher.plan_file(path, impl);
+        return execute_plan(plan, collector);
+    }
+    if (*ext == "lazer") return out_of_scope("combined search in .lazer files", path);
+    if (*ext == "laz") return out_of_scope("compressed format .laz", path);
+    return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
+}
+}  // namespace
+
+Status BoundsClassSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
+    return combined_search_file(*this, path, impl, collector);
+}
+Status BoundsTimeSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
+    return combined_search_file(*this, path, impl, collector);
 }
 
 }  // namespace pcq

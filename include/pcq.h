@@ -96,7 +96,8 @@ int pcq_ctx_synchronize(pcq_ctx *ctx);
  * For PCQ_PRED_TIME, `cls` / `cls_stride` name the PREDICATE'S column instead: n little-endian f64 GPS times at any
  * byte alignment, stride >= 8 — LAST: the time block at offset_to_point_data + n*20 (formats 1, 3-5) or + n*22
  * (6-10), stride 8; LAS: the record + 20 / + 22, stride = record length.  A time record carries no class byte.  The time
- * column is always required; the positions only for buffer and grid collectors.
+ * column is always required; the positions only for buffer and grid collectors.  PCQ_PRED_BOUNDS_TIME passes the time
+ * column the same way, next to the positions; PCQ_PRED_BOUNDS_CLASS passes class bytes as PCQ_PRED_CLASS does.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pcq_columns {
     const void *xyz;            /* n records of {i32 x, i32 y, i32 z}, little endian            */
@@ -112,7 +113,14 @@ typedef struct pcq_columns {
     double offset[3];
 } pcq_columns;
 
-typedef enum pcq_predicate_kind { PCQ_PRED_BOUNDS = 0, PCQ_PRED_CLASS = 1, PCQ_PRED_BOUNDS_F64 = 2, PCQ_PRED_TIME = 3 } pcq_predicate_kind;
+typedef enum pcq_predicate_kind {
+    PCQ_PRED_BOUNDS = 0,
+    PCQ_PRED_CLASS = 1,
+    PCQ_PRED_BOUNDS_F64 = 2,
+    PCQ_PRED_TIME = 3,
+    PCQ_PRED_BOUNDS_CLASS = 4,
+    PCQ_PRED_BOUNDS_TIME = 5
+} pcq_predicate_kind;
 
 /* The predicate.
  * BOUNDS:     in the file's local integer space: lmin <= (x,y,z) <= lmax, inclusive, compared as i64
@@ -127,7 +135,15 @@ typedef enum pcq_predicate_kind { PCQ_PRED_BOUNDS = 0, PCQ_PRED_CLASS = 1, PCQ_P
  *             query/src/search/las.rs:297-358): a NaN time or bound matches nothing, wmin[0] >= wmax[0] is an empty
  *             range (no error), -0.0 == 0.0.  The other fields are ignored.  The time column is passed in
  *             pcq_columns.cls (see there); a match's record is the position with class 0 and colour (0,0,0)
- *             (`..Default::default()`, las.rs:345-355), so `rgb` is ignored. */
+ *             (`..Default::default()`, las.rs:345-355), so `rgb` is ignored.
+ * BOUNDS_CLASS: the BOUNDS rule on lmin/lmax AND the CLASS rule on cls (not in the reference, whose CLI rejects the
+ *             pair).  `xyz` and `cls` (class bytes, any stride >= 1) are both always read, even for a count; a match's
+ *             record is the CLASS search's: position, the class byte of `cls`, colour from `rgb`.
+ * BOUNDS_TIME: the BOUNDS rule on lmin/lmax AND the TIME rule on [wmin[0], wmax[0]).  `xyz` and `cls` (the f64 time
+ *             column, stride >= 8, any alignment) are both always read; a match's record is the TIME search's:
+ *             position, class 0, colour (0,0,0) — `rgb` is ignored.
+ *             For both: an empty integer box (lmin > lmax on an axis, or outside the i32 range) matches nothing and
+ *             launches no kernel. */
 typedef struct pcq_predicate {
     int32_t kind;               /* pcq_predicate_kind */
     uint8_t cls;
@@ -221,7 +237,7 @@ int pcq_prepare_host_scans(pcq_ctx *ctx);
 /* Count-only scan of many device-resident LAST files in ONE launch (files = independent units,
  * main.rs:153-161): segment i is scanned with preds[i] (all bounds, over 16-byte aligned positions
  * blocks — or all class, over classification blocks of any alignment); the total is ADDED to
- * *device_total.  PCQ_PRED_TIME is refused (PCQ_ERR_ARG). */
+ * *device_total.  PCQ_PRED_TIME, PCQ_PRED_BOUNDS_CLASS and PCQ_PRED_BOUNDS_TIME are refused (PCQ_ERR_ARG). */
 int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
                              size_t nsegments, uint64_t *device_total, void *stream);
 
@@ -238,8 +254,9 @@ int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_pr
  * chunk (a disjoint one is then skipped by the emit as well; a contained one is read once, for its
  * records), and the ragged tail behind the last whole bounds chunk is always read.  Results are
  * identical to pcq_scan_dev; layouts the index does not cover fall through to it: strided / LAS
- * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME
- * has no index: it is served by pcq_scan_dev, and the statistics of such a scan are all zero.
+ * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME,
+ * PCQ_PRED_BOUNDS_CLASS and PCQ_PRED_BOUNDS_TIME have no index: they are served by pcq_scan_dev, the statistics of such a
+ * scan are all zero, and the index is neither built nor changed by it.
  * Statistics of the last scan, in index chunks: for a count scan what it read; for a buffer scan the
  * chunks its count pass skipped (disjoint), took whole (contained) and read (straddling); after a
  * build, every chunk was read.  They are collected on the device and fetched (one wait) when asked.

@@ -4,6 +4,7 @@
  *
  *   Searcher::search_file for BoundsSearcher / ClassSearcher     query/src/search/searcher.rs:24-152
  *   ... and TimeSearcher (GPS time range)                         query/src/search/las.rs:297-358
+ *   ... and the combined BoundsClassSearcher / BoundsTimeSearcher  (not in the reference)
  *   CountCollector / BufferCollector / GridSampledCollector      query/src/collect_points.rs:14-127
  *   parse_aabb, get_all_input_files, is_valid_file, get_total_bounds   query/src/main.rs:29-120, 185-189
  *
@@ -73,6 +74,15 @@ int pcq_query_search_file_class(const char *path, uint8_t cls, int optimized, pc
  * searcher.rs).  .las / .last with optimized = 1; matches are recorded with class 0 and colour (0,0,0).  A file of format 0
  * or 2, or above 10, is PCQ_ERR_FORMAT; .laz / .lazer and the Regular implementation are PCQ_ERR_UNSUPPORTED. */
 int pcq_query_search_file_time(const char *path, double start, double end, int optimized, pcq_host_collector *c);
+/* The combined searches (--combine; not in the reference, whose CLI rejects the pair): a point matches when the bounds
+ * search and the class / time search would both match it.  The plan is the attribute search's (its errors, its columns and
+ * its records: class byte and colour for BOUNDS_CLASS, class 0 and colour (0,0,0) for BOUNDS_TIME), then the bounds search's
+ * header early-out (a disjoint file is 0 matches, no GPU) and pcq_box_to_local.  .las / .last with optimized = 1; .laz and
+ * .lazer and the Regular implementation are PCQ_ERR_UNSUPPORTED. */
+int pcq_query_search_file_bounds_class(const char *path, const double bmin[3], const double bmax[3], uint8_t cls, int optimized,
+                                       pcq_host_collector *c);
+int pcq_query_search_file_bounds_time(const char *path, const double bmin[3], const double bmax[3], double start, double end, int optimized,
+                                      pcq_host_collector *c);
 
 /* A dataset resident in HBM (host/resident.cpp; not in the reference, which re-reads the files for every query): the
  * positions and classification blocks of LAST files are loaded into `device`'s HBM once; every count query over them
@@ -118,6 +128,9 @@ int pcq_query_simulate_schedule(const uint64_t *cost, size_t nfiles, const doubl
  * before any GPU work.  Returns the plan's status; *needs_gpu = 1 when a scan would follow, with its columns (the pointers are
  * BYTE OFFSETS into the file) and predicate.  Wakes no GPU. */
 int pcq_query_test_plan_time(const char *path, double start, double end, pcq_columns *cols, pcq_predicate *pred, int *needs_gpu);
+/* Test entry: the same for a combined search — cls 0..255: BOUNDS AND CLASS; cls < 0: BOUNDS AND TIME over [start, end). */
+int pcq_query_test_plan_combined(const char *path, const double bmin[3], const double bmax[3], int cls, double start, double end,
+                                 pcq_columns *cols, pcq_predicate *pred, int *needs_gpu);
 /* Test entry: the two halves of a LAST bounds search with something in between — the file's plan is made (header, offsets,
  * box: the host prologue of run_search_parallel), then, if `replacement` is not NULL, that file is renamed over `path`, then the
  * plan is executed.  A plan must not be executed on another file under the same name. */

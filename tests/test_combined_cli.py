@@ -1,0 +1,242 @@
+"""The combined searches on the host side, without a GPU: `--combine` (BOUNDS AND CLASS, BOUNDS AND TIME) in the CLI, the
+plans of LAS and LAST files (the attribute search's prologue, then the bounds search's header early-out and box), the new
+entry points of the C view and the predicate kinds 4 and 5, and the compiled count kernel's pipeline.  Counts, records and
+grids are in test_gpu_combined.py.
+"""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _time_images as ti  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+QUERY = os.path.join(PKG, "host", "query")
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+
+NEITHER = "Error: Found neither BOUNDS nor CLASS argument but exactly one of these arguments is required!"
+BOTH = "Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify either BOUNDS or CLASS argument!"
+WITH_TIME = "Error: Specifying TIME together with BOUNDS or CLASS is invalid! Specify exactly one of BOUNDS, CLASS or TIME!"
+CLASS_AND_TIME = "Error: --combine joins BOUNDS with CLASS or with TIME; CLASS and TIME cannot be combined!"
+BOX = "0;0;0;1;1;1"
+
+
+def _query(args, env=None):
+    r = subprocess.run([QUERY] + args, capture_output=True, text=True, timeout=120, env=env)
+    return r.returncode, r.stdout, r.stderr
+
+
+@pytest.fixture
+def datadir(tmp_path):
+    d = tmp_path / "data"
+    d.mkdir()
+    return str(d)
+
+
+@pytest.mark.parametrize("args,rc,msg", [
+    (["--class", "2", "--time", "0;1"], 1, CLASS_AND_TIME),
+    (["--bounds", BOX, "--class", "2", "--time", "0;1"], 1, CLASS_AND_TIME),
+    ([], 1, NEITHER),
+    (["--density", "1"], 1, NEITHER),
+    (["--bounds", BOX, "--class", "256"], 101, "Could not prase argument CLASS"),   # values are parsed before they are compared
+    (["--class", "2", "--time", "zz"], 101, "Could not prase argument TIME"),
+    (["--bounds", "0;0", "--time", "0;1"], 101, None),
+])
+def test_combine_flag_matrix_errors(datadir, args, rc, msg):
+    got = _query(["-i", datadir, "--combine"] + args)
+    assert (got[0], got[1]) == (rc, ""), got
+    if msg is not None:
+        assert got[2].strip() == msg
+    else:
+        assert got[2].startswith("Could not prase argument BOUNDS"), got[2]
+
+
+@pytest.mark.parametrize("args", [["--bounds", BOX, "--class", "2"], ["--bounds", BOX, "--time", "0;1"], ["--bounds", BOX],
+                                  ["--class", "7"], ["--time", "-inf;inf"]])
+def test_combine_flag_accepts_one_box_with_one_attribute_and_single_predicates(datadir, args):
+    """The directory is empty: nothing is searched, and the accepted forms end like any other query."""
+    os.makedirs(os.path.join(datadir, "out"), exist_ok=True)
+    for extra in ([], ["--density", "0.5"], ["-o", os.path.join(datadir, "out")]):
+        rc, out, err = _query(["-i", datadir, "--combine", "--optimized", "--parallel"] + args + extra)
+        assert rc == 0, err
+        assert out.startswith("Searching 0 files...\n"), out
+
+
+@pytest.mark.parametrize("args,msg", [
+    (["--bounds", BOX, "--class", "2"], BOTH),
+    (["--bounds", BOX, "--class", "2", "--time", "0;1"], BOTH),
+    (["--bounds", BOX, "--time", "0;1"], WITH_TIME),
+    (["--class", "2", "--time", "0;1"], WITH_TIME),
+])
+def test_without_combine_the_old_messages_stand(datadir, args, msg):
+    got = _query(["-i", datadir] + args)
+    assert (got[0], got[1], got[2].strip()) == (1, "", msg)
+
+
+def test_help_lists_the_combine_flag():
+    rc, out, _ = _query(["-h"])
+    assert rc == 0
+    assert "        --combine            with --bounds, also require --class or --time (a point must match both)\n" in out
+
+
+def _write(path, img):
+    img.tofile(path)
+    return str(path)
+
+
+@pytest.fixture(scope="module")
+def qlib():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    lib.pcq_query_test_plan_combined.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double,
+                                                 C.POINTER(binding.Columns), C.POINTER(binding.Predicate), C.POINTER(C.c_int)]
+    lib.pcq_query_last_error.restype = C.c_char_p
+    return lib
+
+
+def _plan(qlib, path, bmin, bmax, cls=-1, start=0.0, end=0.0):
+    cols, pred, needs = binding.Columns(), binding.Predicate(), C.c_int(-1)
+    lo, hi = (C.c_double * 3)(*bmin), (C.c_double * 3)(*bmax)
+    rc = qlib.pcq_query_test_plan_combined(path.encode(), lo, hi, cls, start, end, C.byref(cols), C.byref(pred), C.byref(needs))
+    return rc, cols, pred, needs.value
+
+
+def _local(bmin, bmax):
+    lmin, lmax = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    lib = C.CDLL(os.path.join(PKG, "libpcq.so"))
+    assert lib.pcq_box_to_local((C.c_double * 3)(*bmin), (C.c_double * 3)(*bmax), (C.c_double * 3)(*ti.SCALE),
+                                (C.c_double * 3)(*ti.OFFSET), lmin, lmax) == 0
+    return list(lmin), list(lmax)
+
+
+BMIN, BMAX = (90.0, -230.0, -20.0), (120.0, -180.0, 40.0)
+
+
+@pytest.mark.parametrize("fmt", [1, 3, 6, 7])
+@pytest.mark.parametrize("layout", ["las", "last"])
+@pytest.mark.parametrize("attr", ["class", "time"])
+def test_plans_of_both_kinds(qlib, tmp_path, fmt, layout, attr):
+    n = 1_001
+    xyz, cls, rgb, t = ti.points(n, fmt)
+    img = ti.las_image(fmt, xyz, cls, rgb, t) if layout == "las" else ti.last_image(fmt, xyz, cls, rgb, t)
+    p = _write(tmp_path / f"f.{layout}", img)
+    if attr == "class":
+        rc, cols, pred, needs = _plan(qlib, p, BMIN, BMAX, cls=2)
+    else:
+        rc, cols, pred, needs = _plan(qlib, p, BMIN, BMAX, start=1200.0, end=1300.0)
+    assert (rc, needs) == (0, 1), qlib.pcq_query_last_error()
+    lmin, lmax = _local(BMIN, BMAX)
+    assert (list(pred.lmin), list(pred.lmax)) == (lmin, lmax)
+    otp = 375 if fmt >= 6 else 227
+    rl, toff, coff, kof = ti.FORMATS[fmt]
+    assert cols.n == n and cols.xyz == otp
+    if attr == "class":
+        assert pred.kind == binding.PRED_BOUNDS_CLASS == 4 and pred.cls == 2
+        if layout == "las":  # the class search's column: +16 on formats 6-10 (the bounds-only LAS path reads +15)
+            assert (cols.cls, cols.xyz_stride, cols.cls_stride) == (otp + kof, rl, rl)
+            has_rgb = fmt in (2, 3, 5)  # las_offset_to_color (las.rs:38-45): the class search reads no colour of formats 7, 8
+            assert cols.rgb == (otp + coff if has_rgb else None) and (not has_rgb or cols.rgb_stride == rl)
+        else:
+            assert (cols.cls, cols.xyz_stride, cols.cls_stride) == (otp + n * kof, 12, 1)
+            assert np.array_equal(img[cols.cls:cols.cls + n], cls)
+            if fmt == 3:
+                assert (cols.rgb, cols.rgb_stride) == (otp + n * coff, 6)
+    else:
+        assert pred.kind == binding.PRED_BOUNDS_TIME == 5 and (pred.wmin[0], pred.wmax[0]) == (1200.0, 1300.0)
+        assert cols.rgb is None
+        if layout == "las":
+            assert (cols.cls, cols.xyz_stride, cols.cls_stride) == (otp + toff, rl, rl)
+        else:
+            assert (cols.cls, cols.xyz_stride, cols.cls_stride) == (otp + n * toff, 12, 8)
+            assert np.array_equal(img[cols.cls:cols.cls + 8 * n].copy().view("<f8"), t)
+
+
+def test_plan_errors_and_which_wins(qlib, tmp_path):
+    xyz, cls, rgb, t = ti.points(10, 2)
+    far = ((1e6, 1e6, 1e6), (2e6, 2e6, 2e6))  # disjoint from every header
+    # the attribute prologue comes first: its errors win over a disjoint box
+    for fmt, fb, status, msg in [(0, None, -3, "does not contain GPS times!"), (1, 14, -3, "Invalid LAS format 14 in file ")]:
+        p = _write(tmp_path / "f.last", ti.las_image(fmt, xyz, cls, rgb, t, fmt_byte=fb))
+        rc, _, _, needs = _plan(qlib, p, *far, start=0.0, end=1.0)
+        assert (rc, needs) == (status, 0)
+        assert msg in qlib.pcq_query_last_error().decode()
+    p = _write(tmp_path / "c.las", ti.las_image(1, xyz, cls, rgb, t, fmt_byte=12))
+    rc, _, _, needs = _plan(qlib, p, *far, cls=2)
+    assert (rc, needs) == (binding.PCQ_ERR_HEADER, 0)  # the class search's header parse rejects the format byte itself
+    # format 0 has no time but a class byte: the class combination plans it
+    p = _write(tmp_path / "z.las", ti.las_image(0, xyz, cls, rgb, t))
+    assert _plan(qlib, p, BMIN, BMAX, cls=2)[::3] == (0, 1)
+    # EOF of a needed block, before the early-out
+    full = ti.last_image(1, xyz, cls, rgb, t)
+    p = _write(tmp_path / "t.last", full[:-1])
+    assert _plan(qlib, p, *far, start=0.0, end=1.0)[::3] == (-5, 0)
+    assert _plan(qlib, p, *far, cls=2)[::3] == (0, 0)  # (the class search needs no time block)
+    p = _write(tmp_path / "c.last", full[:-(12 * 10 + 1)])  # the class block's last byte gone
+    assert _plan(qlib, p, *far, cls=2)[::3] == (-5, 0)
+    # then the header early-out: a disjoint box is 0 matches on the host
+    p = _write(tmp_path / "ok.last", full)
+    assert _plan(qlib, p, *far, cls=2)[::3] == (0, 0)
+    assert _plan(qlib, p, *far, start=0.0, end=1.0)[::3] == (0, 0)
+    # an empty file needs no GPU either
+    p = _write(tmp_path / "e.las", ti.las_image(1, xyz[:0], cls[:0], rgb[:0], t[:0]))
+    assert _plan(qlib, p, BMIN, BMAX, cls=2)[::3] == (0, 0)
+
+
+def test_a_box_disjoint_from_every_header_needs_no_gpu(datadir):
+    for k in range(3):
+        xyz, cls, rgb, t = ti.points(500, 10 + k)
+        _write(os.path.join(datadir, f"f{k}.last"), ti.last_image(3, xyz, cls, rgb, t))
+        _write(os.path.join(datadir, f"g{k}.las"), ti.las_image(6, xyz, cls, rgb, t))
+    env = dict(os.environ, PCQ_TIMING="1")
+    for attr in (["--class", "2"], ["--time", "-inf;inf"]):
+        rc, out, err = _query(["-i", datadir, "--combine", "--optimized", "--parallel", "--bounds", "1e6;1e6;1e6;2e6;2e6;2e6"] + attr, env)
+        assert rc == 0, err
+        lines = out.splitlines()
+        assert lines[0] == "Searching 6 files..." and lines[1] == "Found 0 matching points", out
+        assert "0 of 6 files need the GPU" in err and "context on device" not in err, err
+        assert "Point record size" not in out
+
+
+def test_query_library_exports_the_combined_searches():
+    hdr = open(os.path.join(ROOT, "include", "pcq_query.h")).read()
+    assert re.search(r"int pcq_query_search_file_bounds_class\(const char \*path, const double bmin\[3\], const double bmax\[3\], uint8_t cls, "
+                     r"int optimized,\s+pcq_host_collector \*c\);", hdr)
+    assert re.search(r"int pcq_query_search_file_bounds_time\(const char \*path, const double bmin\[3\], const double bmax\[3\], double start, "
+                     r"double end, int optimized,\s+pcq_host_collector \*c\);", hdr)
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    for sym in ("pcq_query_search_file_bounds_class", "pcq_query_search_file_bounds_time", "pcq_query_test_plan_combined"):
+        assert hasattr(lib, sym), sym
+    pcq_h = open(os.path.join(ROOT, "include", "pcq.h")).read()
+    assert re.search(r"PCQ_PRED_BOUNDS_CLASS = 4\b", pcq_h) and re.search(r"PCQ_PRED_BOUNDS_TIME = 5\b", pcq_h)
+    assert (binding.PRED_BOUNDS_CLASS, binding.PRED_BOUNDS_TIME) == (4, 5)
+    p = binding.Predicate.bounds_class([1, 2, 3], [4, 5, 6], 9)
+    assert (p.kind, list(p.lmin), list(p.lmax), p.cls) == (4, [1, 2, 3], [4, 5, 6], 9)
+    p = binding.Predicate.bounds_time([1, 2, 3], [4, 5, 6], -1.5, float("inf"))
+    assert (p.kind, list(p.lmin), list(p.lmax), p.wmin[0], p.wmax[0]) == (5, [1, 2, 3], [4, 5, 6], -1.5, float("inf"))
+    assert C.CDLL(os.path.join(PKG, "libpcq.so")).pcq_abi_version() == 6
+
+
+def test_combined_count_kernel_keeps_its_loads_in_flight():
+    """K1 with a second column (scan_count.hip): the class bytes / times of the next step are asked for with its positions
+    and no wait for all loads (vmcnt(0)) stands right behind any of the pipeline's loads; nothing spills to scratch."""
+    from test_abi_and_host import _kernel_asm, _kernel_bodies
+    found = {}
+    for name, body in _kernel_bodies(_kernel_asm("scan_count.hip"), "k_bounds_count_w1_pipe"):
+        col = "ClassBytes" if "ClassBytes" in name else "GpsTimes" if "GpsTimes" in name else None
+        if col is None:
+            continue
+        assert not [l for l in body if l.strip().startswith("scratch_")], name
+        loads = [n for n, l in enumerate(body) if l.strip().startswith("global_load") and l.rstrip().endswith(" nt")]
+        col_loads = [n for n in loads if ("dword " in body[n] if col == "ClassBytes" else " s[" in body[n])]
+        for n in loads:
+            assert not any("vmcnt(0)" in x for x in body[n + 1:n + 3]), (name, body[n].strip())
+        assert len(col_loads) >= 8, (name, len(col_loads))  # two per tile, two tiles per step, two register sets
+        assert sum("ds_bpermute_b32" in l for l in body) >= 12, name
+        found[col] = True
+    assert found == {"ClassBytes": True, "GpsTimes": True}
