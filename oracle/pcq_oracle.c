@@ -616,6 +616,203 @@ int pcqo_search_las_mem_by_classification_optimized(const uint8_t *data, size_t 
 }
 
 /* ------------------------------------------------------------------------------------------ */
+/* GPS time-range scans — las.rs:297-358; LAST: DESIGN.md §8 (last.rs:339-400 is a todo!())  */
+/* ------------------------------------------------------------------------------------------ */
+
+static int rd_f64(const image *im, uint64_t off, double *v) {
+    if (off > im->len || im->len - off < 8) return 0;
+    *v = lef64(im->p + off);
+    return 1;
+}
+
+/* `bytes` bytes at `off` lie inside the image (no overflow on absurd point counts) */
+static int span_ok(const image *im, uint64_t off, uint64_t n, uint64_t width) {
+    if (off > im->len) return 0;
+    return n == 0 || (im->len - off) / width >= n;
+}
+
+/* Range<f64>::contains — `start <= t && t < end` in IEEE arithmetic (las.rs:336) */
+static int time_in(double t, double start, double end) { return start <= t && t < end; }
+
+/* las.rs:302-330: raw::Header::read_from + Header::from_raw on the raw format byte, then the match on it.  DESIGN.md §8:
+ * a format above 10 reports the match arm's "Invalid LAS format" (:324-329), not the error from_raw raises first. */
+static int time_prologue(const uint8_t *data, size_t len, const char *path, pcqo_las_header *h, uint64_t *t_in_point) {
+    int rc = pcqo_parse_las_header(data, len, 0, h);
+    if (rc == PCQO_ERR_HEADER && strncmp(g_err, "invalid point format number", 27) == 0)
+        return fail(PCQO_ERR_FORMAT, "Invalid LAS format %u in file %s", data[104], path);
+    if (rc) return rc;
+    switch (h->point_data_record_format) {
+    case 0: /* :306-311 */
+    case 2: /* :313-318 */
+        return fail(PCQO_ERR_FORMAT, "File %s does not contain GPS times!", path);
+    case 1: /* :312 */
+    case 3: case 4: case 5: /* :319 */
+        *t_in_point = 20;
+        return PCQO_OK;
+    default: /* 6..=10, :320 */
+        *t_in_point = 22;
+        return PCQO_OK;
+    }
+}
+
+/* las.rs:345-355: the position and `..Default::default()` — class 0, colour (0, 0, 0) */
+static void time_record(const pcqo_las_header *h, int32_t xi, int32_t yi, int32_t zi, pcqo_point *pt) {
+    memset(pt, 0, sizeof *pt);
+    pt->x = ((double)xi * h->scale[0]) + h->offset[0]; /* :347-351, unfused */
+    pt->y = ((double)yi * h->scale[1]) + h->offset[1];
+    pt->z = ((double)zi * h->scale[2]) + h->offset[2];
+}
+
+/* las.rs:297-358 */
+int pcqo_search_las_mem_by_time_range_optimized(const uint8_t *data, size_t len, const char *path, double start,
+                                                double end, pcqo_collector *c) {
+    image im = {data, len};
+    pcqo_las_header h;
+    uint64_t t_in_point = 0;
+    int rc = time_prologue(data, len, path, &h, &t_in_point);
+    if (rc) return rc;
+    uint64_t n = h.number_of_points;
+    for (uint64_t idx = 0; idx < n; idx++) { /* :332 */
+        uint64_t at = idx * (uint64_t)h.point_data_record_length + (uint64_t)h.offset_to_point_data; /* :333-334 */
+        double t;
+        if (!rd_f64(&im, at + t_in_point, &t)) return fail(PCQO_ERR_EOF, "failed to fill whole buffer"); /* :335-336 */
+        if (!time_in(t, start, end)) continue;                                                          /* :337-339 */
+        int32_t xi, yi, zi;                                                                              /* :341-344 */
+        if (!rd_i32(&im, at, &xi) || !rd_i32(&im, at + 4, &yi) || !rd_i32(&im, at + 8, &zi))
+            return fail(PCQO_ERR_EOF, "failed to fill whole buffer");
+        pcqo_point pt;
+        time_record(&h, xi, yi, zi, &pt);
+        pcqo_collector_collect_one(c, &pt);
+    }
+    return PCQO_OK;
+}
+
+/* the LAS body on the transposed record (last_reader.rs:83-144) — the times are one block of n f64 at
+ * offset_to_point_data + n * 20 (formats 1, 3-5) or + n * 22 (6-10); the positions block and the time block are checked
+ * for EOF before the loop. */
+int pcqo_search_last_mem_by_time_range_optimized(const uint8_t *data, size_t len, const char *path, double start,
+                                                 double end, pcqo_collector *c) {
+    image im = {data, len};
+    pcqo_las_header h;
+    uint64_t t_in_point = 0;
+    int rc = time_prologue(data, len, path, &h, &t_in_point);
+    if (rc) return rc;
+    uint64_t n = h.number_of_points, otp = h.offset_to_point_data;
+    if (n == 0) return PCQO_OK;
+    uint64_t time_block = otp + n * t_in_point;
+    if (!span_ok(&im, otp, n, 12) || !span_ok(&im, time_block, n, 8))
+        return fail(PCQO_ERR_EOF, "failed to fill whole buffer");
+    for (uint64_t idx = 0; idx < n; idx++) {
+        double t = lef64(data + time_block + 8 * idx);
+        if (!time_in(t, start, end)) continue;
+        const uint8_t *q = data + otp + 12 * idx;
+        pcqo_point pt;
+        time_record(&h, (int32_t)le32(q), (int32_t)le32(q + 4), (int32_t)le32(q + 8), &pt);
+        pcqo_collector_collect_one(c, &pt);
+    }
+    return PCQO_OK;
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* combined scans: the box AND a class byte or a GPS time range (not in the reference)        */
+/* ------------------------------------------------------------------------------------------ */
+
+/* DESIGN.md §8, in its order: (1) the attribute search's prologue as it stands — header parse with its masking rule
+ * (las.rs:199-200 raw, last.rs:220-223 masked; las.rs:302-303 raw for TIME), format errors, "does not contain GPS times!",
+ * and the EOF checks of every block that search may touch, positions included; (2) the bounds search's header early-out
+ * (last.rs:92-94); (3) the box in local integers (last.rs:98-109: PCQO_ERR_PANIC when min > max); (4) per point, the box
+ * (last.rs:117-135) AND the attribute.  Records are the attribute search's: for CLASS its class byte (+16 on LAS
+ * formats 6-10) and colour (las.rs:240-248, last.rs:272-280); for TIME class 0 and colour (0, 0, 0) (las.rs:345-355). */
+static int search_mem_combined(const uint8_t *data, size_t len, int transposed, int time_attr, const char *path,
+                               const double bmin[3], const double bmax[3], uint8_t cls, double start, double end,
+                               pcqo_collector *c) {
+    image im = {data, len};
+    pcqo_las_header h;
+    uint64_t attr_in_point = 0, col_in_point = 0;
+    int has_color = 0, rc;
+    if (time_attr) {
+        rc = time_prologue(data, len, path, &h, &attr_in_point);
+        if (rc) return rc;
+    } else {
+        rc = pcqo_parse_las_header(data, len, transposed, &h); /* last.rs:220-223 masks, las.rs:199-200 does not */
+        if (rc) return rc;
+        uint8_t fmt = h.point_data_record_format;
+        if (fmt <= 5) attr_in_point = 15; /* las.rs:202-212, last.rs:226-236 */
+        else if (fmt <= 10) attr_in_point = 16;
+        else return fail(PCQO_ERR_FORMAT, "Invalid LAS format %u in file %s", fmt, path);
+        has_color = color_offset_for(fmt, &col_in_point); /* las.rs:214-219, last.rs:238-243 */
+    }
+    uint64_t n = h.number_of_points, otp = h.offset_to_point_data, rl = h.point_data_record_length;
+    uint64_t attr_w = time_attr ? 8 : 1;
+    if (n > 0) {
+        int ok;
+        if (transposed) {
+            ok = span_ok(&im, otp, n, 12) && span_ok(&im, otp + n * attr_in_point, n, attr_w) &&
+                 (!has_color || span_ok(&im, otp + n * col_in_point, n, 6));
+        } else { /* every record up to the last byte the search may read */
+            uint64_t need = 12;
+            if (attr_in_point + attr_w > need) need = attr_in_point + attr_w;
+            if (has_color && col_in_point + 6 > need) need = col_in_point + 6;
+            ok = n - 1 <= (UINT64_MAX - need) / (rl ? rl : 1) && span_ok(&im, otp, (n - 1) * rl + need, 1);
+        }
+        if (!ok) return fail(PCQO_ERR_EOF, "failed to fill whole buffer");
+    }
+
+    if (!pcqo_aabb_intersects(h.min, h.max, bmin, bmax)) return PCQO_OK; /* last.rs:92-94 */
+    int64_t lmin[3], lmax[3];
+    rc = pcqo_box_to_local(bmin, bmax, h.scale, h.offset, lmin, lmax); /* last.rs:98-109 */
+    if (rc) return rc;
+
+    for (uint64_t idx = 0; idx < n; idx++) {
+        uint64_t rec = transposed ? otp + 12 * idx : otp + idx * rl;
+        int32_t xyz[3] = {(int32_t)le32(data + rec), (int32_t)le32(data + rec + 4), (int32_t)le32(data + rec + 8)};
+        int inside = 1;
+        for (int a = 0; a < 3; a++) inside &= (int64_t)xyz[a] >= lmin[a] && (int64_t)xyz[a] <= lmax[a];
+        uint64_t attr_at = transposed ? otp + n * attr_in_point + attr_w * idx : rec + attr_in_point;
+        pcqo_point pt;
+        if (time_attr) {
+            if (!inside || !time_in(lef64(data + attr_at), start, end)) continue;
+            time_record(&h, xyz[0], xyz[1], xyz[2], &pt);
+        } else {
+            uint8_t k = data[attr_at];
+            if (!inside || k != cls) continue; /* las.rs:229-231, last.rs:259-262: the whole byte */
+            pt.r = pt.g = pt.b = 0;
+            if (has_color) {
+                const uint8_t *q = transposed ? data + otp + n * col_in_point + 6 * idx : data + rec + col_in_point;
+                pt.r = le16(q), pt.g = le16(q + 2), pt.b = le16(q + 4);
+            }
+            pt.x = ((double)xyz[0] * h.scale[0]) + h.offset[0]; /* las.rs:251-255, last.rs:283-287 */
+            pt.y = ((double)xyz[1] * h.scale[1]) + h.offset[1];
+            pt.z = ((double)xyz[2] * h.scale[2]) + h.offset[2];
+            pt.classification = k;
+        }
+        pcqo_collector_collect_one(c, &pt);
+    }
+    return PCQO_OK;
+}
+
+int pcqo_search_las_mem_by_bounds_and_class_optimized(const uint8_t *data, size_t len, const char *path,
+                                                      const double bmin[3], const double bmax[3], uint8_t cls,
+                                                      pcqo_collector *c) {
+    return search_mem_combined(data, len, 0, 0, path, bmin, bmax, cls, 0.0, 0.0, c);
+}
+int pcqo_search_last_mem_by_bounds_and_class_optimized(const uint8_t *data, size_t len, const char *path,
+                                                       const double bmin[3], const double bmax[3], uint8_t cls,
+                                                       pcqo_collector *c) {
+    return search_mem_combined(data, len, 1, 0, path, bmin, bmax, cls, 0.0, 0.0, c);
+}
+int pcqo_search_las_mem_by_bounds_and_time_optimized(const uint8_t *data, size_t len, const char *path,
+                                                     const double bmin[3], const double bmax[3], double start,
+                                                     double end, pcqo_collector *c) {
+    return search_mem_combined(data, len, 0, 1, path, bmin, bmax, 0, start, end, c);
+}
+int pcqo_search_last_mem_by_bounds_and_time_optimized(const uint8_t *data, size_t len, const char *path,
+                                                      const double bmin[3], const double bmax[3], double start,
+                                                      double end, pcqo_collector *c) {
+    return search_mem_combined(data, len, 1, 1, path, bmin, bmax, 0, start, end, c);
+}
+
+/* ------------------------------------------------------------------------------------------ */
 /* file level: open + mmap (last.rs:27-34); dispatch (searcher.rs:43-152)                     */
 /* ------------------------------------------------------------------------------------------ */
 
@@ -629,6 +826,11 @@ static const char *path_extension(const char *path) { /* Path::extension() */
 
 int pcqo_search_file(const char *path, int query_kind, const double bmin[3], const double bmax[3],
                      uint8_t cls, pcqo_collector *c, int *record_size_printed) {
+    return pcqo_search_file_range(path, query_kind, bmin, bmax, cls, 0.0, 0.0, c, record_size_printed);
+}
+
+int pcqo_search_file_range(const char *path, int query_kind, const double bmin[3], const double bmax[3], uint8_t cls,
+                           double start, double end, pcqo_collector *c, int *record_size_printed) {
     const char *ext = path_extension(path);
     if (!ext) return fail(PCQO_ERR_EXTENSION, "Invalid extension on file %s", path);
     int is_las = strcmp(ext, "las") == 0, is_last = strcmp(ext, "last") == 0, is_lazer = strcmp(ext, "lazer") == 0;
@@ -653,7 +855,14 @@ int pcqo_search_file(const char *path, int query_kind, const double bmin[3], con
     }
     close(fd);
     int rc;
-    if (is_lazer) /* searcher.rs:83, :144 — one implementation for Regular and Optimized */
+    if (query_kind >= PCQO_QUERY_TIME && is_lazer) /* lazer.rs:115-122 is a todo!(); DESIGN.md §8 */
+        rc = fail(PCQO_ERR_UNSUPPORTED, "%s search in .lazer files", query_kind == PCQO_QUERY_TIME ? "time" : "combined");
+    else if (query_kind == PCQO_QUERY_TIME)
+        rc = is_last ? pcqo_search_last_mem_by_time_range_optimized(p, len, path, start, end, c)
+                     : pcqo_search_las_mem_by_time_range_optimized(p, len, path, start, end, c);
+    else if (query_kind == PCQO_QUERY_BOUNDS_CLASS || query_kind == PCQO_QUERY_BOUNDS_TIME)
+        rc = search_mem_combined(p, len, is_last, query_kind == PCQO_QUERY_BOUNDS_TIME, path, bmin, bmax, cls, start, end, c);
+    else if (is_lazer) /* searcher.rs:83, :144 — one implementation for Regular and Optimized */
         rc = query_kind == PCQO_QUERY_BOUNDS ? pcqo_search_lazer_mem_by_bounds(p, len, bmin, bmax, c)
                                              : pcqo_search_lazer_mem_by_classification(p, len, cls, c);
     else if (is_last)

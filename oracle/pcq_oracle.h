@@ -36,7 +36,8 @@ enum {
     PCQO_ERR_EOF = -5,          /* read past the end of the mmap (UnexpectedEof)                       */
     PCQO_ERR_GRID = -6,         /* "Too many cells ... in SparseGrid"           (grid_sampling.rs:32-34)*/
     PCQO_ERR_PANIC = -7,        /* AABB::from_min_max min > max panic           (last.rs:98)           */
-    PCQO_ERR_ARG = -8           /* bad argument to the oracle API itself                               */
+    PCQO_ERR_ARG = -8,          /* bad argument to the oracle API itself                               */
+    PCQO_ERR_UNSUPPORTED = -11  /* a todo!() of the reference (time / combined .lazer)   */
 };
 
 /* readers/src/lib.rs:10-19 — #[repr(C, packed)] Point, 31 bytes. */
@@ -123,6 +124,26 @@ int pcqo_search_las_mem_by_bounds_optimized(const uint8_t *data, size_t len, con
 int pcqo_search_las_mem_by_classification_optimized(const uint8_t *data, size_t len, uint8_t cls,
                                                     pcqo_collector *c);
 
+/* ---- GPS time range [start, end): las.rs:297-358; the LAST form is DESIGN.md §8's (last.rs:339-400 is a todo!()).
+ *      `path` appears in the format messages only. ---- */
+int pcqo_search_las_mem_by_time_range_optimized(const uint8_t *data, size_t len, const char *path, double start,
+                                                double end, pcqo_collector *c);
+int pcqo_search_last_mem_by_time_range_optimized(const uint8_t *data, size_t len, const char *path, double start,
+                                                 double end, pcqo_collector *c);
+/* ---- combined searches (not in the reference): the box AND a class byte or a time range ---- */
+int pcqo_search_las_mem_by_bounds_and_class_optimized(const uint8_t *data, size_t len, const char *path,
+                                                      const double bmin[3], const double bmax[3], uint8_t cls,
+                                                      pcqo_collector *c);
+int pcqo_search_last_mem_by_bounds_and_class_optimized(const uint8_t *data, size_t len, const char *path,
+                                                       const double bmin[3], const double bmax[3], uint8_t cls,
+                                                       pcqo_collector *c);
+int pcqo_search_las_mem_by_bounds_and_time_optimized(const uint8_t *data, size_t len, const char *path,
+                                                     const double bmin[3], const double bmax[3], double start,
+                                                     double end, pcqo_collector *c);
+int pcqo_search_last_mem_by_bounds_and_time_optimized(const uint8_t *data, size_t len, const char *path,
+                                                      const double bmin[3], const double bmax[3], double start,
+                                                      double end, pcqo_collector *c);
+
 /* ---- LAZER (lazer_oracle.c): query/src/search/lazer.rs:34-116 over readers/src/lazer_reader.rs ---- */
 int pcqo_search_lazer_mem_by_bounds(const uint8_t *data, size_t len, const double bmin[3], const double bmax[3],
                                     pcqo_collector *c);
@@ -145,9 +166,18 @@ void pcqo_free(void *p);
 
 /* ---- file-level: open + mmap (last.rs:27-34) then the scans above; dispatch by extension
  *      restates searcher.rs:43-152 for the ("las"|"last", Optimized) and "lazer" arms. ---- */
-enum { PCQO_QUERY_BOUNDS = 0, PCQO_QUERY_CLASS = 1 };
+enum {
+    PCQO_QUERY_BOUNDS = 0,
+    PCQO_QUERY_CLASS = 1,
+    PCQO_QUERY_TIME = 2,         /* [start, end) */
+    PCQO_QUERY_BOUNDS_CLASS = 3, /* box AND class */
+    PCQO_QUERY_BOUNDS_TIME = 4   /* box AND [start, end) */
+};
 int pcqo_search_file(const char *path, int query_kind, const double bmin[3], const double bmax[3],
                      uint8_t cls, pcqo_collector *c, int *record_size_printed);
+/* the same with the time range of PCQO_QUERY_TIME / _BOUNDS_TIME */
+int pcqo_search_file_range(const char *path, int query_kind, const double bmin[3], const double bmax[3], uint8_t cls,
+                           double start, double end, pcqo_collector *c, int *record_size_printed);
 
 /* Multi-threaded count scan used as the CPU baseline: one thread per file image, at most
  * `threads` at a time (rayon par_iter, main.rs:153-161), counts summed (main.rs:164-180). */

@@ -6,7 +6,8 @@
  * Restates: get_all_input_files main.rs:29-57 · parse_aabb :59-92 · get_total_bounds :94-120 ·
  * run_search_sequential :122-144 · run_search_parallel :146-183 · is_valid_file :185-189 ·
  * main :191-319.  Only the `--optimized` arms for .las/.last exist here (SURVEY.md §2 rows 12-15 are
- * out of scope); anything else is reported as an error.
+ * out of scope); anything else is reported as an error.  `--time "START;END"` and `--combine` are not in the reference's
+ * CLI: their messages, exit codes and precedence are DESIGN.md §8's.
  */
 #define _GNU_SOURCE
 #include "pcq_oracle.h"
@@ -124,18 +125,20 @@ static int read_header(const char *path, int mask, pcqo_las_header *h) {
 int main(int argc, char **argv) {
     struct timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
-    const char *input = NULL, *bounds_s = NULL, *class_s = NULL, *output = NULL, *density_s = NULL;
-    int parallel = 0, optimized = 0;
+    const char *input = NULL, *bounds_s = NULL, *class_s = NULL, *time_s = NULL, *output = NULL, *density_s = NULL;
+    int parallel = 0, optimized = 0, combine = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
         const char **dst = NULL;
         if (!strcmp(a, "-i") || !strcmp(a, "--input")) dst = &input;
         else if (!strcmp(a, "--bounds")) dst = &bounds_s;
         else if (!strcmp(a, "--class")) dst = &class_s;
+        else if (!strcmp(a, "--time")) dst = &time_s;
         else if (!strcmp(a, "-o") || !strcmp(a, "--output")) dst = &output;
         else if (!strcmp(a, "--density")) dst = &density_s;
         else if (!strcmp(a, "--parallel")) { parallel = 1; continue; }
         else if (!strcmp(a, "--optimized")) { optimized = 1; continue; }
+        else if (!strcmp(a, "--combine")) { combine = 1; continue; }
         else {
             fprintf(stderr, "error: Found argument '%s' which wasn't expected\n", a);
             return 1;
@@ -184,28 +187,58 @@ int main(int argc, char **argv) {
         }
         cls = (unsigned)v;
     }
+    double tstart = 0, tend = 0;
+    if (time_s) { /* "START;END", each half parsed like a --bounds component; a panic as for its siblings */
+        const char *semi = strchr(time_s, ';');
+        int ok = semi && !strchr(semi + 1, ';');
+        if (ok) {
+            char *head = strndup(time_s, (size_t)(semi - time_s));
+            ok = parse_f64(head, &tstart) && parse_f64(semi + 1, &tend);
+            free(head);
+        }
+        if (!ok) {
+            fprintf(stderr, "Could not prase argument TIME\n");
+            return 101;
+        }
+    }
     if (density_s && !parse_f64(density_s, &density)) { /* main.rs:237 */
         fprintf(stderr, "Could not prase argument DENSITY\n");
         return 101;
     }
-    if (bounds_s && class_s) { /* main.rs:238-240 */
-        fprintf(stderr, "Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify "
-                        "either BOUNDS or CLASS argument!\n");
-        return 1;
+    if (combine) { /* --combine joins BOUNDS with CLASS or with TIME */
+        if (class_s && time_s) {
+            fprintf(stderr, "Error: --combine joins BOUNDS with CLASS or with TIME; CLASS and TIME cannot be combined!\n");
+            return 1;
+        }
+    } else {
+        if (bounds_s && class_s) { /* main.rs:238-240 */
+            fprintf(stderr, "Error: Specifying BOUNDS and CLASS at the same time is invalid! Specify "
+                            "either BOUNDS or CLASS argument!\n");
+            return 1;
+        }
+        if (time_s && (bounds_s || class_s)) { /* DESIGN.md §8 */
+            fprintf(stderr, "Error: Specifying TIME together with BOUNDS or CLASS is invalid! Specify exactly one of "
+                            "BOUNDS, CLASS or TIME!\n");
+            return 1;
+        }
     }
-    if (!bounds_s && !class_s) { /* main.rs:242-244 */
+    if (!bounds_s && !class_s && !time_s) { /* main.rs:242-244 */
         fprintf(stderr, "Error: Found neither BOUNDS nor CLASS argument but exactly one of these "
                         "arguments is required!\n");
         return 1;
     }
-    int kind = bounds_s ? PCQO_QUERY_BOUNDS : PCQO_QUERY_CLASS;
+    int kind = bounds_s && class_s  ? PCQO_QUERY_BOUNDS_CLASS
+               : bounds_s && time_s ? PCQO_QUERY_BOUNDS_TIME
+               : bounds_s           ? PCQO_QUERY_BOUNDS
+               : class_s            ? PCQO_QUERY_CLASS
+                                    : PCQO_QUERY_TIME;
 
     double gmin[3], gmax[3];
     if (density_s) { /* main.rs:253-264 */
-        if (bounds_s) {
+        if (bounds_s) { /* (--combine too: the query box) */
             memcpy(gmin, bmin, sizeof gmin);
             memcpy(gmax, bmax, sizeof gmax);
-        } else { /* get_total_bounds, main.rs:94-120 */
+        } else { /* get_total_bounds, main.rs:94-120 (--time too) */
             for (int a = 0; a < 3; a++) gmin[a] = 1.7976931348623157e308, gmax[a] = -1.7976931348623157e308;
             for (size_t i = 0; i < files.n; i++) {
                 const char *e = ext_of(files.v[i]);
@@ -267,8 +300,8 @@ int main(int argc, char **argv) {
     /* The per-file work is order-independent in parallel mode; the oracle runs it in file order. */
     for (size_t i = 0; i < files.n; i++) {
         int recsz = -1;
-        int rc = pcqo_search_file(files.v[i], kind, bmin, bmax, (uint8_t)cls,
-                                  coll[parallel ? i : 0], &recsz);
+        int rc = pcqo_search_file_range(files.v[i], kind, bmin, bmax, (uint8_t)cls, tstart, tend,
+                                        coll[parallel ? i : 0], &recsz);
         if (recsz >= 0) printf("Point record size: %d\n", recsz); /* las.rs:73 */
         if (rc == PCQO_ERR_PANIC) {
             fprintf(stderr, "%s\n", pcqo_last_error());

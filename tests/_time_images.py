@@ -20,9 +20,13 @@ FORMATS = {
     1: (28, 20, None, 15),
     2: (26, None, 20, 15),
     3: (34, 20, 28, 15),
+    4: (57, 20, None, 15),   # format 1 + a 29-byte wave packet
+    5: (63, 20, 28, 15),     # format 3 + the wave packet
     6: (30, 22, None, 16),
     7: (36, 22, 30, 16),
     8: (38, 22, 30, 16),
+    9: (59, 22, None, 16),   # format 6 + the wave packet
+    10: (67, 22, 30, 16),    # format 8 + the wave packet
 }
 
 SCALE = (0.01, 0.02, 0.05)
@@ -59,17 +63,19 @@ def records(fmt, xyz, cls, rgb, t):
     return rec
 
 
-def header(fmt, n, xyz, scale=SCALE, offset=OFFSET, fmt_byte=None):
-    """LAS 1.2 header (227 bytes) for formats up to 5, LAS 1.4 (375 bytes, 64-bit point count) for 6-10."""
+def header(fmt, n, xyz, scale=SCALE, offset=OFFSET, fmt_byte=None, v14=None, legacy=None):
+    """LAS 1.2 header (227 bytes) for formats up to 5, LAS 1.4 (375 bytes, 64-bit point count) for 6-10.  v14=True gives
+    formats up to 5 the 1.4 header too; legacy=False leaves its legacy point count 0 (the 64-bit count then holds n)."""
     rl = FORMATS[fmt][0] if fmt in FORMATS else 34
-    v14 = fmt >= 6
+    v14 = fmt >= 6 if v14 is None else v14
+    legacy = not v14 if legacy is None else legacy
     size = 375 if v14 else 227
     h = bytearray(size)
     h[0:4] = b"LASF"
     h[24], h[25] = 1, (4 if v14 else 2)
     struct.pack_into("<HII", h, 94, size, size, 0)
     h[104] = fmt if fmt_byte is None else fmt_byte
-    struct.pack_into("<HI", h, 105, rl, 0 if v14 else n)
+    struct.pack_into("<HI", h, 105, rl, n if legacy else 0)
     struct.pack_into("<3d", h, 131, *scale)
     struct.pack_into("<3d", h, 155, *offset)
     w = world(xyz, scale, offset) if n else np.zeros((1, 3))
@@ -80,12 +86,12 @@ def header(fmt, n, xyz, scale=SCALE, offset=OFFSET, fmt_byte=None):
     return bytes(h)
 
 
-def las_image(fmt, xyz, cls, rgb, t, fmt_byte=None):
+def las_image(fmt, xyz, cls, rgb, t, fmt_byte=None, **hdr):
     rec = records(fmt, xyz, cls, rgb, t)
-    return np.concatenate([np.frombuffer(header(fmt, len(xyz), xyz, fmt_byte=fmt_byte), dtype=np.uint8), rec.reshape(-1)])
+    return np.concatenate([np.frombuffer(header(fmt, len(xyz), xyz, fmt_byte=fmt_byte, **hdr), dtype=np.uint8), rec.reshape(-1)])
 
 
-def last_image(fmt, xyz, cls, rgb, t):
+def last_image(fmt, xyz, cls, rgb, t, fmt_byte=None, **hdr):
     """The LAS record transposed by attribute: positions, time and colour as one block each, every other byte alone."""
     rl, toff, coff, _ = FORMATS[fmt]
     rec = records(fmt, xyz, cls, rgb, t)
@@ -95,7 +101,7 @@ def last_image(fmt, xyz, cls, rgb, t):
         attrs.append((o, s))
         o += s
     body = np.concatenate([np.ascontiguousarray(rec[:, a:a + s]).reshape(-1) for a, s in attrs])
-    return np.concatenate([np.frombuffer(header(fmt, len(xyz), xyz), dtype=np.uint8), body])
+    return np.concatenate([np.frombuffer(header(fmt, len(xyz), xyz, fmt_byte=fmt_byte, **hdr), dtype=np.uint8), body])
 
 
 def time_offset(fmt):

@@ -5,7 +5,7 @@ The reference (Rust) cannot be built or run in the container and its own tests p
 (query/src/grid_sampling.rs:116-209), so the known-answer vectors here are derived by evaluating
 the reference's expressions literally with Python's IEEE-754 doubles and arbitrary-precision
 integers — a restatement independent of oracle/*.c — on inputs small enough to check by hand.
-Each block cites the reference lines it evaluates.  Output: expected.json, tiny_fmt2.last,
+Each block cites the reference lines it evaluates.  Output: expected.json, tiny_fmt4.las, tiny_fmt9.last, tiny_fmt2.last,
 tiny_fmt3.las (a few hundred bytes each).
 
 Run:  python tests/golden/make_golden.py      (deterministic; rewrites the files in place)
@@ -171,6 +171,70 @@ def records(indices, pts_world):
     return [[pts_world[i][0].hex(), pts_world[i][1].hex(), pts_world[i][2].hex(), *POINTS[i][4], POINTS[i][3]] for i in indices]
 
 
+# ---- GPS time search (las.rs:297-358) and the combined searches ----------------------------------------------
+TIME_IDX = [0, 1, 2, 3, 4, 5, 7, 8]   # POINTS without the i32 extreme (a header box one can check by hand)
+TIMES = [0.0, -0.0, float("nan"), 1.5, 2.5, 5e-324, -1.0, float("inf")]
+TIME_RANGES = [(0.0, 2.0), (-0.0, 0.0), (float("-inf"), float("inf")), (float("nan"), 1.0), (-1.0, 5e-324), (2.5, 2.5), (3.0, -3.0)]
+
+
+def hexf(v):
+    return v.hex() if v == v else "nan"
+
+
+def time_files():
+    """format 4 LAS (1.2, record 57: cls@15, gps@20, a 29-byte wave packet@28) and format 9 LAST (1.4 header of 375 bytes,
+    legacy count 0; record 59: cls@16, gps@22, wave packet@30), the same points and times"""
+    pts = [POINTS[i] for i in TIME_IDX]
+    n = len(pts)
+    pts_world = [tuple(world(p[a], SCALE[a], OFFSET[a]) for a in range(3)) for p in pts]
+    las = bytearray(header(4, 57, n, pts_world)) + bytearray(57 * n)
+    for i, (x, y, z, c, _) in enumerate(pts):
+        o = 227 + 57 * i
+        struct.pack_into("<iii", las, o, x, y, z)
+        las[o + 15] = c
+        las[o + 16] = 0xEE  # scan angle: a byte that is not the class
+        struct.pack_into("<d", las, o + 20, TIMES[i])
+    h = bytearray(header(9, 59, n, pts_world)) + bytearray(375 - 227)
+    h[25] = 4
+    struct.pack_into("<HI", h, 94, 375, 375)
+    struct.pack_into("<I", h, 107, 0)   # legacy count 0: the 64-bit count holds n
+    struct.pack_into("<I", h, 111, 0)
+    struct.pack_into("<Q", h, 247, n)
+    last = h + bytearray(59 * n)
+    for i, (x, y, z, c, _) in enumerate(pts):
+        struct.pack_into("<iii", last, 375 + 12 * i, x, y, z)
+        last[375 + 15 * n + i] = 0xEE   # classification flags: a byte that is not the class
+        last[375 + 16 * n + i] = c
+        struct.pack_into("<d", last, 375 + 22 * n + 8 * i, TIMES[i])
+    return bytes(las), bytes(last), pts, pts_world
+
+
+def time_section():
+    las, last, pts, pts_world = time_files()
+    open(os.path.join(HERE, "tiny_fmt4.las"), "wb").write(las)
+    open(os.path.join(HERE, "tiny_fmt9.last"), "wb").write(last)
+
+    def recs(idx, with_class):  # a time record: position, class 0, colour (0, 0, 0) (las.rs:345-355); formats 4, 9: no colour
+        return [[pts_world[i][0].hex(), pts_world[i][1].hex(), pts_world[i][2].hex(), 0, 0, 0, pts[i][3] if with_class else 0]
+                for i in idx]
+
+    res = {"times": [hexf(t) for t in TIMES], "time": [], "bounds_time": [], "bounds_class": []}
+    for start, end in TIME_RANGES:  # Range::contains: start <= t && t < end
+        idx = [i for i, t in enumerate(TIMES) if start <= t and t < end]
+        res["time"].append({"start": hexf(start), "end": hexf(end), "indices": idx, "records": recs(idx, False)})
+    bmin, bmax = (100.0, 200.0, -10.0), (110.0, 210.0, 0.0)  # box_exact: local (0, 0, 0) .. (1000, 500, 200)
+    lmin, lmax, _ = box_to_local(bmin, bmax, SCALE, OFFSET)
+    inside = [i for i, p in enumerate(pts) if all(lmin[a] <= p[a] <= lmax[a] for a in range(3))]
+    for start, end in TIME_RANGES[:3]:
+        idx = [i for i in inside if start <= TIMES[i] and TIMES[i] < end]
+        res["bounds_time"].append({"bmin": list(bmin), "bmax": list(bmax), "start": hexf(start), "end": hexf(end), "indices": idx,
+                                   "records": recs(idx, False)})
+    for c in (6, 2, 134, 0xEE):
+        idx = [i for i in inside if pts[i][3] == c]  # the whole byte (las.rs:229-231, last.rs:259-262)
+        res["bounds_class"].append({"bmin": list(bmin), "bmax": list(bmax), "class": c, "indices": idx, "records": recs(idx, True)})
+    return res
+
+
 def main():
     out = {}
     # ---- casts --------------------------------------------------------------------------------------
@@ -273,6 +337,7 @@ def main():
     out["grid"]["too_many_cells"] = {"bmin": [0.0] * 3, "bmax": [1e9] * 3, "cell": 1e-4, "bits": g_big.bits, "too_many": g_big.too_many}
 
     lazer_section(out, last, pts_world)
+    out["time"] = time_section()
     json.dump(out, open(os.path.join(HERE, "expected.json"), "w"), indent=1)
     print("wrote expected.json, tiny_fmt2.last (%d B), tiny_fmt3.las (%d B)" % (len(last), len(las)))
 

@@ -1,0 +1,479 @@
+"""The oracle's GPS time search and combined searches pinned against numpy, and the `query` CLI against the
+oracle's CLI on every argument and file case that a host resolves without a GPU.
+
+The oracle restates las.rs:297-358 (time), DESIGN.md §8 (the LAST time form, the combined searches and the CLI flags); the
+numpy side restates the same from the record layout alone: sel = (start <= t) & (t < end) on float64 (NaN -> False); the
+box is the oracle's pinned box_to_local (tests/golden) compared inclusively in i64, behind the header early-out; a time
+record is the position with class 0 and colour (0, 0, 0), a class record carries its class byte and, for formats 2, 3 and
+5 only (las.rs:38-45), its colour.
+"""
+import ctypes as C
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _oracle  # noqa: E402
+import _time_images as ti  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+QUERY = os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "host", "query")
+QUERY_ORACLE = os.path.join(ROOT, "oracle", "query_oracle")
+POINT_DTYPE = _oracle.POINT_DTYPE
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+COLOR_READ = {2: 20, 3: 28, 5: 28}  # the colour offsets the optimized searches know (las.rs:38-45, last.rs:83-88)
+ALL_FORMATS = sorted(ti.FORMATS)
+
+
+def image(layout, fmt, xyz, cls, rgb, t, **kw):
+    return ti.las_image(fmt, xyz, cls, rgb, t, **kw) if layout == "las" else ti.last_image(fmt, xyz, cls, rgb, t, **kw)
+
+
+def want_records(xyz, cls, rgb, sel, fmt=None):
+    """Records in file order; fmt None: a time record (class 0, no colour), else the class search's record of that format."""
+    out = ti.expect_records(xyz, sel, POINT_DTYPE)
+    if fmt is not None:
+        out["classification"] = cls[sel]
+        if fmt in COLOR_READ:
+            out["r"], out["g"], out["b"] = rgb[sel, 0], rgb[sel, 1], rgb[sel, 2]
+    return out
+
+
+def run(oracle, search, *args, **kw):
+    """(status, count, records) of one oracle search into a count and a buffer collector."""
+    oc, ob = oracle.count_collector(), oracle.buffer_collector()
+    try:
+        rc = search(*args, oc, **kw)
+        assert search(*args, ob, **kw) == rc
+        return rc, oc.point_count(), ob.points()
+    finally:
+        oc.free(), ob.free()
+
+
+def box_select(oracle, xyz, bmin, bmax, scale=ti.SCALE, offset=ti.OFFSET):
+    lmin, lmax = oracle.box_to_local(bmin, bmax, scale, offset)
+    x = xyz.astype(np.int64)
+    return np.all((x >= np.array(lmin)) & (x <= np.array(lmax)), axis=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# time search
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["las", "last"])
+@pytest.mark.parametrize("fmt", ALL_FORMATS)
+def test_time_search_of_every_format_against_numpy(oracle, layout, fmt):
+    n = 1_500
+    xyz, cls, rgb, _ = ti.points(n, 40 + fmt)
+    for k, (start, end) in enumerate(ti.RANGES):
+        t = ti.adversarial_times(n, start, end, 100 * fmt + k)
+        img = image(layout, fmt, xyz, cls, rgb, t)
+        rc, cnt, pts = run(oracle, oracle.search_time, img, layout, start, end, path="d/f")
+        if fmt in (0, 2):  # las.rs:306-318
+            assert (rc, oracle.err()) == (_oracle.ERR_FORMAT, "File d/f does not contain GPS times!")
+            continue
+        sel = ti.select(t, start, end)
+        assert rc == 0, oracle.err()
+        assert cnt == int(sel.sum()), (fmt, start, end)
+        assert pts.tobytes() == want_records(xyz, cls, rgb, sel).tobytes(), (fmt, start, end)
+
+
+@pytest.mark.parametrize("layout", ["las", "last"])
+def test_time_offsets_by_raw_format(oracle, layout):
+    """The time is read at +20 for formats 1 and 3-5 and at +22 for 6-10: a file whose only real times sit at the other
+    offset finds nothing there."""
+    n = 300
+    xyz, cls, rgb, t = ti.points(n, 5)
+    for fmt in ALL_FORMATS:
+        if fmt in (0, 2):
+            continue
+        img = image(layout, fmt, xyz, cls, rgb, t)
+        rc, cnt, _ = run(oracle, oracle.search_time, img, layout, 1000.0, 2000.0)
+        assert (rc, cnt) == (0, n), fmt
+        toff = ti.time_offset(fmt)
+        assert toff == (20 if fmt <= 5 else 22)
+        if layout == "las":  # move every time by two bytes: the search must no longer see them
+            rl = ti.FORMATS[fmt][0]
+            body = img[len(img) - n * rl:].reshape(n, rl)
+            moved = body[:, toff:toff + 8].copy()
+            body[:, toff:toff + 8] = 0
+            other = 22 if toff == 20 else 20
+            if other + 8 > rl:
+                continue
+            body[:, other:other + 8] = moved
+            rc, cnt, _ = run(oracle, oracle.search_time, img, layout, 1000.0, 2000.0)
+            assert (rc, cnt) == (0, 0), fmt
+
+
+@pytest.mark.parametrize("fmt_byte", [11, 14, 255])
+@pytest.mark.parametrize("layout", ["las", "last"])
+def test_time_formats_above_10(oracle, layout, fmt_byte):
+    """the match arm's message (las.rs:324-329), not the header parser's."""
+    xyz, cls, rgb, t = ti.points(20, 1)
+    img = image(layout, 1, xyz, cls, rgb, t, fmt_byte=fmt_byte)
+    rc, _, _ = run(oracle, oracle.search_time, img, layout, 0.0, 1.0, path="x/y")
+    assert (rc, oracle.err()) == (_oracle.ERR_FORMAT, f"Invalid LAS format {fmt_byte} in file x/y")
+
+
+@pytest.mark.parametrize("fmt", [1, 3, 4, 5])
+@pytest.mark.parametrize("layout", ["las", "last"])
+def test_time_with_v14_header_and_legacy_count_0(oracle, layout, fmt):
+    n = 777
+    xyz, cls, rgb, t = ti.points(n, fmt)
+    ref = run(oracle, oracle.search_time, image(layout, fmt, xyz, cls, rgb, t), layout, 1300.0, 1700.0)
+    for legacy in (True, False):
+        img = image(layout, fmt, xyz, cls, rgb, t, v14=True, legacy=legacy)
+        got = run(oracle, oracle.search_time, img, layout, 1300.0, 1700.0)
+        assert got[0] == ref[0] == 0 and got[1] == ref[1] > 0 and got[2].tobytes() == ref[2].tobytes(), legacy
+
+
+@pytest.mark.parametrize("fmt", [1, 5, 6, 10])
+def test_time_truncated_files(oracle, fmt):
+    """LAS: the search fails exactly when a byte of the last record's time is missing (its colour may be gone);
+    LAST: both the positions block and the time block must be whole, whatever matches."""
+    n = 50
+    xyz, cls, rgb, t = ti.points(n, fmt)
+    rl, toff, _, _ = ti.FORMATS[fmt]
+    las = ti.las_image(fmt, xyz, cls, rgb, t)
+    tail = rl - (toff + 8)  # bytes behind the last record's time
+    for cut, ok in ((tail, True), (tail + 1, False), (rl, False)):
+        if cut == 0:
+            continue
+        for start, end in ((1000.0, 2000.0), (5.0, 6.0)):  # every point matches / none does
+            rc = run(oracle, oracle.search_time, las[:len(las) - cut], "las", start, end)[0]
+            assert rc == (0 if ok else _oracle.ERR_EOF), (cut, start)
+    last = ti.last_image(fmt, xyz, cls, rgb, t)
+    otp = len(last) - n * rl
+    tend = otp + n * (toff + 8)
+    assert run(oracle, oracle.search_time, last[:tend], "last", 5.0, 6.0)[0] == 0
+    assert run(oracle, oracle.search_time, last[:tend - 1], "last", 5.0, 6.0)[0] == _oracle.ERR_EOF
+    # the positions block cut short is found though no point matches (the time block is gone too, a fortiori)
+    assert run(oracle, oracle.search_time, last[:otp + 12 * n - 1], "last", 5.0, 6.0)[0] == _oracle.ERR_EOF
+    empty = ti.last_image(fmt, xyz[:0], cls[:0], rgb[:0], t[:0])
+    assert run(oracle, oracle.search_time, empty, "last", -np.inf, np.inf)[:2] == (0, 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# combined searches
+# ---------------------------------------------------------------------------------------------------------------------
+BOXES = [((60.0, -250.0, -20.0), (140.0, -150.0, 40.0)),      # part of the data
+         ((-1e9, -1e9, -1e9), (1e9, 1e9, 1e9)),               # everything
+         ((50.0, -300.0, -50.0), (50.0, -300.0, -50.0)),      # a point-sized box
+         ((120.0, -190.0, 0.0), (121.0, -180.0, 30.0))]        # anisotropic scales: the x-scale typo on the min corner
+
+
+@pytest.mark.parametrize("layout", ["las", "last"])
+@pytest.mark.parametrize("fmt", ALL_FORMATS)
+def test_bounds_and_class_of_every_format_against_numpy(oracle, layout, fmt):
+    n = 2_000
+    xyz, cls, rgb, t = ti.points(n, 60 + fmt)
+    img = image(layout, fmt, xyz, cls, rgb, t)
+    for bmin, bmax in BOXES:
+        inside = box_select(oracle, xyz, bmin, bmax)
+        for c in (1, 2, 6, 7):
+            rc, cnt, pts = run(oracle, oracle.search_bounds_class, img, layout, bmin, bmax, c)
+            sel = inside & (cls == c)
+            assert rc == 0, oracle.err()
+            assert cnt == int(sel.sum()), (fmt, bmin, c)
+            assert pts.tobytes() == want_records(xyz, cls, rgb, sel, fmt).tobytes(), (fmt, bmin, c)
+
+
+@pytest.mark.parametrize("layout", ["las", "last"])
+@pytest.mark.parametrize("fmt", ALL_FORMATS)
+def test_bounds_and_time_of_every_format_against_numpy(oracle, layout, fmt):
+    n = 1_500
+    xyz, cls, rgb, _ = ti.points(n, 80 + fmt)
+    for k, (start, end) in enumerate(ti.RANGES):
+        t = ti.adversarial_times(n, start, end, 300 + 10 * fmt + k)
+        img = image(layout, fmt, xyz, cls, rgb, t)
+        for bmin, bmax in BOXES[:2] + BOXES[3:]:
+            rc, cnt, pts = run(oracle, oracle.search_bounds_time, img, layout, bmin, bmax, start, end, path="f")
+            if fmt in (0, 2):
+                assert (rc, oracle.err()) == (_oracle.ERR_FORMAT, "File f does not contain GPS times!")
+                continue
+            sel = box_select(oracle, xyz, bmin, bmax) & ti.select(t, start, end)
+            assert rc == 0, oracle.err()
+            assert cnt == int(sel.sum()), (fmt, start, end, bmin)
+            assert pts.tobytes() == want_records(xyz, cls, rgb, sel).tobytes(), (fmt, start, end, bmin)
+
+
+def test_combined_plan_order(oracle):
+    """§8's order: the attribute prologue (format and EOF errors), then the header early-out, then the box (panic)."""
+    n = 100
+    xyz, cls, rgb, t = ti.points(n, 3)
+    far = ((1e6, 1e6, 1e6), (2e6, 2e6, 2e6))
+    inverted_far = ((2e6, 2e6, 2e6), (1e6, 1e6, 1e6))
+    typo = ((100.0, -140.0, 0.0), (110.0, -130.0, 10.0))  # lmin.y = 60 / 0.01 = 6000 > lmax.y = 70 / 0.02 = 3500: panic
+    for layout in ("las", "last"):
+        good = image(layout, 3, xyz, cls, rgb, t)
+        short = good[:-8 * n]  # (LAST: the colour block and part of the time block)
+        for search, extra in ((oracle.search_bounds_class, (2,)), (oracle.search_bounds_time, (0.0, 1.0))):
+            assert run(oracle, search, good, layout, *far, *extra)[:2] == (0, 0)
+            assert run(oracle, search, good, layout, *inverted_far, *extra)[:2] == (0, 0)  # disjoint: no panic
+            assert run(oracle, search, good, layout, *typo, *extra)[0] == _oracle.ERR_PANIC
+            assert run(oracle, search, short, layout, *far, *extra)[0] == _oracle.ERR_EOF   # EOF before the early-out
+        no_time = image(layout, 2, xyz, cls, rgb, t)
+        assert run(oracle, oracle.search_bounds_time, no_time, layout, *far, 0.0, 1.0)[0] == _oracle.ERR_FORMAT
+        assert run(oracle, oracle.search_bounds_class, no_time, layout, *far, 2)[:2] == (0, 0)
+        empty = image(layout, 3, xyz[:0], cls[:0], rgb[:0], t[:0])
+        # no points: the box is still converted (the header's bounds of an empty file are (0, 0, 0)); the x-scale typo
+        # makes lmin.y = 199 / 0.01 > lmax.y = 199 / 0.02
+        unit = ((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))
+        assert run(oracle, oracle.search_bounds_class, empty, layout, *unit, 2)[0] == _oracle.ERR_PANIC
+        assert run(oracle, oracle.search_bounds_time, empty, layout, *unit, 0.0, 1.0)[0] == _oracle.ERR_PANIC
+        assert run(oracle, oracle.search_bounds_time, empty, layout, *far, 0.0, 1.0)[:2] == (0, 0)
+
+
+def test_combined_class_reads_the_class_search_byte(oracle):
+    """LAS formats 6-10: BOUNDS_CLASS takes the class byte at +16 (the bounds-only LAS path reads +15); LAST formats
+    are masked to their low nibble as the class search does (last.rs:222), LAS formats are not."""
+    n = 400
+    xyz, cls, rgb, t = ti.points(n, 8)
+    img = ti.las_image(6, xyz, cls, rgb, t)
+    rl = ti.FORMATS[6][0]
+    img[len(img) - n * rl:].reshape(n, rl)[:, 15] = 99
+    everything = BOXES[1]
+    rc, cnt, _ = run(oracle, oracle.search_bounds_class, img, "las", *everything, 2)
+    assert (rc, cnt) == (0, int((cls == 2).sum()))
+    assert run(oracle, oracle.search_bounds_class, img, "las", *everything, 99)[:2] == (0, 0)
+    masked = ti.last_image(3, xyz, cls, rgb, t, fmt_byte=0x43)
+    rc, cnt, pts = run(oracle, oracle.search_bounds_class, masked, "last", *everything, 6)
+    assert (rc, cnt) == (0, int((cls == 6).sum())) and pts["r"].any()
+    unmasked = ti.las_image(3, xyz, cls, rgb, t, fmt_byte=0x43)
+    assert run(oracle, oracle.search_bounds_class, unmasked, "las", *everything, 6)[0] == _oracle.ERR_HEADER
+
+
+@pytest.mark.parametrize("fmt", [3, 5, 7, 10])
+def test_combined_truncated_files(oracle, fmt):
+    """The attribute search's EOF checks: every block it may read, positions and (class search) colour included."""
+    n = 40
+    xyz, cls, rgb, t = ti.points(n, fmt)
+    rl, toff, _, kof = ti.FORMATS[fmt]
+    coff = COLOR_READ.get(fmt)
+    las = ti.las_image(fmt, xyz, cls, rgb, t)
+    need_c = max(12, kof + 1, coff + 6 if coff else 0)
+    need_t = toff + 8
+    for search, extra, need in ((oracle.search_bounds_class, (2,), need_c), (oracle.search_bounds_time, (5.0, 6.0), need_t)):
+        behind = rl - need
+        if behind:
+            assert run(oracle, search, las[:len(las) - behind], "las", *BOXES[0], *extra)[0] == 0
+        assert run(oracle, search, las[:len(las) - behind - 1], "las", *BOXES[0], *extra)[0] == _oracle.ERR_EOF
+    last = ti.last_image(fmt, xyz, cls, rgb, t)
+    otp = len(last) - n * rl
+    ends_c = [otp + 12 * n, otp + n * (kof + 1)] + ([otp + n * (coff + 6)] if coff else [])
+    for e in ends_c:
+        assert run(oracle, oracle.search_bounds_class, last[:e - 1], "last", *BOXES[0], 2)[0] == _oracle.ERR_EOF
+    assert run(oracle, oracle.search_bounds_class, last[:max(ends_c)], "last", *BOXES[0], 2)[0] == 0
+    for e in (otp + 12 * n, otp + n * (toff + 8)):
+        assert run(oracle, oracle.search_bounds_time, last[:e - 1], "last", *BOXES[0], 5.0, 6.0)[0] == _oracle.ERR_EOF
+    assert run(oracle, oracle.search_bounds_time, last[:otp + n * (toff + 8)], "last", *BOXES[0], 5.0, 6.0)[0] == 0
+
+
+def test_search_file_dispatches_the_new_kinds(oracle, tmp_path):
+    n = 500
+    xyz, cls, rgb, t = ti.points(n, 1)
+    for layout in ("las", "last"):
+        p = str(tmp_path / f"f.{layout}")
+        image(layout, 3, xyz, cls, rgb, t).tofile(p)
+        oc = oracle.count_collector()
+        assert oracle.search_file_range(p, _oracle.QUERY_TIME, None, None, 0, 1200.0, 1300.0, oc) == 0
+        assert oc.point_count() == int(ti.select(t, 1200.0, 1300.0).sum())
+        oc.free()
+        oc = oracle.count_collector()
+        assert oracle.search_file_range(p, _oracle.QUERY_BOUNDS_CLASS, *BOXES[0], 2, 0.0, 0.0, oc) == 0
+        assert oc.point_count() == int((box_select(oracle, xyz, *BOXES[0]) & (cls == 2)).sum())
+        oc.free()
+        oc = oracle.count_collector()
+        assert oracle.search_file_range(p, _oracle.QUERY_BOUNDS_TIME, *BOXES[0], 0, 1200.0, 1700.0, oc) == 0
+        assert oc.point_count() == int((box_select(oracle, xyz, *BOXES[0]) & ti.select(t, 1200.0, 1700.0)).sum())
+        oc.free()
+    p = str(tmp_path / "f.lazer")
+    open(p, "wb").write(b"\0" * 64)
+    for kind in (_oracle.QUERY_TIME, _oracle.QUERY_BOUNDS_CLASS, _oracle.QUERY_BOUNDS_TIME):
+        oc = oracle.count_collector()
+        assert oracle.search_file_range(p, kind, *BOXES[0], 2, 0.0, 1.0, oc) == _oracle.ERR_UNSUPPORTED
+        oc.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the product's plans read the times the oracle reads (no GPU: the host prologue only)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def qlib():
+    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
+    cp, pp, ip, dp = C.POINTER(binding.Columns), C.POINTER(binding.Predicate), C.POINTER(C.c_int), C.POINTER(C.c_double)
+    lib.pcq_query_test_plan_time.argtypes = [C.c_char_p, C.c_double, C.c_double, cp, pp, ip]
+    lib.pcq_query_test_plan_combined.argtypes = [C.c_char_p, dp, dp, C.c_int, C.c_double, C.c_double, cp, pp, ip]
+    lib.pcq_query_last_error.restype = C.c_char_p
+    return lib
+
+
+def _column(img, cols, n, width):
+    """The n values of a plan's attribute column, read through its offset and stride."""
+    idx = cols.cls + cols.cls_stride * np.arange(n)[:, None] + np.arange(width)[None, :]
+    return img[idx].copy()
+
+
+@pytest.mark.parametrize("layout", ["las", "last"])
+@pytest.mark.parametrize("fmt", [f for f in ALL_FORMATS if f not in (0, 2)])
+def test_plans_of_every_format_read_the_files_times(qlib, tmp_path, layout, fmt):
+    """The time search's and the combined time search's plans point at the times of every format (+20 for 1 and 3-5,
+    +22 for 6-10), and the combined class search's at the class byte the oracle compares."""
+    n = 301
+    xyz, cls, rgb, t = ti.points(n, 90 + fmt)
+    img = image(layout, fmt, xyz, cls, rgb, t)
+    p = tmp_path / f"f.{layout}"
+    img.tofile(p)
+    d3 = C.c_double * 3
+    for combined in (False, True):
+        cols, pred, needs = binding.Columns(), binding.Predicate(), C.c_int(-1)
+        if combined:
+            rc = qlib.pcq_query_test_plan_combined(str(p).encode(), d3(-1e9, -1e9, -1e9), d3(1e9, 1e9, 1e9), -1, 0.0, 1.0,
+                                                   C.byref(cols), C.byref(pred), C.byref(needs))
+        else:
+            rc = qlib.pcq_query_test_plan_time(str(p).encode(), 0.0, 1.0, C.byref(cols), C.byref(pred), C.byref(needs))
+        assert (rc, needs.value) == (0, 1), qlib.pcq_query_last_error()
+        assert np.array_equal(_column(img, cols, n, 8).view("<f8").ravel(), t), (fmt, combined)
+    cols, pred, needs = binding.Columns(), binding.Predicate(), C.c_int(-1)
+    rc = qlib.pcq_query_test_plan_combined(str(p).encode(), d3(-1e9, -1e9, -1e9), d3(1e9, 1e9, 1e9), 2, 0.0, 0.0, C.byref(cols),
+                                           C.byref(pred), C.byref(needs))
+    assert (rc, needs.value) == (0, 1), qlib.pcq_query_last_error()
+    assert np.array_equal(_column(img, cols, n, 1).ravel(), cls), fmt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CLI parity without a GPU
+# ---------------------------------------------------------------------------------------------------------------------
+def _both(args, env=None):
+    out = []
+    for exe in (QUERY, QUERY_ORACLE):
+        r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120, env=env)
+        stdout = "\n".join(line for line in r.stdout.splitlines() if not line.startswith("Searched "))
+        out.append((r.returncode, stdout, r.stderr))
+    return out
+
+
+@pytest.fixture(scope="module")
+def cli_dirs(tmp_path_factory):
+    root = tmp_path_factory.mktemp("cli")
+    xyz, cls, rgb, t = ti.points(300, 17)
+    dirs = {"empty": root / "empty", "out": root / "out"}
+    for k in dirs.values():
+        k.mkdir()
+    for name, layout, fmt, fb in (("fmt0", "las", 0, None), ("fmt2", "last", 2, None), ("fmt14", "las", 1, 14),
+                                  ("fmt14t", "last", 1, 14)):
+        d = root / name
+        d.mkdir()
+        image(layout, fmt, xyz, cls, rgb, t, fmt_byte=fb).tofile(d / f"f.{layout}")
+        dirs[name] = d
+    d = root / "mixed"  # every format with times, LAS and LAST
+    d.mkdir()
+    for fmt in (1, 3, 4, 5, 6, 7, 8, 9, 10):
+        for layout in ("las", "last"):
+            image(layout, fmt, xyz, cls, rgb, t).tofile(d / f"f{fmt}.{layout}")
+    dirs["mixed"] = d
+    return {k: str(v) for k, v in dirs.items()}
+
+
+FAR = ["--bounds", "1e6;1e6;1e6;2e6;2e6;2e6"]
+ARG_CASES = [
+    ["--time", "abc"], ["--time", "1;2;3"], ["--time", "1;"], ["--time", " 1;2"], ["--time", "0x1;2"],
+    ["--combine", "--bounds", "0;0;0;1;1;1", "--time", "zz"],
+    ["--class", "2", "--time", "zz"], ["--class", "300", "--time", "0;1"], ["--time", "0;1", "--density", "q"],
+    ["--bounds", "0;0;0;1;1;1", "--time", "0;1"], ["--class", "2", "--time", "0;1"],
+    ["--bounds", "0;0;0;1;1;1", "--class", "2", "--time", "0;1"], ["--bounds", "0;0;0;1;1;1", "--class", "2"],
+    ["--combine", "--class", "2", "--time", "0;1"], ["--combine", "--bounds", "0;0;0;1;1;1", "--class", "2", "--time", "0;1"],
+    ["--combine", "--bounds", "1;0;0;0;1;1", "--class", "2"],  # min > max: the panic of parse_aabb
+    ["--combine"], [], ["--density", "1"], ["--combine", "--density", "1"],
+]
+
+
+@pytest.mark.parametrize("args", ARG_CASES, ids=[" ".join(a) or "none" for a in ARG_CASES])
+@pytest.mark.parametrize("parallel", [False, True])
+def test_cli_argument_errors_match_the_oracle_cli(cli_dirs, args, parallel):
+    a = ["-i", cli_dirs["empty"], "--optimized"] + args + (["--parallel"] if parallel else [])
+    got, want = _both(a)
+    assert got == want
+
+
+EMPTY_CASES = [["--time", "1;2"], ["--time", "-inf;inf"], ["--time", "NaN;1"], ["--time", "2;1"],
+               ["--combine", "--bounds", "0;0;0;1;1;1", "--class", "2"], ["--combine", "--bounds", "0;0;0;1;1;1", "--time", "0;1"],
+               ["--combine", "--class", "2"], ["--combine", "--time", "0;1"]]
+
+
+@pytest.mark.parametrize("args", EMPTY_CASES, ids=[" ".join(a) for a in EMPTY_CASES])
+@pytest.mark.parametrize("extra", [[], ["-o", "OUT"]], ids=["count", "output"])
+def test_cli_empty_directory_matches_the_oracle_cli(cli_dirs, args, extra):
+    extra = [cli_dirs["out"] if e == "OUT" else e for e in extra]
+    got, want = _both(["-i", cli_dirs["empty"], "--optimized", "--parallel"] + args + extra)
+    assert got == want
+
+
+FILE_CASES = [
+    ("fmt0", ["--time", "0;1"]), ("fmt2", ["--time", "0;1"]), ("fmt14", ["--time", "0;1"]), ("fmt14t", ["--time", "0;1"]),
+    ("fmt0", ["--combine"] + FAR + ["--time", "0;1"]), ("fmt2", ["--combine"] + FAR + ["--time", "0;1"]),
+    ("fmt14", ["--combine"] + FAR + ["--time", "0;1"]), ("fmt14", ["--combine"] + FAR + ["--class", "2"]),
+    ("fmt14t", ["--combine"] + FAR + ["--class", "2"]), ("fmt0", ["--combine"] + FAR + ["--class", "2"]),
+    ("fmt2", ["--combine"] + FAR + ["--class", "2"]),
+    ("mixed", ["--combine"] + FAR + ["--class", "2"]), ("mixed", ["--combine"] + FAR + ["--time", "-inf;inf"]),
+    ("mixed", ["--combine", "--bounds", "2e6;2e6;2e6;1e6;1e6;1e6", "--class", "2"]),
+    ("mixed", ["--combine"] + FAR + ["--class", "2", "--density", "5"]),
+    ("mixed", ["--combine"] + FAR + ["--time", "0;1", "-o", "OUT"]),
+]
+
+
+@pytest.mark.parametrize("case", FILE_CASES, ids=[c[0] + " " + " ".join(c[1]) for c in FILE_CASES])
+def test_cli_files_resolved_on_the_host_match_the_oracle_cli(cli_dirs, case):
+    """Format errors and boxes disjoint from every header are resolved by the parallel driver's planning pass, before a
+    device is opened."""
+    name, args = case
+    args = [cli_dirs["out"] if a == "OUT" else a for a in args]
+    got, want = _both(["-i", cli_dirs[name], "--optimized", "--parallel"] + args)
+    assert got == want
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# hand-derived known answers (tests/golden/make_golden.py: a format-4 LAS and a format-9 LAST with NaN and +-0.0 times)
+# ---------------------------------------------------------------------------------------------------------------------
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def golden_time():
+    import json
+    g = json.load(open(os.path.join(GOLDEN, "expected.json")))["time"]
+    files = {"las": np.fromfile(os.path.join(GOLDEN, "tiny_fmt4.las"), dtype=np.uint8),
+             "last": np.fromfile(os.path.join(GOLDEN, "tiny_fmt9.last"), dtype=np.uint8)}
+    return g, files
+
+
+def f_of(h):
+    return float("nan") if h == "nan" else float.fromhex(h)
+
+
+def golden_records(recs):
+    out = np.zeros(len(recs), dtype=POINT_DTYPE)
+    for i, (x, y, z, r, g, b, c) in enumerate(recs):
+        out[i] = (float.fromhex(x), float.fromhex(y), float.fromhex(z), r, g, b, c)
+    return out
+
+
+@pytest.mark.parametrize("layout", ["las", "last"])
+def test_time_and_combined_known_answers(oracle, layout):
+    g, files = golden_time()
+    img = files[layout]
+    for case in g["time"]:
+        rc, cnt, pts = run(oracle, oracle.search_time, img, layout, f_of(case["start"]), f_of(case["end"]))
+        assert (rc, cnt) == (0, len(case["indices"])), case
+        assert pts.tobytes() == golden_records(case["records"]).tobytes(), case
+    for case in g["bounds_time"]:
+        rc, cnt, pts = run(oracle, oracle.search_bounds_time, img, layout, case["bmin"], case["bmax"], f_of(case["start"]),
+                           f_of(case["end"]))
+        assert (rc, cnt) == (0, len(case["indices"])), case
+        assert pts.tobytes() == golden_records(case["records"]).tobytes(), case
+    for case in g["bounds_class"]:
+        rc, cnt, pts = run(oracle, oracle.search_bounds_class, img, layout, case["bmin"], case["bmax"], case["class"])
+        assert (rc, cnt) == (0, len(case["indices"])), case
+        assert pts.tobytes() == golden_records(case["records"]).tobytes(), case
