@@ -422,7 +422,9 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: null argument");
     if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count and buffer collectors only");
-    if (pred->kind == PCQ_PRED_TIME || pred_is_combined(pred->kind)) {  // no index of these: the plain scan, statistics that claim nothing
+    // no index of these kinds (nor of a world-space box, nor of a kind that does not exist: pcq_scan_dev validates): the plain
+    // scan, statistics that claim nothing
+    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS) {
         ix->last = pcq_index_stats{};
         ix->stats_stream = nullptr;
         ix->stats_kind = 0;

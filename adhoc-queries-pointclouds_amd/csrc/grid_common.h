@@ -383,7 +383,7 @@ struct EntryRef {
     const GridEntryDev *table;
     const uint8_t *tile_entry;  // [T]
     uint32_t multi;             // more than one entry in this fold
-    uint32_t _pad;
+    uint32_t tile_last;         // T - 1: see entry_of
     GridEntryDev e0;
     // (written field by field with explicit global loads: as `id == 0 ? e0 : table[id]` the compiler selects between the
     // two ADDRESSES — kernel argument segment or table — and loads six doubles through flat instructions for every tuple)
@@ -404,7 +404,12 @@ struct EntryRef {
     template <bool MULTI = true>
     __device__ __forceinline__ uint32_t entry_of(uint32_t idx) const {
         if (!MULTI) return 0u;
-        return multi ? (uint32_t)ldg(tile_entry + idx / (uint32_t)P0_TILE) : 0u;
+        if (!multi) return 0u;
+        // The tile is clamped: the folds load a tuple for every lane, and the lanes beyond the partition's last tuple repeat
+        // that one — but an EMPTY partition has none, and what they load then is whatever lies at its place (a region of the
+        // second level nobody wrote, the spare bytes behind the last tuple).  Its idx is anything; nothing else of it is used.
+        const uint32_t tile = idx / (uint32_t)P0_TILE;
+        return (uint32_t)ldg(tile_entry + (tile < tile_last ? tile : tile_last));
     }
     // how entry `id` packs its 16-byte tuples
     template <bool MULTI = true>

@@ -300,6 +300,7 @@ static int grid_fold(pcq_ctx *ctx, pcq_collector *c) {
     eref.table = d_entries;
     eref.tile_entry = d_tile_entry;
     eref.multi = gs->entries.size() > 1 ? 1u : 0u;
+    eref.tile_last = T - 1;
     eref.e0 = gs->entries[0];
     hipLaunchKernelGGL(k_dir_transpose, dim3((T + 63) / 64), dim3(BLOCK), 0, s, d_runs, nruns, T, Tp, Tp1, d_startT, d_preT, d_tile_addr, d_tile_entry);
     hipLaunchKernelGGL(k_bin_prefix, dim3(F1), dim3(1024), 0, s, d_preT, T, Tp1, d_bintot);

@@ -682,9 +682,16 @@ extern "C" int pcq_collector_reset(pcq_collector *c) {
     c->next_index = 0;
     // scans enqueued on a caller's stream may still be reading and moving the counters
     if (c->kind != COLL_GRID && c->last_stream && c->last_stream != s) PCQ_HIP(hipStreamSynchronize(c->last_stream));
-    if (c->kind == COLL_COUNT) PCQ_HIP(hipMemsetAsync(c->d_count, 0, 8, s));
+    // The counters are zeroed on the context's stream and the stream is drained: the next scan may arrive on a caller's
+    // stream that the context's scratch was last used on (pcq_scratch_stream then waits for nothing), and nothing else
+    // would order the zeroing in front of that scan's read of the counter.
+    if (c->kind == COLL_COUNT) {
+        PCQ_HIP(hipMemsetAsync(c->d_count, 0, 8, s));
+        PCQ_HIP(hipStreamSynchronize(s));
+    }
     if (c->kind == COLL_BUFFER) {
         PCQ_HIP(hipMemsetAsync(c->d_count, 0, 16, s));
+        PCQ_HIP(hipStreamSynchronize(s));
         c->n_upper = 0;
         c->count_slot = 0;
     }

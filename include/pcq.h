@@ -191,7 +191,8 @@ int pcq_collector_points(pcq_collector *c, pcq_point *out, uint64_t cap, uint64_
 int pcq_collector_grid_cells(pcq_collector *c, uint64_t *out, uint64_t cap, uint64_t *out_n);
 /* SparseGrid::new results (grid_sampling.rs:24-44). */
 int pcq_collector_grid_params(const pcq_collector *c, uint64_t dims[3], uint64_t bits[3]);
-/* Resets the collector to its freshly constructed state (keeps allocations). */
+/* Resets the collector to its freshly constructed state (keeps allocations).  Waits for the collector's scans, and for
+ * the zeroing of its counters: the next scan may be enqueued on any stream. */
 int pcq_collector_reset(pcq_collector *c);
 /* Brings a collector that is kept for later into its compact form NOW and waits for it: a grid collector folds its
  * pending matches into per-cell winners (the reference's HashMap never holds more than the winners,
@@ -255,8 +256,8 @@ int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_pr
  * records), and the ragged tail behind the last whole bounds chunk is always read.  Results are
  * identical to pcq_scan_dev; layouts the index does not cover fall through to it: strided / LAS
  * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME,
- * PCQ_PRED_BOUNDS_CLASS and PCQ_PRED_BOUNDS_TIME have no index: they are served by pcq_scan_dev, the statistics of such a
- * scan are all zero, and the index is neither built nor changed by it.
+ * PCQ_PRED_BOUNDS_CLASS, PCQ_PRED_BOUNDS_TIME and PCQ_PRED_BOUNDS_F64 have no index: they are served by pcq_scan_dev, the
+ * statistics of such a scan are all zero, and the index is neither built nor changed by it.
  * Statistics of the last scan, in index chunks: for a count scan what it read; for a buffer scan the
  * chunks its count pass skipped (disjoint), took whole (contained) and read (straddling); after a
  * build, every chunk was read.  They are collected on the device and fetched (one wait) when asked.
