@@ -345,76 +345,43 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     return PCQ_OK;
 }
 
-// A buffer collector: the emit's count pass takes each tile's state from the index (scan_generic.hip, k_tile_counts with IDX),
-// then the records are written as by pcq_scan_dev.  The first scan of a block builds the index first.
-static int scan_buffer_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix, pcq_collector *c, void *stream) {
-    int rc = pcq_validate_scan(cols, pred, c);
-    if (rc) return rc;
-    const bool bounds = pred->kind == PCQ_PRED_BOUNDS;
-    const bool covered = bounds ? cols->xyz_stride == 12 && ((uintptr_t)cols->xyz & 15) == 0 && cols->n >= CHUNK_POINTS
-                                : pred->kind == PCQ_PRED_CLASS && cols->cls && cols->cls_stride == 1 && cols->n > 0;
-    if (!covered) return pcq_scan_dev(ctx, cols, pred, c, stream);  // layout the index does not cover: plain scan
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    DevPred dp;
-    rc = pcq_make_dev_pred(pred, &dp);
-    if (rc) return rc;
-    rc = pcq_scratch_stream(ctx, s);
-    if (rc) return rc;
-    const int max_blocks = ctx->num_cus * 8;
-    EmitIndex eix = {};
-    bool built;
-    uint64_t chunks;
-    if (bounds) {
-        chunks = cols->n / CHUNK_POINTS;
-        built = ix->d_boxes && ix->xyz == cols->xyz && ix->n_xyz == cols->n;
-        if (!built) {
-            const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
-            rc = pcq_ensure_partials(ctx, (size_t)grid);
-            if (rc) return rc;
-            if (ix->d_boxes) PCQ_HIP(hipFree(ix->d_boxes));
-            ix->d_boxes = nullptr;
-            PCQ_HIP(hipMalloc((void **)&ix->d_boxes, chunks * sizeof(ChunkBox)));
-            DevPred boxes_only = dp;
-            boxes_only.empty = 1;  // the boxes alone: the emit below counts
-            hipLaunchKernelGGL(k_index_build_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), chunks, boxes_only,
-                               ix->d_boxes, ctx->d_partials);
-            PCQ_HIP(hipGetLastError());
-            ix->xyz = cols->xyz;
-            ix->n_xyz = cols->n;
-            ix->nchunks = chunks;
-        }
-        eix.boxes = reinterpret_cast<const int32_t *>(ix->d_boxes);
-        eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
-    } else {
-        chunks = (cols->n + CLASS_CHUNK - 1) / CLASS_CHUNK;
-        built = ix->d_hist && ix->cls == cols->cls && ix->n_cls == cols->n;
-        if (!built) {
-            if (ix->d_hist) PCQ_HIP(hipFree(ix->d_hist));
-            ix->d_hist = nullptr;
-            PCQ_HIP(hipMalloc((void **)&ix->d_hist, chunks * 256 * sizeof(uint32_t)));
-            const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
-            hipLaunchKernelGGL(k_index_build_class, dim3(grid), dim3(BLOCK), 0, s, (const uint8_t *)cols->cls, cols->n, chunks, ix->d_hist);
-            PCQ_HIP(hipGetLastError());
-            ix->cls = cols->cls;
-            ix->n_cls = cols->n;
-            ix->ncchunks = chunks;
-        }
-        eix.hist = ix->d_hist;
-        eix.covered_tiles = cols->n / EMIT_TILE_POINTS;  // whole tiles
-    }
-    ix->last = pcq_index_stats{};
-    ix->last.chunks = chunks;
-    if (!built) {  // the build read every chunk
-        ix->last.built = 1;
-        ix->last.scanned = chunks;
-        ix->stats_stream = nullptr;
-        ix->stats_kind = 0;
-    } else {
-        ix->stats_stream = s;  // classified and fetched by pcq_index_get_stats: nothing on the scan path
-        ix->stats_kind = bounds ? 1 : 2;
-        ix->stats_pred = dp;
-    }
-    return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+// What the index covers: packed, 16-byte aligned positions with at least one whole chunk; packed class bytes.
+static bool bounds_index_covers(const pcq_columns *cols) {
+    return cols->xyz_stride == 12 && ((uintptr_t)cols->xyz & 15) == 0 && cols->n >= CHUNK_POINTS;
+}
+static bool class_index_covers(const pcq_columns *cols) { return cols->cls && cols->cls_stride == 1 && cols->n > 0; }
+
+// The boxes of the `chunks` whole chunks of cols->xyz, built on `s` unless the index holds them for these columns already
+// (*had).  The build counts the matches of `build_with` into the context's partials on its way: the real predicate for a
+// count scan (one launch builds and counts), one with empty = 1 for a buffer scan (the boxes alone: the emit counts).
+static int ensure_boxes(pcq_ctx *ctx, pcq_index *ix, const pcq_columns *cols, uint64_t chunks, int grid, const DevPred &build_with,
+                        hipStream_t s, bool *had) {
+    *had = ix->d_boxes && ix->xyz == cols->xyz && ix->n_xyz == cols->n;
+    if (*had) return PCQ_OK;
+    if (ix->d_boxes) PCQ_HIP(hipFree(ix->d_boxes));
+    ix->d_boxes = nullptr;
+    PCQ_HIP(hipMalloc((void **)&ix->d_boxes, chunks * sizeof(ChunkBox)));
+    hipLaunchKernelGGL(k_index_build_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), chunks, build_with,
+                       ix->d_boxes, ctx->d_partials);
+    PCQ_HIP(hipGetLastError());
+    ix->xyz = cols->xyz;
+    ix->n_xyz = cols->n;
+    ix->nchunks = chunks;
+    return PCQ_OK;
+}
+// The same for the class histograms of cols->cls.
+static int ensure_hist(pcq_index *ix, const pcq_columns *cols, uint64_t chunks, int grid, hipStream_t s, bool *had) {
+    *had = ix->d_hist && ix->cls == cols->cls && ix->n_cls == cols->n;
+    if (*had) return PCQ_OK;
+    if (ix->d_hist) PCQ_HIP(hipFree(ix->d_hist));
+    ix->d_hist = nullptr;
+    PCQ_HIP(hipMalloc((void **)&ix->d_hist, chunks * 256 * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_index_build_class, dim3(grid), dim3(BLOCK), 0, s, (const uint8_t *)cols->cls, cols->n, chunks, ix->d_hist);
+    PCQ_HIP(hipGetLastError());
+    ix->cls = cols->cls;
+    ix->n_cls = cols->n;
+    ix->ncchunks = chunks;
+    return PCQ_OK;
 }
 
 extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
@@ -422,88 +389,87 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
     PCQ_ON_DEVICE_OF_CTX(ctx);
     if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: null argument");
     if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed: count and buffer collectors only");
-    // no index of these kinds (nor of a world-space box, nor of a kind that does not exist: pcq_scan_dev validates): the plain
-    // scan, statistics that claim nothing
-    if (pred->kind != PCQ_PRED_BOUNDS && pred->kind != PCQ_PRED_CLASS) {
+    int rc = pcq_validate_scan(cols, pred, c);  // (before the index or the collector is touched: the kernels below trust the columns)
+    if (rc) return rc;
+    const bool bounds = pred->kind == PCQ_PRED_BOUNDS;
+    // no index of the other kinds (nor of a world-space box): the plain scan, statistics that claim nothing
+    if (!bounds && pred->kind != PCQ_PRED_CLASS) {
         ix->last = pcq_index_stats{};
         ix->stats_stream = nullptr;
         ix->stats_kind = 0;
         return pcq_scan_dev(ctx, cols, pred, c, stream);
     }
-    if (c->kind == COLL_BUFFER) return scan_buffer_indexed(ctx, cols, pred, ix, c, stream);
+    if (!(bounds ? bounds_index_covers(cols) : class_index_covers(cols))) return pcq_scan_dev(ctx, cols, pred, c, stream);  // layout the index does not cover: plain scan
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    c->last_stream = s;
     DevPred dp;
-    int rc = pcq_make_dev_pred(pred, &dp);
+    rc = pcq_make_dev_pred(pred, &dp);
     if (rc) return rc;
     rc = pcq_scratch_stream(ctx, s);
     if (rc) return rc;
+    const bool count = c->kind == COLL_COUNT;
+    const uint64_t chunks = bounds ? cols->n / CHUNK_POINTS : (cols->n + CLASS_CHUNK - 1) / CLASS_CHUNK;
     const int max_blocks = ctx->num_cus * 8;
-    if (pred->kind == PCQ_PRED_BOUNDS) {
-        if (cols->xyz_stride != 12 || ((uintptr_t)cols->xyz & 15) != 0 || cols->n < CHUNK_POINTS)
-            return pcq_scan_dev(ctx, cols, pred, c, stream);  // layout the index does not cover: plain scan
-        const uint64_t nchunks = cols->n / CHUNK_POINTS;
-        const uint64_t rest_first = nchunks * CHUNK_POINTS;
-        const int grid = (int)(nchunks < (uint64_t)max_blocks ? nchunks : (uint64_t)max_blocks);
+    const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+    bool had;
+    if (bounds) {
         rc = pcq_ensure_partials(ctx, (size_t)grid);
         if (rc) return rc;
-        const bool built = ix->d_boxes && ix->xyz == cols->xyz && ix->n_xyz == cols->n;
-        ix->last = pcq_index_stats{};
-        ix->last.chunks = nchunks;
-        if (!built) {
-            if (ix->d_boxes) PCQ_HIP(hipFree(ix->d_boxes));
-            ix->d_boxes = nullptr;
-            PCQ_HIP(hipMalloc((void **)&ix->d_boxes, nchunks * sizeof(ChunkBox)));
-            hipLaunchKernelGGL(k_index_build_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), nchunks, dp,
-                               ix->d_boxes, ctx->d_partials);
-            ix->xyz = cols->xyz;
-            ix->n_xyz = cols->n;
-            ix->nchunks = nchunks;
-            ix->last.built = 1;
-            ix->last.scanned = nchunks;
-        } else {
-            PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(k_index_count_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), nchunks, dp,
-                               ix->d_boxes, ctx->d_partials, ix->d_stats);
-        }
-        hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
-        PCQ_HIP(hipGetLastError());
-        ix->stats_stream = built ? s : nullptr;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
-        ix->stats_kind = 0;
-        if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned
-            pcq_columns tail = *cols;
-            tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
-            tail.cls = nullptr;
-            tail.rgb = nullptr;
-            tail.n = cols->n - rest_first;
-            return pcq_scan_dev(ctx, &tail, pred, c, stream);
-        }
-        return PCQ_OK;
+        DevPred build_with = dp;
+        if (!count) build_with.empty = 1;
+        rc = ensure_boxes(ctx, ix, cols, chunks, grid, build_with, s, &had);
+    } else {
+        rc = ensure_hist(ix, cols, chunks, grid, s, &had);
     }
-    // class
-    if (cols->cls_stride != 1 || !cols->cls) return pcq_scan_dev(ctx, cols, pred, c, stream);
-    const uint64_t ncc = (cols->n + CLASS_CHUNK - 1) / CLASS_CHUNK;
-    if (ncc == 0) return PCQ_OK;
-    const bool built = ix->d_hist && ix->cls == cols->cls && ix->n_cls == cols->n;
+    if (rc) return rc;
+    ix->last = pcq_index_stats{};
+    ix->last.chunks = chunks;
     ix->stats_stream = nullptr;
     ix->stats_kind = 0;
-    ix->last = pcq_index_stats{};
-    ix->last.chunks = ncc;
-    if (!built) {
-        if (ix->d_hist) PCQ_HIP(hipFree(ix->d_hist));
-        ix->d_hist = nullptr;
-        PCQ_HIP(hipMalloc((void **)&ix->d_hist, ncc * 256 * sizeof(uint32_t)));
-        const int grid = (int)(ncc < (uint64_t)max_blocks ? ncc : (uint64_t)max_blocks);
-        hipLaunchKernelGGL(k_index_build_class, dim3(grid), dim3(BLOCK), 0, s, (const uint8_t *)cols->cls, cols->n, ncc, ix->d_hist);
-        ix->cls = cols->cls;
-        ix->n_cls = cols->n;
-        ix->ncchunks = ncc;
+    if (!had) {  // the build read every chunk
         ix->last.built = 1;
-        ix->last.scanned = ncc;
-    } else {
-        ix->last.whole = ncc;  // answered from the histograms: no classification byte is read
+        ix->last.scanned = chunks;
     }
-    hipLaunchKernelGGL(k_index_count_class, dim3(1), dim3(BLOCK), 0, s, ix->d_hist, ncc, (uint32_t)pred->cls, c->d_count);
+    if (!count) {
+        // A buffer collector: the emit's count pass takes each tile's state from the index (scan_generic.hip, k_tile_counts with
+        // IDX), then the records are written as by pcq_scan_dev.
+        if (had) {
+            ix->stats_stream = s;  // classified and fetched by pcq_index_get_stats: nothing on the scan path
+            ix->stats_kind = bounds ? 1 : 2;
+            ix->stats_pred = dp;
+        }
+        EmitIndex eix = {};
+        if (bounds) {
+            eix.boxes = reinterpret_cast<const int32_t *>(ix->d_boxes);
+            eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
+        } else {
+            eix.hist = ix->d_hist;
+            eix.covered_tiles = cols->n / EMIT_TILE_POINTS;  // whole tiles
+        }
+        return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+    }
+    c->last_stream = s;
+    if (!bounds) {
+        if (had) ix->last.whole = chunks;  // answered from the histograms: no classification byte is read
+        hipLaunchKernelGGL(k_index_count_class, dim3(1), dim3(BLOCK), 0, s, ix->d_hist, chunks, (uint32_t)pred->cls, c->d_count);
+        PCQ_HIP(hipGetLastError());
+        return PCQ_OK;
+    }
+    if (had) {
+        PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_index_count_bounds, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), chunks, dp,
+                           ix->d_boxes, ctx->d_partials, ix->d_stats);
+        ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
+    }
+    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
     PCQ_HIP(hipGetLastError());
+    const uint64_t rest_first = chunks * CHUNK_POINTS;
+    if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned
+        pcq_columns tail = *cols;
+        tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
+        tail.cls = nullptr;
+        tail.rgb = nullptr;
+        tail.n = cols->n - rest_first;
+        return pcq_scan_dev(ctx, &tail, pred, c, stream);
+    }
     return PCQ_OK;
 }

@@ -248,7 +248,8 @@ static int grid_fold(pcq_ctx *ctx, pcq_collector *c) {
     GridState *gs = c->gs;
     if (!gs || gs->runs.empty()) return PCQ_OK;
     hipStream_t s = ctx->stream;
-    if (c->last_stream && c->last_stream != s) PCQ_HIP(hipStreamSynchronize(c->last_stream));
+    int wrc = pcq_collector_wait_last(c, s);
+    if (wrc) return wrc;
     Scratch tmp(ctx);
     StreamDrainOnExit drain_before_tmp(s);
     const int nruns = (int)gs->runs.size();

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pcq.h"
+#include "stage_plan.h"  // the predicate-kind helpers (pred_has_box, ...), the collector kinds, what a scan reads
 
 // ---------------------------------------------------------------------------------------------
 // error plumbing
@@ -64,11 +65,6 @@ struct DevPred {
     uint32_t _pad;
     double wmin[3], wmax[3];  // PCQ_PRED_BOUNDS_F64; PCQ_PRED_TIME, PCQ_PRED_BOUNDS_TIME: [wmin[0], wmax[0])
 };
-// The kinds by what they test.  The combined kinds (PCQ_PRED_BOUNDS_CLASS / _TIME) test the integer box (lo, width, empty)
-// AND the attribute in pcq_columns.cls: a class byte or an f64 GPS time.
-__host__ __device__ constexpr bool pred_has_box(int k) { return k == PCQ_PRED_BOUNDS || k == PCQ_PRED_BOUNDS_CLASS || k == PCQ_PRED_BOUNDS_TIME; }
-__host__ __device__ constexpr bool pred_is_combined(int k) { return k == PCQ_PRED_BOUNDS_CLASS || k == PCQ_PRED_BOUNDS_TIME; }
-__host__ __device__ constexpr bool pred_tests_time(int k) { return k == PCQ_PRED_TIME || k == PCQ_PRED_BOUNDS_TIME; }
 
 struct DevCols {
     const uint8_t *xyz;
@@ -154,13 +150,57 @@ struct PoolBlock {
     size_t bytes = 0;
     bool used = false;
 };
+// The staging ring of the host / file scans (host_stream.hip): two pinned host buffers with their device twins, the events
+// that order their reuse, the copy helpers that fill them and the two warm-up threads.  Nothing else names its state; what
+// the operations below keep true:
+//   * a pair is present only when BOTH its pinned and its device buffer exist — an allocation that fails halfway frees the
+//     half, so that the next call allocates again and reports the failure (pcq.h: pcq_prepare_host_scans);
+//   * whatever frees, resizes or re-creates the pairs or the copy pool joins the prepare thread first, and whatever uses
+//     the copy stream joins the copy-path warm-up first;
+//   * pair b is "busy" from mark_busy(b) until its event has been waited for or the streams have been drained.
+class StageRing {
+public:
+    int init(pcq_ctx *ctx);                  // (the events; pcq_init)
+    void destroy();                          // joins, drains and frees everything (pcq_shutdown)
+    int ensure(size_t bytes, int upto = 2);  // pairs 0 .. upto-1 present, each of at least `bytes`
+    void drop();                             // no pairs (drained first), no copy pool: the next scan re-creates them (option "numa_local")
+    void prepare();                          // pcq_prepare_host_scans: both pairs and the copy pool, on a thread of its own
+    void join_prepare();                     // ... which reads chunk_points, copy_threads and numa_local: join it before they change
+    bool copy_path_ready();                  // false: the process's first large copy has not been made — now under way on a thread
+    void wait_copy_path();                   // in front of the caller's own use of the copy stream
+    uint8_t *host(int b) const { return h_[b]; }
+    uint8_t *dev(int b) const { return d_[b]; }
+    int fetch(int fd, uint8_t *dst, const uint8_t *src, size_t bytes);  // caller memory or file -> pinned memory, over the copy helpers
+    int copy_out(int b, void *d_dst, size_t bytes);  // pinned buffer b -> device memory on the copy stream; marks "copied"
+    int wait_copied(int b, hipStream_t s);   // `s` waits for that copy
+    int host_wait_copied(int b);             // the host does
+    int wait_free(int b);                    // until the kernels that read pair b last are done with it
+    int mark_busy(int b, hipStream_t s);     // pair b is read by what has been enqueued on s so far
+    bool busy() const { return busy_[0] || busy_[1]; }
+    void set_idle() { busy_[0] = busy_[1] = false; }  // (the caller has drained the compute stream)
+    int drain();                             // both streams drained, no pair busy
+
+private:
+    int ensure_now(size_t bytes, int upto);
+    void ensure_pool_now();
+    void free_pairs();
+    pcq_ctx *ctx_ = nullptr;
+    uint8_t *h_[2] = {nullptr, nullptr}, *d_[2] = {nullptr, nullptr};
+    size_t bytes_ = 0;                       // the size the pairs have, or will be allocated with
+    bool busy_[2] = {false, false};          // kernels not yet known to be done with staging pair b (event consumed_[b])
+    hipEvent_t copied_[2] = {nullptr, nullptr}, consumed_[2] = {nullptr, nullptr};
+    CopyPool *pool_ = nullptr;               // created on first use by pcq_scan_host / pcq_scan_fd
+    std::thread prepare_;                    // pcq_prepare_host_scans: joined by whoever touches the pairs or the copy pool next
+    std::thread copy_warm_;                  // sets the copy path up: one pinned megabyte through hipMemcpyAsync, beside the first file's scan
+    std::atomic<int> copy_warm_state_{0};    // 0 not started, 1 under way, 2 done
+    void *copy_warm_h_ = nullptr, *copy_warm_d_ = nullptr;
+};
+
 struct pcq_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // compute stream
     hipStream_t copy_stream = nullptr;  // H2D stream
     hipStream_t scratch_stream = nullptr;  // the stream whose kernels may still be using the context's scratch (pcq_scratch_stream)
-    hipEvent_t copied[2] = {nullptr, nullptr};
-    hipEvent_t consumed[2] = {nullptr, nullptr};
     int num_cus = 0;
     hipDeviceProp_t prop;
     // scratch: per-block partial counts / block offsets
@@ -168,12 +208,7 @@ struct pcq_ctx {
     size_t partials_cap = 0;
     uint64_t *d_scalars = nullptr;      // a few device u64 scratch words
     uint64_t *h_scalars = nullptr;      // pinned mirror
-    // staging for pcq_scan_host
-    uint8_t *h_stage[2] = {nullptr, nullptr};
-    uint8_t *d_stage[2] = {nullptr, nullptr};
-    size_t stage_bytes = 0;
-    std::thread stage_warm;             // pcq_prepare_host_scans: joined by whoever touches the staging ring or the copy pool next
-    bool stage_busy[2] = {false, false};  // kernels not yet known to be done with staging pair b (event consumed[b])
+    StageRing ring;                     // staging for pcq_scan_host / pcq_scan_fd (host_stream.hip)
     // segment table for batched launches
     DevSegment *d_segments = nullptr;
     DevSegment *h_segments = nullptr;
@@ -201,10 +236,7 @@ struct pcq_ctx {
     int64_t grid_deferred = 0;          // diagnostics: bins the streaming fold left to k_fold<BIG> (survivor list outgrown)
     int host_in_place = 2;              // option: count and grid scans of host / file data read the pinned staging ring IN PLACE (over PCIe) instead of
                                         // copying it to a device twin first: 0 never, 1 always, 2 while the process's copy path is being set up
-                                        // (pcq_api.hip scan_host_impl)
-    std::thread copy_warm;              // the thread that sets it up: one pinned megabyte through hipMemcpyAsync, beside the first file's scan
-    std::atomic<int> copy_warm_state{0};  // 0 not started, 1 under way, 2 done
-    void *copy_warm_h = nullptr, *copy_warm_d = nullptr;
+                                        // (host_stream.hip scan_host_impl)
     int emit_park_max = 256;            // option: a tile with at most this many matches leaves them as 16-byte words for the emit (0 = never; <= 256)
     int emit_sparse_max = 64;           // option: a tile of 2048 points with at most this many matches is written by k_emit_sparse (0 = never)
     bool scanned_before = false;        // (PCQ_TIMING: the first host / file scan of a context prints where its time goes)
@@ -234,15 +266,12 @@ struct pcq_ctx {
                                   // GPU, page-cache pages on the other socket need 8 (profiles/r01_cli_probe_timing.log); a stream of
                                   // files read with pread: 8 -> 5.5, 12 -> 5.0, 16 -> 4.9 ms per 240 MB (profiles/r04_cli_threads.log).
                                   // pcq_init caps it at the host's hardware threads per GPU.
-    CopyPool *copy_pool = nullptr;  // created on first use by pcq_scan_host / pcq_scan_fd
     uint64_t chunk_points = 1ull << 20;    // 12 MB of positions per staging chunk: the steady rate of 24 MB (profiles/r01_host_path_rate.json: 1-8 Mi equal)
                                            // at half the pinning in front of a process's first file (profiles/r04_cli_chunks.log: 25 -> 20 ms)
 };
 
-// pcq_api.hip: [offset, offset+bytes) of fd -> device memory through the pinned staging buffers
+// host_stream.hip: [offset, offset+bytes) of fd -> device memory through the pinned staging buffers
 int pcq_stream_fd_to_device(pcq_ctx *ctx, int fd, uint64_t offset, uint64_t bytes, uint8_t *d_dst);
-
-enum { COLL_COUNT = 0, COLL_BUFFER = 1, COLL_GRID = 2 };
 
 struct pcq_collector {
     int kind = COLL_COUNT;
@@ -270,6 +299,9 @@ struct pcq_collector {
 // ---------------------------------------------------------------------------------------------
 int pcq_make_dev_pred(const pcq_predicate *p, DevPred *out);
 int pcq_scratch_stream(pcq_ctx *ctx, hipStream_t s);
+// collectors.hip: scans enqueued on a caller's stream may still be reading and moving the collector's state — waits for the
+// stream of the collector's last scan unless that is `s` (whose order the caller's next operation keeps anyway)
+int pcq_collector_wait_last(const pcq_collector *c, hipStream_t s);
 int pcq_ensure_partials(pcq_ctx *ctx, size_t n);
 
 // scan_count.hip
@@ -289,7 +321,7 @@ int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &p
 // ix (optional): the count pass takes each tile's state from the chunk index first (bounds or class predicates)
 int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint8_t *d_out31, const uint64_t *d_npoints_in,
                            uint64_t *d_npoints_out, hipStream_t s, const EmitIndex *ix = nullptr);
-// pcq_api.hip: pcq_scan_dev on stream s; ix (optional) is handed to the buffer collector's emit
+// collectors.hip: pcq_scan_dev on stream s; ix (optional) is handed to the buffer collector's emit
 int pcq_validate_scan(const pcq_columns *cols, const pcq_predicate *pred, const pcq_collector *c);
 int pcq_scan_dev_impl(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_collector *c, hipStream_t s,
                       const EmitIndex *ix = nullptr);

@@ -249,7 +249,7 @@ def box_empty(p):
 
 def chunks_of(ds, op, coll_kind, chunk_points):
     """The [first, end) point ranges one scan hands to the device: the whole range for a device scan, staging chunks for
-    a host or file scan (pcq_api.hip scan_host_impl)."""
+    a host or file scan (host_stream.hip scan_host_impl)."""
     n = op["n"]
     if op["entry"] in ("scan_dev", "scan_dev_indexed"):
         return [(0, n)]

@@ -368,6 +368,22 @@ def test_copy_pool_under_thread_sanitizer(tmp_path):
     assert r.returncode == 0 and r.stdout.startswith("ok 250"), (r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_staging_plan_of_the_host_scans(tmp_path):
+    """csrc/stage_plan.h decides what a host / file scan moves and where it lies in a staging buffer: which columns, AoS or
+    SoA, points per chunk, region offsets, bytes per transfer.  Pure host arithmetic, compiled with g++ alone: every
+    predicate kind x collector kind x layout x n x chunk_points against the plan's invariants, and six plans against
+    numbers worked out by hand (tests/native/stage_plan_driver.cpp)."""
+    import shutil
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "stage_plan")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "native", "stage_plan_driver.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_every_entry_point_runs_on_the_context_device():
     """A driver thread that never chose a device sits on device 0; draining the collectors of GPU k from it must
     still allocate and launch on GPU k.  Every extern "C" function that takes a context, a collector or an index

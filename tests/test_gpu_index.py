@@ -113,3 +113,26 @@ def test_indexed_class_count(oracle, gpu_ctx, n):
     finally:
         gpu_ctx.index_free(ix)
         gpu_ctx.free(base)
+
+
+def test_indexed_count_validates_its_columns_first(oracle, gpu_ctx):
+    """An indexed bounds count over a layout the index covers (resident, 16-byte aligned, two whole chunks) launches its own
+    kernels on the columns it is handed: like every scan it refuses what pcq_validate_scan refuses — here a first_index
+    above 2^62 — before it counts anything or builds the index."""
+    spec = specs._spec(99, 8192, 1, (0.01,) * 3, (0.0,) * 3, (-500, -500, -100), (1001, 1001, 201))
+    xyz, _ = oracle.synth_columns(spec)
+    base, dptr = upload(gpu_ctx, xyz)
+    assert dptr % 16 == 0
+    cols = binding.make_columns(xyz=dptr, n=8192, first_index=2 ** 62 + 1, scale=list(spec.scale), offset=list(spec.offset))
+    ix = gpu_ctx.index_new()
+    cc = gpu_ctx.count_collector()
+    try:
+        with pytest.raises(pkg.PcqError) as e:
+            gpu_ctx.scan_dev_indexed(cols, pkg.Predicate.bounds([-2 ** 31] * 3, [2 ** 31 - 1] * 3), ix, cc)
+        assert e.value.code == binding.PCQ_ERR_ARG
+        assert cc.point_count() == 0
+        assert gpu_ctx.index_stats(ix) == {"chunks": 0, "skipped": 0, "whole": 0, "scanned": 0, "built": 0}
+    finally:
+        cc.free()
+        gpu_ctx.index_free(ix)
+        gpu_ctx.free(base)

@@ -843,6 +843,27 @@ def test_prepare_host_scans_runs_beside_the_caller_and_changes_nothing(oracle):
             ctx.scan_host(cols, pkg.Predicate.bounds(lmin, lmax), cc)
             assert cc.point_count() == want
             cc.free()
+    # The prepare thread reads numa_local, copy_threads and chunk_points, and allocates what numa_local frees: each of
+    # them set right behind it waits for the thread.  60 000 points in chunks of 4096: 15 chunks, both pairs, pairs reused.
+    ob = oracle.buffer_collector()
+    assert oracle.search_last_bounds(image, bmin, bmax, ob) == 0
+    rcols = binding.make_columns(xyz=image.ctypes.data + otp, cls=image.ctypes.data + otp + 15 * n, n=n,
+                                 scale=list(hdr.scale), offset=list(hdr.offset))
+    with pkg.Context(0) as ctx:
+        numa_local = ctx.get_option("numa_local")
+        ctx.prepare_host_scans()
+        ctx.set_option("numa_local", 0)
+        ctx.set_option("copy_threads", 3)
+        ctx.set_option("chunk_points", 4096)
+        cc, gb = ctx.count_collector(), ctx.buffer_collector()
+        ctx.scan_host(cols, pkg.Predicate.bounds(lmin, lmax), cc)
+        ctx.scan_host(rcols, pkg.Predicate.bounds(lmin, lmax), gb)
+        assert cc.point_count() == want == gb.point_count()
+        assert gb.points().tobytes() == ob.points().tobytes()
+        cc.free()
+        gb.free()
+        ctx.set_option("numa_local", numa_local)
+    ob.free()
     with pkg.Context(0) as ctx:
         ctx.prepare_host_scans()  # and nothing else: shutdown joins the thread
 
