@@ -21,61 +21,16 @@
 #include <new>
 
 #include "pcq_internal.h"
+#include "scan_tiles.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
 constexpr int WAVES = 4;
-constexpr int TILE_POINTS = 256;
 constexpr int CHUNK_TILES = 16;                           // 16 wave-tiles = 4096 points = 48 KiB
 constexpr uint64_t CHUNK_POINTS = (uint64_t)CHUNK_TILES * TILE_POINTS;
 constexpr uint64_t CLASS_CHUNK = 65536;
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-constexpr uint64_t R0 = 0x9249249249249249ull, R1 = 0x2492492492492492ull, R2 = 0x4924924924924924ull;
-__device__ __forceinline__ constexpr uint64_t start_lanes(int s) { return (s % 3) == 0 ? R0 : ((s % 3) == 1 ? R2 : R1); }
-__device__ __forceinline__ v4i ld_nt(const v4i *p) { return __builtin_nontemporal_load(p); }
-
-struct LaneBox {
-    int lo[3];
-    uint32_t w[3];
-};
-__device__ __forceinline__ LaneBox rotate_box(const int32_t (&lo)[3], const uint32_t (&w)[3], int lane) {
-    const int r = lane % 3;
-    LaneBox b;
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-        const int c = (r + t) % 3;
-        b.lo[t] = c == 0 ? lo[0] : (c == 1 ? lo[1] : lo[2]);
-        b.w[t] = c == 0 ? w[0] : (c == 1 ? w[1] : w[2]);
-    }
-    return b;
-}
-
-// Same mask algebra as scan_count.hip::tile_count_regs (see there for the derivation).
-__device__ __forceinline__ uint32_t tile_count_regs(const v4i (&v)[3], const LaneBox &b) {
-    uint64_t m[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int t = (k + j) % 3;
-            m[k][j] = __ballot((uint32_t)(v[k][j] - b.lo[t]) <= b.w[t]);
-        }
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint64_t m0 = m[k][0], m1 = m[k][1], m2 = m[k][2], m3 = m[k][3];
-        const uint64_t c0 = k < 2 ? m[k < 2 ? k + 1 : k][0] : 0ull;
-        const uint64_t c1 = k < 2 ? m[k < 2 ? k + 1 : k][1] : 0ull;
-        const uint64_t n0 = (m0 >> 1) | (c0 << 63), n1 = (m1 >> 1) | (c1 << 63);
-        const uint64_t a = m1 & m2, t0 = m0 & a, t1 = a & m3, bb = m3 & n0, t2 = m2 & bb, t3 = bb & n1;
-        const uint64_t s012 = (t0 & start_lanes(k)) | (t1 & start_lanes(k + 1)) | (t2 & start_lanes(k + 2));
-        cnt += (uint32_t)__popcll(s012) + (uint32_t)__popcll(t3 & start_lanes(k + 3));
-    }
-    return cnt;
-}
+// (BLOCK, TILE_POINTS, LaneBox, rotate_box, ld_nt and the mask algebra tile_count_regs: scan_tiles.h)
 
 struct ChunkBox {  // integer AABB of one chunk
     int32_t mn[3], mx[3];
@@ -202,6 +157,58 @@ __global__ __launch_bounds__(BLOCK) void k_index_count_bounds(const v4i *__restr
     }
 }
 
+// Box AND class (pcq_scan_dev_indexed_combined): each 4096-point chunk takes its box state together with the state of the
+// 65536-point class chunk it lies in (index_combined_state).  Only SCAN chunks are read: their positions and their 4096 class
+// bytes, tested tile by tile as K1 does with its second column (scan_tiles.h, COL_U8; the class block at any alignment).
+__global__ __launch_bounds__(BLOCK) void k_index_count_bounds_class(const v4i *__restrict__ base, const uint8_t *__restrict__ cls, uint64_t n,
+                                                                    uint64_t nchunks, DevPred pred, const ChunkBox *__restrict__ boxes,
+                                                                    const uint32_t *__restrict__ hist, uint64_t *__restrict__ partials,
+                                                                    unsigned long long *__restrict__ stats) {
+    __shared__ uint64_t s_cnt[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const LaneBox lb = rotate_box(pred.lo, pred.width, lane);
+    const Col2<COL_U8> c2 = col2_setup(cls, pred, lane, IntC<COL_U8>{});
+    uint64_t total = 0;
+    uint32_t n_skip = 0, n_full = 0, n_scan = 0;
+    for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        const ChunkBox cb = boxes[ch];  // block-uniform
+        const uint64_t cch = ch / (CLASS_CHUNK / CHUNK_POINTS), first = cch * CLASS_CHUNK;
+        const int st = index_combined_state(index_box_state(cb.mn, cb.mx, pred),
+                                            index_class_state(hist[cch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK));
+        if (st == CHUNK_NONE) {
+            n_skip++;
+            continue;
+        }
+        if (st == CHUNK_ALL) {
+            if (threadIdx.x == 0) total += CHUNK_POINTS;
+            n_full++;
+            continue;
+        }
+        n_scan++;
+#pragma unroll
+        for (int q = 0; q < CHUNK_TILES / WAVES; q++) {
+            const uint64_t t = ch * CHUNK_TILES + (uint64_t)wave * (CHUNK_TILES / WAVES) + q;
+            const v4i *tile = base + t * 192;
+            v4i v[3];
+            v[0] = ld_nt(tile + lane);
+            v[1] = ld_nt(tile + 64 + lane);
+            v[2] = ld_nt(tile + 128 + lane);
+            Col2Regs<COL_U8> r;
+            col2_load_plain(r, c2, t);
+            const uint32_t c = tile_count_regs<COL_U8>(v, lb, c2, verdict_word(r, c2));
+            if (lane == 0) total += c;
+        }
+    }
+    if (lane == 0) s_cnt[wave] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (n_skip) atomicAdd(&stats[0], (unsigned long long)n_skip);
+        if (n_full) atomicAdd(&stats[1], (unsigned long long)n_full);
+        if (n_scan) atomicAdd(&stats[2], (unsigned long long)n_scan);
+    }
+}
+
 // First class scan: 256-bin histogram per 65536-point chunk (LDS atomics), one block per chunk.
 __global__ __launch_bounds__(BLOCK) void k_index_build_class(const uint8_t *__restrict__ cls, uint64_t n, uint64_t nchunks,
                                                              uint32_t *__restrict__ hist) {
@@ -247,7 +254,7 @@ __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restri
 
 // Statistics of an indexed buffer scan in index-chunk units: stats[0..2] += chunks disjoint from the predicate (not read by
 // the count pass) / contained (not read by the count pass) / straddling (read) — the classification k_tile_counts<.., IDX> took
-// its tile states from.  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
+// its tile states from.  boxes alone: a bounds scan; hist alone: a class scan (class chunks); both: box AND class (bounds chunks).  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
 __global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__restrict__ boxes, const uint32_t *__restrict__ hist, uint64_t nchunks,
                                                             uint64_t n, DevPred pred, unsigned long long *__restrict__ stats) {
     uint32_t k[3] = {0, 0, 0};
@@ -256,6 +263,10 @@ __global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__re
         if (boxes) {
             const ChunkBox cb = boxes[ch];
             st = index_box_state(cb.mn, cb.mx, pred);
+            if (hist) {  // box AND class, in bounds chunks
+                const uint64_t cch = ch / (CLASS_CHUNK / CHUNK_POINTS), first = cch * CLASS_CHUNK;
+                st = index_combined_state(st, index_class_state(hist[cch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK));
+            }
         } else {
             const uint64_t first = ch * CLASS_CHUNK;
             st = index_class_state(hist[ch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK);
@@ -289,8 +300,8 @@ struct pcq_index {
     unsigned long long *d_stats = nullptr;
     pcq_index_stats last = {};
     hipStream_t stats_stream = nullptr;  // non-null: `last` must be completed from d_stats (fetched lazily)
-    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds count) · 1 / 2: a bounds / class buffer scan,
-    DevPred stats_pred = {};             //    classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
+    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds count) · 1 / 2 / 3: a bounds / class / box AND class buffer
+    DevPred stats_pred = {};             //    scan, classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
 };
 
 extern "C" int pcq_index_new(pcq_ctx *ctx, pcq_index **out) {
@@ -326,12 +337,12 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     if (ix->stats_stream) {  // the counters of the last indexed bounds scan are still on the device
         unsigned long long h[3] = {0, 0, 0};
         if (ix->stats_kind) {
-            const uint64_t nch = ix->stats_kind == 1 ? ix->nchunks : ix->ncchunks;
+            const uint64_t nch = ix->stats_kind == 2 ? ix->ncchunks : ix->nchunks;
             const int grid = (int)((nch + BLOCK - 1) / BLOCK < (uint64_t)ix->ctx->num_cus ? (nch + BLOCK - 1) / BLOCK : (uint64_t)ix->ctx->num_cus);
             PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), ix->stats_stream));
             if (grid > 0)
-                hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream, ix->stats_kind == 1 ? ix->d_boxes : nullptr,
-                                   ix->stats_kind == 2 ? ix->d_hist : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
+                hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream, ix->stats_kind != 2 ? ix->d_boxes : nullptr,
+                                   ix->stats_kind != 1 ? ix->d_hist : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
             PCQ_HIP(hipGetLastError());
         }
         PCQ_HIP(hipStreamSynchronize(ix->stats_stream));
@@ -467,6 +478,74 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
         pcq_columns tail = *cols;
         tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
         tail.cls = nullptr;
+        tail.rgb = nullptr;
+        tail.n = cols->n - rest_first;
+        return pcq_scan_dev(ctx, &tail, pred, c, stream);
+    }
+    return PCQ_OK;
+}
+
+// Box AND class through both parts of the index.  Parts missing for these columns are built first (the boxes without a count:
+// k_index_build_bounds knows boxes only), then the pruned pass always runs.
+extern "C" int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                                             pcq_collector *c, void *stream) {
+    PCQ_ON_DEVICE_OF_CTX(ctx);
+    if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_combined: null argument");
+    if (pred->kind != PCQ_PRED_BOUNDS_CLASS)
+        return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_combined: predicate kind %d (PCQ_PRED_BOUNDS_CLASS only)", pred->kind);
+    if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_combined: count and buffer collectors only");
+    int rc = pcq_validate_scan(cols, pred, c);  // (before the index or the collector is touched: the kernels below trust the columns)
+    if (rc) return rc;
+    if (!(bounds_index_covers(cols) && class_index_covers(cols))) {  // layout the index does not cover: plain scan, statistics that claim nothing
+        ix->last = pcq_index_stats{};
+        ix->stats_stream = nullptr;
+        ix->stats_kind = 0;
+        return pcq_scan_dev(ctx, cols, pred, c, stream);
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    DevPred dp;
+    rc = pcq_make_dev_pred(pred, &dp);
+    if (rc) return rc;
+    rc = pcq_scratch_stream(ctx, s);
+    if (rc) return rc;
+    const uint64_t chunks = cols->n / CHUNK_POINTS, cchunks = (cols->n + CLASS_CHUNK - 1) / CLASS_CHUNK;
+    const int max_blocks = ctx->num_cus * 8;
+    const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+    const int cgrid = (int)(cchunks < (uint64_t)max_blocks ? cchunks : (uint64_t)max_blocks);
+    rc = pcq_ensure_partials(ctx, (size_t)grid);
+    if (rc) return rc;
+    bool had_boxes, had_hist;
+    DevPred boxes_only = dp;
+    boxes_only.empty = 1;
+    rc = ensure_boxes(ctx, ix, cols, chunks, grid, boxes_only, s, &had_boxes);
+    if (!rc) rc = ensure_hist(ix, cols, cchunks, cgrid, s, &had_hist);
+    if (rc) return rc;
+    ix->last = pcq_index_stats{};
+    ix->last.chunks = chunks;
+    ix->last.built = !had_boxes || !had_hist;
+    ix->stats_stream = s;  // completed by pcq_index_get_stats: no sync on the scan path
+    if (c->kind != COLL_COUNT) {
+        ix->stats_kind = 3;  // classified from the index when asked for
+        ix->stats_pred = dp;
+        EmitIndex eix = {};
+        eix.boxes = reinterpret_cast<const int32_t *>(ix->d_boxes);
+        eix.hist = ix->d_hist;
+        eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
+        return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+    }
+    ix->stats_kind = 0;
+    c->last_stream = s;
+    PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_index_count_bounds_class, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
+                       cols->n, chunks, dp, ix->d_boxes, ix->d_hist, ctx->d_partials, ix->d_stats);
+    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    PCQ_HIP(hipGetLastError());
+    const uint64_t rest_first = chunks * CHUNK_POINTS;
+    if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS class bytes
+        pcq_columns tail = *cols;
+        tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
+        tail.cls = (const uint8_t *)cols->cls + rest_first;
+        tail.cls_stride = 1;
         tail.rgb = nullptr;
         tail.n = cols->n - rest_first;
         return pcq_scan_dev(ctx, &tail, pred, c, stream);

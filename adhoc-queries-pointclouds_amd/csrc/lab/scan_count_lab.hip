@@ -1024,17 +1024,9 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         const int src = pcq_scratch_stream(ctx, s);
         if (src) return src;
     }
-    if (nsegments > ctx->segments_cap) {
-        if (ctx->d_segments) (void)hipFree(ctx->d_segments);
-        if (ctx->h_segments) (void)hipHostFree(ctx->h_segments);
-        ctx->d_segments = nullptr;
-        ctx->h_segments = nullptr;
-        ctx->segments_cap = 0;
-        ctx->segments_uploaded = 0;
-        size_t cap = nsegments < 64 ? 64 : nsegments;
-        PCQ_HIP(hipMalloc((void **)&ctx->d_segments, cap * sizeof(DevSegment)));
-        PCQ_HIP(hipHostMalloc((void **)&ctx->h_segments, cap * sizeof(DevSegment), hipHostMallocDefault));
-        ctx->segments_cap = cap;
+    {
+        const int trc = pcq_ensure_segment_table(ctx, nsegments * sizeof(DevSegment));
+        if (trc) return trc;
     }
     static_assert(sizeof(DevClassSegment) <= sizeof(DevSegment), "the two segment tables share one buffer");
     const int kind = preds[0].kind;

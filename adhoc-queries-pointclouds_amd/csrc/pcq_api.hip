@@ -223,6 +223,23 @@ int pcq_ensure_partials(pcq_ctx *ctx, size_t n) {
     return PCQ_OK;
 }
 
+// The segment tables of the batched count kernels (DevSegment, DevClassSegment, DevCombinedSegment) share one pinned buffer
+// and its device twin, sized in bytes.
+int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes) {
+    if (bytes <= ctx->segments_cap) return PCQ_OK;
+    if (ctx->d_segments) (void)hipFree(ctx->d_segments);
+    if (ctx->h_segments) (void)hipHostFree(ctx->h_segments);
+    ctx->d_segments = nullptr;
+    ctx->h_segments = nullptr;
+    ctx->segments_cap = 0;
+    ctx->segments_uploaded = 0;
+    const size_t cap = bytes < 64 * sizeof(DevCombinedSegment) ? 64 * sizeof(DevCombinedSegment) : bytes;
+    PCQ_HIP(hipMalloc((void **)&ctx->d_segments, cap));
+    PCQ_HIP(hipHostMalloc((void **)&ctx->h_segments, cap, hipHostMallocDefault));
+    ctx->segments_cap = cap;
+    return PCQ_OK;
+}
+
 extern "C" int pcq_get_device_info(pcq_ctx *ctx, pcq_device_info *out) {
     if (!ctx || !out) return pcq_fail(PCQ_ERR_ARG, "pcq_get_device_info: null argument");
     memset(out, 0, sizeof *out);

@@ -99,6 +99,19 @@ struct DevClassSegment {
     uint32_t _pad;
 };
 
+// One segment of a batched box AND class count launch (scan_count_combined.hip): DevSegment with the class block beside it.
+// Tables of these live in the same d_segments / h_segments buffers at their own pitch.
+struct DevCombinedSegment {
+    const int4 *xyz;       // 16-byte aligned positions block
+    const uint8_t *cls;    // classification block of the same points, any alignment
+    uint64_t n;            // points
+    uint64_t tile_begin;   // first global step of this segment
+    int32_t lo[3];
+    uint32_t width[3];
+    int32_t empty;
+    uint32_t pat;          // class byte replicated x4
+};
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -117,7 +130,7 @@ struct DevGrid {
 // at point 0.  Tiles from `covered_tiles` on (the ragged tail) are always counted.
 struct EmitIndex {
     const int32_t *boxes;    // bounds: {mn[3], mx[3]} per chunk (integer AABB), or nullptr
-    const uint32_t *hist;    // class: 256 bins per chunk, or nullptr
+    const uint32_t *hist;    // class: 256 bins per chunk, or nullptr   (box AND class: both)
     uint64_t covered_tiles;
 };
 enum { CHUNK_SCAN = 0, CHUNK_NONE = 1, CHUNK_ALL = 2 };  // straddling: read it · disjoint: no match · contained: every point matches
@@ -136,6 +149,12 @@ __device__ __forceinline__ int index_box_state(const int32_t (&mn)[3], const int
 // A class chunk of `points` points whose histogram bin for the predicate's class is `bin`.
 __device__ __forceinline__ int index_class_state(uint32_t bin, uint64_t points) {
     return bin == 0 ? CHUNK_NONE : ((uint64_t)bin == points ? CHUNK_ALL : CHUNK_SCAN);
+}
+// Box AND class: a bounds chunk's box state with the state of the class chunk it lies in.  Nothing matches where either
+// part has no match, every point matches only where both say so, and everything else is read.
+__device__ __forceinline__ int index_combined_state(int box_state, int class_state) {
+    if (box_state == CHUNK_NONE || class_state == CHUNK_NONE) return CHUNK_NONE;
+    return box_state == CHUNK_ALL && class_state == CHUNK_ALL ? CHUNK_ALL : CHUNK_SCAN;
 }
 
 constexpr uint64_t PCQ_EMPTY_KEY = ~0ull;
@@ -212,7 +231,7 @@ struct pcq_ctx {
     // segment table for batched launches
     DevSegment *d_segments = nullptr;
     DevSegment *h_segments = nullptr;
-    size_t segments_cap = 0;
+    size_t segments_cap = 0;            // BYTES of each of the two buffers (the tables of the batched kernels differ in pitch)
     size_t segments_uploaded = 0;       // number of segments of the table currently in d_segments (0 = none)
     int segments_kind = -1;             // predicate kind of the uploaded table
     // device-memory pool (pcq_pool_alloc / pcq_pool_free): the grid collector's tuple runs, partition buffers and
@@ -303,6 +322,8 @@ int pcq_scratch_stream(pcq_ctx *ctx, hipStream_t s);
 // stream of the collector's last scan unless that is `s` (whose order the caller's next operation keeps anyway)
 int pcq_collector_wait_last(const pcq_collector *c, hipStream_t s);
 int pcq_ensure_partials(pcq_ctx *ctx, size_t n);
+// pcq_api.hip: d_segments / h_segments hold at least `bytes` each (a table that grows forgets the uploaded one)
+int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes);
 
 // scan_count.hip
 int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,

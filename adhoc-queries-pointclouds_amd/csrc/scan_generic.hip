@@ -171,17 +171,21 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
 // empty match bits, a contained one 2048 and full bits (only whole tiles are covered), neither reads a position or class byte
 // nor parks anything; the emit pass then skips the first and builds the records of the second as always.  Every other tile is
 // counted as without the index.
-enum { INDEX_NONE = 0, INDEX_BOUNDS = 1, INDEX_CLASS = 2 };
+// INDEX_BOUNDS_CLASS (PCQ_PRED_BOUNDS_CLASS, pcq_scan_dev_indexed_combined): both parts, combined by index_combined_state.
+enum { INDEX_NONE = 0, INDEX_BOUNDS = 1, INDEX_CLASS = 2, INDEX_BOUNDS_CLASS = 3 };
 template <int IDX>
 __device__ __forceinline__ int tile_index_state(const EmitIndex &ix, const DevPred &pr, uint64_t n, uint64_t tile) {
     if (tile >= ix.covered_tiles) return CHUNK_SCAN;
-    if (IDX == INDEX_BOUNDS) {
+    int box_state = CHUNK_ALL;
+    if (IDX == INDEX_BOUNDS || IDX == INDEX_BOUNDS_CLASS) {
         const int32_t *b = ix.boxes + (tile >> 1) * 6;  // 4096-point chunk = tiles 2c, 2c + 1
         const int32_t mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
-        return index_box_state(mn, mx, pr);
+        box_state = index_box_state(mn, mx, pr);
+        if (IDX == INDEX_BOUNDS) return box_state;
     }
     const uint64_t ch = tile >> 5, first = ch * INDEX_CLASS_CHUNK;  // 65536-point chunk = tiles 32c .. 32c + 31
-    return index_class_state(ix.hist[ch * 256 + (pr.cls & 255u)], n - first < INDEX_CLASS_CHUNK ? n - first : INDEX_CLASS_CHUNK);
+    const int class_state = index_class_state(ix.hist[ch * 256 + (pr.cls & 255u)], n - first < INDEX_CLASS_CHUNK ? n - first : INDEX_CLASS_CHUNK);
+    return IDX == INDEX_CLASS ? class_state : index_combined_state(box_state, class_state);
 }
 
 template <int KIND, bool RGB, int IDX = INDEX_NONE>
@@ -564,6 +568,8 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
         else hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS, false, INDEX_BOUNDS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     } else if (ix && pred.kind == PCQ_PRED_CLASS && ix->hist)
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false, INDEX_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
+    else if (ix && pred.kind == PCQ_PRED_BOUNDS_CLASS && ix->boxes && ix->hist)
+        hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_CLASS, false, INDEX_BOUNDS_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_TIME) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_TIME, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});
     else if (pred.kind == PCQ_PRED_BOUNDS_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});

@@ -329,3 +329,21 @@ extern "C" int pcq_query_resident_count_class(pcq_host_resident *r, uint8_t cls,
     if (!r || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     return done(r->ds->count_class(cls, matches, points_scanned));
 }
+extern "C" int pcq_query_resident_count_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
+                                                     uint64_t *matches, uint64_t *points_scanned) {
+    if (!r || !bmin || !bmax || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);
+    if (!st.ok()) return done(st);
+    return done(r->ds->count_bounds_class(b, cls, matches, points_scanned));
+}
+extern "C" int pcq_query_resident_search_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
+                                                      pcq_host_collector *c) {
+    if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);  // PCQ_ERR_PANIC for min > max
+    if (!st.ok()) return done(st);
+    st = resident_collector_ok(r, c);
+    if (!st.ok()) return done(st);
+    return done(r->ds->search_bounds_class(b, cls, *c->c));
+}

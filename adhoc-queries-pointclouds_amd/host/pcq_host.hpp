@@ -388,9 +388,11 @@ public:
     static Status load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points = false);
     Status count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
+    Status count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
+    Status search_bounds_class(const AABB &bounds, uint8_t cls, ResultCollector &rc);
     // chunk-index statistics of the last search_*, summed over the files it scanned through the index
     Status last_stats(pcq_index_stats *out);
     size_t files() const { return files_.size(); }

@@ -11,6 +11,9 @@
 // file by file into one collector.  A count or buffer collector goes through each file's chunk index (pcq_scan_dev_indexed):
 // its first query of a kind builds the index, later ones read only the chunks that straddle the box.  A grid collector goes
 // through pcq_scan_dev; its pass 0 does not consult the index.
+//
+// Box AND class (count_bounds_class / search_bounds_class): both blocks of a file lie in HBM side by side, so the count is one
+// pcq_scan_dev_count_batch_combined and the search goes through both parts of the file's index (pcq_scan_dev_indexed_combined).
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -123,6 +126,35 @@ Status ResidentDataset::count_class(uint8_t cls, uint64_t *matches, uint64_t *po
     return run(cols, preds, matches);
 }
 
+// `--combine --bounds --class` over the dataset, count only: the prologue of count_bounds per file, then one batched launch
+// over the positions and classification blocks of the surviving files (pcq_scan_dev_count_batch_combined).
+Status ResidentDataset::count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
+    std::vector<pcq_columns> cols;
+    std::vector<pcq_predicate> preds;
+    uint64_t scanned = 0;
+    for (const auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_BOUNDS_CLASS;
+        pred.cls = cls;
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
+        pcq_columns c{};
+        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
+        c.cls = f.cls, c.cls_stride = 1;
+        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
+        cols.push_back(c);
+        preds.push_back(pred);
+        scanned += c.n;
+    }
+    if (points_scanned) *points_scanned = scanned;
+    int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
+    if (!rc && !cols.empty()) rc = pcq_scan_dev_count_batch_combined(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
+    if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
+    return Status::FromLib(rc);
+}
+
 // One file of search_bounds / search_class: execute_plan (search.cpp) with the resident blocks in place of the file.
 Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc) {
     const uint64_t n = f.header.number_of_points;
@@ -141,7 +173,8 @@ Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultC
             r = pcq_index_new(ctx_, &f.index);
             if (r) return Status::FromLib(r);
         }
-        r = pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
+        r = pred.kind == PCQ_PRED_BOUNDS_CLASS ? pcq_scan_dev_indexed_combined(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
+                                               : pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
         if (!r) last_indices_.push_back(f.index);
     }
     rc.next_index += n;
@@ -177,6 +210,26 @@ Status ResidentDataset::search_class(uint8_t cls, ResultCollector &rc) {
         pcq_predicate pred{};
         pred.kind = PCQ_PRED_CLASS;
         pred.cls = cls;  // :259-262 whole byte
+        Status st = scan(f, pred, rc);
+        if (!st.ok()) return st;
+    }
+    return Status::Ok();
+}
+
+// The combined search of search.cpp (DESIGN §8 "Combined searches") for every file: the prologue of search_bounds, then box
+// AND class in one scan — through both parts of the file's chunk index for count and buffer collectors.
+Status ResidentDataset::search_bounds_class(const AABB &bounds, uint8_t cls, ResultCollector &rc) {
+    if (!with_points_ && rc.has_points())
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
+    last_indices_.clear();
+    for (auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_BOUNDS_CLASS;
+        pred.cls = cls;
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
         Status st = scan(f, pred, rc);
         if (!st.ok()) return st;
     }

@@ -241,6 +241,12 @@ int pcq_prepare_host_scans(pcq_ctx *ctx);
  * *device_total.  PCQ_PRED_TIME, PCQ_PRED_BOUNDS_CLASS and PCQ_PRED_BOUNDS_TIME are refused (PCQ_ERR_ARG). */
 int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
                              size_t nsegments, uint64_t *device_total, void *stream);
+/* The same for box AND class: every predicate is PCQ_PRED_BOUNDS_CLASS, and segment i — packed positions (xyz_stride 12,
+ * 16-byte aligned) beside the packed class bytes of the same points (cls_stride 1, any alignment, non-null when n > 0) — is
+ * counted with the box and the class byte of preds[i]; the total is ADDED to *device_total.  nsegments == 0 is PCQ_OK.  Any
+ * other predicate kind or layout is refused (PCQ_ERR_ARG) before anything is launched. */
+int pcq_scan_dev_count_batch_combined(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
+                                      size_t nsegments, uint64_t *device_total, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step
@@ -275,6 +281,18 @@ int pcq_index_free(pcq_index *ix);
 int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out);
 int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
                          pcq_collector *c, void *stream);
+/* PCQ_PRED_BOUNDS_CLASS (only; other kinds PCQ_ERR_ARG) through BOTH parts of the same index object, count and buffer
+ * collectors (grid: PCQ_ERR_ARG).  Parts an earlier pcq_scan_dev_indexed built for these columns are used as they are, a
+ * missing part is built first and serves later pcq_scan_dev_indexed bounds / class scans; then the pruned pass runs, on the
+ * building call too.  A 4096-point bounds chunk takes its box state together with the state of the 65536-point class chunk
+ * it lies in: no match in either -> skipped, nothing read; both contained -> counted whole, nothing read; everything else ->
+ * its positions and its 4096 class bytes are read.  Results and records are pcq_scan_dev's for PCQ_PRED_BOUNDS_CLASS, byte
+ * for byte and in order; the ragged tail behind the last whole bounds chunk is always read.  Covered: packed positions,
+ * 16-byte aligned, at least 4096 points, with packed non-null class bytes; any other layout falls through to pcq_scan_dev with
+ * all-zero statistics and leaves the index untouched.  Statistics in bounds chunks: chunks = n / 4096 = skipped + whole +
+ * scanned, built = 1 when this call built either part. */
+int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                                  pcq_collector *c, void *stream);
 
 /* The one collective of the path (main.rs:164-180) for callers that drive n GPUs from ONE process:
  * recv[i][0] = the sum over i of send[i][0] (8 bytes each in ctxs[i]'s HBM, e.g. the counter of

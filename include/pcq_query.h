@@ -94,6 +94,11 @@ int pcq_query_resident_free(pcq_host_resident *r);
 int pcq_query_resident_count_bounds(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint64_t *matches,
                                     uint64_t *points_scanned);
 int pcq_query_resident_count_class(pcq_host_resident *r, uint8_t cls, uint64_t *matches, uint64_t *points_scanned);
+/* Box AND class, count only (`--combine --bounds ... --class`): the per-file prologue of the bounds count (header early-out,
+ * box conversion; PCQ_ERR_PANIC for min > max) + ONE batched launch over the positions and classification blocks of the
+ * surviving files (pcq_scan_dev_count_batch_combined).  points_scanned: the points of the files whose headers meet the box. */
+int pcq_query_resident_count_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
+                                          uint64_t *matches, uint64_t *points_scanned);
 /* Point and density queries over a resident dataset: the per-file searches over every loaded file, in load order, into ONE
  * collector.  Count and buffer collectors go through each file's chunk index (pcq_scan_dev_indexed: the first query of a
  * kind builds it, later ones read only the chunks that straddle the box); grid collectors through pcq_scan_dev, unpruned.
@@ -107,6 +112,12 @@ int pcq_query_resident_load_points(int device, const char *const *files, size_t 
 int pcq_query_resident_search_bounds(pcq_host_resident *r, const double bmin[3], const double bmax[3], pcq_host_collector *c);
 /* == pcq_query_search_file_class(path, cls, optimized=1, c) for every loaded file, in load order. */
 int pcq_query_resident_search_class(pcq_host_resident *r, uint8_t cls, pcq_host_collector *c);
+/* == pcq_query_search_file_bounds_class(path, bmin, bmax, cls, optimized=1, c) for every loaded file, in load order, the
+ * header early-out included.  Count and buffer collectors go through both parts of each file's chunk index
+ * (pcq_scan_dev_indexed_combined: the parts are those of search_bounds and search_class, built by whichever comes first);
+ * grid collectors through pcq_scan_dev. */
+int pcq_query_resident_search_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
+                                           pcq_host_collector *c);
 /* Index statistics of the last resident search, summed over its files (those it scanned through an index; none for a grid
  * collector).  Waits for the search's scans. */
 int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out);

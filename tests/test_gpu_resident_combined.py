@@ -1,0 +1,340 @@
+"""host/resident.cpp: box AND class over a dataset kept in HBM.  pcq_query_resident_count_bounds_class (one batched launch)
+and pcq_query_resident_search_bounds_class (file by file through both parts of each file's chunk index) must equal the
+per-file combined searches (pcq_query_search_file_bounds_class, --optimized) over the same files, in load order, into one
+collector — the count, the records byte for byte and in order, the grid cells and their winners — and the oracle fed the
+same files."""
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+specs = importlib.import_module("adhoc-queries-pointclouds_amd.synth_specs")
+POINT_DTYPE = pkg.POINT_DTYPE
+PCQ_ERR_ARG, PCQ_ERR_PANIC = -8, -7
+QUERY_BOUNDS_CLASS = 3  # the oracle's query kind
+
+
+class IndexStats(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("skipped", C.c_uint64), ("whole", C.c_uint64), ("scanned", C.c_uint64), ("built", C.c_uint64)]
+
+
+class Q:
+    """ctypes view of the parts of include/pcq_query.h used here"""
+
+    def __init__(self):
+        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
+        dd = P(C.c_double)
+        lib.pcq_query_last_error.restype = C.c_char_p
+        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
+        lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, P(vp)]
+        lib.pcq_query_collector_new_grid.argtypes = [C.c_int, dd, dd, C.c_double, P(vp)]
+        lib.pcq_query_collector_free.argtypes = [vp]
+        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
+        lib.pcq_query_collector_points.argtypes = [vp, vp, u64, P(u64)]
+        lib.pcq_query_collector_grid_cells.argtypes = [vp, vp, u64, P(u64)]
+        lib.pcq_query_search_file_bounds_class.argtypes = [C.c_char_p, dd, dd, C.c_uint8, C.c_int, vp]
+        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
+        lib.pcq_query_resident_load_points.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
+        lib.pcq_query_resident_free.argtypes = [vp]
+        lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
+        lib.pcq_query_resident_search_class.argtypes = [vp, C.c_uint8, vp]
+        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
+        lib.pcq_query_resident_search_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, vp]
+        lib.pcq_query_resident_last_stats.argtypes = [vp, P(IndexStats)]
+
+    @staticmethod
+    def d3(v):
+        return (C.c_double * 3)(*[float(x) for x in v])
+
+    def err(self):
+        return self.lib.pcq_query_last_error()
+
+    def collector(self, kind, grid=None, device=0):
+        h = C.c_void_p()
+        if kind == "count":
+            rc = self.lib.pcq_query_collector_new_count(device, C.byref(h))
+        elif kind == "buffer":
+            rc = self.lib.pcq_query_collector_new_buffer(device, C.byref(h))
+        else:
+            rc = self.lib.pcq_query_collector_new_grid(device, self.d3(grid[0]), self.d3(grid[1]), grid[2], C.byref(h))
+        assert rc == 0, self.err()
+        return h
+
+    def result(self, h, kind):
+        """count, or the records (buffer: file order), or (sorted cell keys, winners in key order)"""
+        n = C.c_uint64()
+        assert self.lib.pcq_query_collector_point_count(h, C.byref(n)) == 0, self.err()
+        if kind == "count":
+            return n.value
+        assert self.lib.pcq_query_collector_points(h, None, 0, C.byref(n)) == 0
+        pts = np.zeros(n.value, dtype=POINT_DTYPE)
+        if n.value:
+            assert self.lib.pcq_query_collector_points(h, pts.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
+        if kind == "buffer":
+            return pts.tobytes()
+        assert self.lib.pcq_query_collector_grid_cells(h, None, 0, C.byref(n)) == 0
+        keys = np.zeros(n.value, dtype=np.uint64)
+        if n.value:
+            assert self.lib.pcq_query_collector_grid_cells(h, keys.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
+        order = np.argsort(keys, kind="stable")
+        return keys[order].tobytes(), pts[order].tobytes()
+
+    def load(self, paths, points=True, device=0):
+        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+        h = C.c_void_p()
+        fn = self.lib.pcq_query_resident_load_points if points else self.lib.pcq_query_resident_load
+        rc = fn(device, arr, len(paths), C.byref(h))
+        return rc, h
+
+    def stats(self, r):
+        st = IndexStats()
+        assert self.lib.pcq_query_resident_last_stats(r, C.byref(st)) == 0, self.err()
+        return {k: getattr(st, k) for k, _ in IndexStats._fields_}
+
+    def count(self, r, bmin, bmax, cls):
+        m, s = C.c_uint64(12345), C.c_uint64(12345)
+        rc = self.lib.pcq_query_resident_count_bounds_class(r, self.d3(bmin), self.d3(bmax), cls, C.byref(m), C.byref(s))
+        assert rc == 0, self.err()
+        return m.value, s.value
+
+
+# LAST field blocks of formats 0-3 (offset in the record, bytes): each is n x size bytes at offset_to_point_data + n x offset
+FIELDS = {0: [(0, 12), (12, 2), (14, 1), (15, 1), (16, 1), (17, 1), (18, 2)]}
+FIELDS[1] = FIELDS[0] + [(20, 8)]
+FIELDS[2] = FIELDS[0] + [(20, 6)]
+FIELDS[3] = FIELDS[0] + [(20, 8), (28, 6)]
+CLASS_MIX = [(1, 0.4), (2, 0.3), (6, 0.2), (134, 0.1)]
+
+
+@pytest.fixture(scope="module")
+def q():
+    return Q()
+
+
+@pytest.fixture(scope="module")
+def files(oracle, tmp_path_factory):
+    """LAST files of formats 0-3, and one (format 2, with colour) whose point blocks are permuted into x order."""
+    d = tmp_path_factory.mktemp("resident_combined")
+    out = []
+    for fmt in (0, 1, 2, 3):
+        spec = specs._spec(9300 + fmt, 70_001 + 13 * fmt, fmt, (0.01, 0.02, 0.05), (100.0, -200.0, 7.5), (-5000, -5000, -1000),
+                           (10001, 10001, 2001), classes=CLASS_MIX)
+        p = str(d / f"f{fmt}.last")
+        oracle.synth_write(spec, p)
+        out.append(p)
+    spec = specs._spec(9400, 400_009, 2, (0.01, 0.02, 0.05), (100.0, -200.0, 7.5), (-5000, -5000, -1000), (10001, 10001, 2001),
+                       classes=CLASS_MIX)
+    img = oracle.synth_image(spec, transposed=True).copy()
+    hdr = oracle.parse_header(img[:400].tobytes())
+    n, otp = hdr.number_of_points, hdr.offset_to_point_data
+    xyz = img[otp:otp + 12 * n].view(np.int32).reshape(n, 3)
+    order = np.argsort(xyz[:, 0], kind="stable")
+    for off, size in FIELDS[2]:
+        blk = img[otp + n * off: otp + n * (off + size)].reshape(n, size)
+        img[otp + n * off: otp + n * (off + size)] = blk[order].reshape(-1)
+    p = str(d / "sorted_x.last")
+    img.tofile(p)
+    out.append(p)
+    return out
+
+
+POINTS = [70_001, 70_014, 70_027, 70_040, 400_009]
+BOXES = [((90.0, -250.0, 0.0), (120.0, -150.0, 20.0)), ((0.0, -400.0, -100.0), (200.0, 0.0, 100.0)),
+         ((149.99, -400.0, -100.0), (150.0, 0.0, 100.0)), ((500.0, 500.0, 500.0), (600.0, 600.0, 600.0)),
+         ((60.0, -300.0, -100.0), (61.0, -100.0, 200.0)),        # a thin x slab
+         ((-1e12, -1e12, -1e12), (1e12, 1e12, 1e12))]
+SLAB = BOXES[4]
+CLASSES = [2, 134, 19]
+GRID = ((40.0, -320.0, -60.0), (160.0, -80.0, 120.0))
+
+
+def oracle_result(oracle, paths, kind, box, cls, grid=None):
+    oc = {"count": oracle.count_collector, "buffer": oracle.buffer_collector, "grid": lambda: oracle.grid_collector(*grid)}[kind]()
+    for path in paths:
+        assert oracle.search_file(path, QUERY_BOUNDS_CLASS, box[0], box[1], cls, oc)[0] == 0
+    if kind == "count":
+        out = oc.point_count()
+    elif kind == "buffer":
+        out = oc.points().tobytes()
+    else:
+        out = (oc.grid_cells().tobytes(), oc.points().tobytes())
+    oc.free()
+    return out
+
+
+def per_file(q, paths, kind, box, cls, grid=None):
+    h = q.collector(kind, grid)
+    for path in paths:
+        assert q.lib.pcq_query_search_file_bounds_class(path.encode(), q.d3(box[0]), q.d3(box[1]), cls, 1, h) == 0, q.err()
+    out = q.result(h, kind)
+    q.lib.pcq_query_collector_free(h)
+    return out
+
+
+def resident(q, r, kind, box, cls, grid=None):
+    h = q.collector(kind, grid)
+    assert q.lib.pcq_query_resident_search_bounds_class(r, q.d3(box[0]), q.d3(box[1]), cls, h) == 0, q.err()
+    out = q.result(h, kind)
+    q.lib.pcq_query_collector_free(h)
+    return out
+
+
+@pytest.fixture(scope="module")
+def expected(oracle, q, files):
+    """The per-file searches and the oracle, once per (box, class, collector)."""
+    out = {}
+    for bi, box in enumerate(BOXES):
+        for cls in CLASSES:
+            for kind, grid in [("count", None), ("buffer", None), ("grid", GRID + (2.0,))]:
+                want = per_file(q, files, kind, box, cls, grid)
+                assert want == oracle_result(oracle, files, kind, box, cls, grid), (box, cls, kind)
+                out[bi, cls, kind] = want
+    return out
+
+
+def test_resident_count_equals_per_file_searches_and_oracle(q, files, expected):
+    rc, r = q.load(files, points=False)
+    assert rc == 0, q.err()
+    try:
+        for bi, box in enumerate(BOXES):
+            for cls in CLASSES:
+                for rep in range(2):  # (the second time the segment table is the one in HBM)
+                    matches, scanned = q.count(r, box[0], box[1], cls)
+                    assert matches == expected[bi, cls, "count"], (box, cls, rep)
+                    assert scanned == (0 if bi == 3 else sum(POINTS)), (box, cls)  # every header meets every box but the far one
+        assert any(expected[bi, 2, "count"] > 0 for bi in range(len(BOXES)))
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_points_scanned_counts_only_files_whose_header_meets_the_box(oracle, q, files, tmp_path):
+    """A file shifted far away in x (its header box with it) is skipped by the early-out: not counted, not scanned."""
+    spec = specs._spec(9500, 30_011, 2, (0.01, 0.02, 0.05), (5000.0, -200.0, 7.5), (-5000, -5000, -1000), (10001, 10001, 2001), classes=CLASS_MIX)
+    far = str(tmp_path / "far.last")
+    oracle.synth_write(spec, far)
+    paths = [files[0], far, files[2]]
+    rc, r = q.load(paths)
+    assert rc == 0, q.err()
+    try:
+        box = BOXES[1]
+        matches, scanned = q.count(r, box[0], box[1], 2)
+        assert scanned == POINTS[0] + POINTS[2]
+        assert matches == per_file(q, paths, "count", box, 2) == oracle_result(oracle, paths, "count", box, 2) > 0
+        for kind, grid in [("buffer", None), ("grid", GRID + (2.0,))]:  # the skipped file does not move the file-order index
+            got = resident(q, r, kind, box, 2, grid)
+            assert got == per_file(q, paths, kind, box, 2, grid) == oracle_result(oracle, paths, kind, box, 2, grid), kind
+        everything = BOXES[5]
+        matches, scanned = q.count(r, everything[0], everything[1], 6)
+        assert scanned == POINTS[0] + 30_011 + POINTS[2] and matches == per_file(q, paths, "count", everything, 6)
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_resident_search_equals_per_file_searches_and_oracle(q, files, expected):
+    rc, r = q.load(files)
+    assert rc == 0, q.err()
+    try:
+        for bi, box in enumerate(BOXES):
+            for cls in CLASSES:
+                for kind, grid in [("count", None), ("buffer", None), ("grid", GRID + (2.0,))]:
+                    for rep in range(2):  # the second time through the built indices
+                        assert resident(q, r, kind, box, cls, grid) == expected[bi, cls, kind], (box, cls, kind, rep)
+                        st = q.stats(r)
+                        if kind == "grid" or bi == 3:
+                            assert st["chunks"] == 0, st  # grid collectors, and files the early-out skipped, use no index
+                        else:
+                            assert st["chunks"] == sum(n // 4096 for n in POINTS) == st["skipped"] + st["whole"] + st["scanned"], st
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_thin_slab_on_the_x_ordered_file_skips_chunks(q, files, expected):
+    rc, r = q.load([files[4]])
+    assert rc == 0, q.err()
+    try:
+        want = per_file(q, [files[4]], "buffer", SLAB, 2)
+        assert len(want) > 0
+        for kind in ("buffer", "count"):
+            for rep in range(2):
+                got = resident(q, r, kind, SLAB, 2)
+                assert got == (want if kind == "buffer" else len(want) // 31)
+                st = q.stats(r)
+                assert st["built"] == (1 if (kind, rep) == ("buffer", 0) else 0) and st["chunks"] == POINTS[4] // 4096
+                assert st["skipped"] > 0.9 * st["chunks"] and st["skipped"] + st["whole"] + st["scanned"] == st["chunks"], st
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_index_parts_are_shared_across_the_host_entries(q, files):
+    """search_bounds builds the boxes, search_bounds_class the histograms beside them, search_class finds both there."""
+    paths = files[2:]
+    rc, r = q.load(paths)
+    assert rc == 0, q.err()
+    try:
+        box = BOXES[1]
+        hb = q.collector("count")
+        assert q.lib.pcq_query_resident_search_bounds(r, q.d3(box[0]), q.d3(box[1]), hb) == 0, q.err()
+        assert q.stats(r)["built"] == len(paths)
+        assert resident(q, r, "count", box, 2) == per_file(q, paths, "count", box, 2)
+        assert q.stats(r)["built"] == len(paths)  # the histograms
+        assert resident(q, r, "buffer", box, 6) == per_file(q, paths, "buffer", box, 6)
+        assert q.stats(r)["built"] == 0
+        hc = q.collector("count")
+        assert q.lib.pcq_query_resident_search_class(r, 2, hc) == 0, q.err()
+        assert q.stats(r)["built"] == 0
+        assert q.lib.pcq_query_resident_search_bounds(r, q.d3(box[0]), q.d3(box[1]), hb) == 0, q.err()
+        assert q.stats(r)["built"] == 0
+        want_b, want_c = C.c_uint64(), C.c_uint64()
+        for h, out in ((hb, want_b), (hc, want_c)):
+            assert q.lib.pcq_query_collector_point_count(h, C.byref(out)) == 0
+        # (the same searches on a dataset that has no combined part in its indices)
+        rc2, r2 = q.load(paths)
+        assert rc2 == 0, q.err()
+        hb2, hc2 = q.collector("count"), q.collector("count")
+        for _ in range(2):
+            assert q.lib.pcq_query_resident_search_bounds(r2, q.d3(box[0]), q.d3(box[1]), hb2) == 0
+        assert q.lib.pcq_query_resident_search_class(r2, 2, hc2) == 0
+        assert q.result(hb2, "count") == want_b.value > 0 and q.result(hc2, "count") == want_c.value > 0
+        for h in (hb, hc, hb2, hc2):
+            q.lib.pcq_query_collector_free(h)
+        q.lib.pcq_query_resident_free(r2)
+    finally:
+        q.lib.pcq_query_resident_free(r)
+
+
+def test_errors_and_skips(q, files):
+    rc, r = q.load(files)
+    assert rc == 0, q.err()
+    rc2, r2 = q.load(files, points=False)
+    assert rc2 == 0, q.err()
+    try:
+        hb, hg, hc = q.collector("buffer"), q.collector("grid", GRID + (2.0,)), q.collector("count")
+        box = BOXES[1]
+        # a dataset loaded for counts only serves count collectors
+        for h in (hb, hg):
+            assert q.lib.pcq_query_resident_search_bounds_class(r2, q.d3(box[0]), q.d3(box[1]), 2, h) == PCQ_ERR_ARG
+            assert b"without its colour blocks" in q.err()
+        assert q.lib.pcq_query_resident_search_bounds_class(r2, q.d3(box[0]), q.d3(box[1]), 2, hc) == 0, q.err()
+        assert q.result(hc, "count") == per_file(q, files, "count", box, 2)
+        # min > max panics like AABB::from_min_max (main.rs:80-91)
+        m, s = C.c_uint64(7), C.c_uint64(7)
+        assert q.lib.pcq_query_resident_search_bounds_class(r, q.d3((1, 1, 1)), q.d3((0, 2, 2)), 2, hb) == PCQ_ERR_PANIC
+        assert q.lib.pcq_query_resident_count_bounds_class(r, q.d3((1, 1, 1)), q.d3((0, 2, 2)), 2, C.byref(m), C.byref(s)) == PCQ_ERR_PANIC
+        assert q.result(hb, "buffer") == b""
+        # a box disjoint from every header
+        assert q.count(r, BOXES[3][0], BOXES[3][1], 2) == (0, 0)
+        assert resident(q, r, "buffer", BOXES[3], 2) == b""
+        for h in (hb, hg, hc):
+            q.lib.pcq_query_collector_free(h)
+    finally:
+        q.lib.pcq_query_resident_free(r)
+        q.lib.pcq_query_resident_free(r2)
