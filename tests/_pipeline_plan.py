@@ -1,0 +1,369 @@
+"""How deep the count kernels' software pipelines run for a given input, and inputs that tell one step from another.
+
+Every count kernel on the hot path is a persistent grid of one-wave workgroups with two register sets A and B:
+
+    load A(u); loop { load B(u + g); eval A; break if u + g is past the end;
+                      load A(u + 2g); eval B; break if u + 2g is past the end; u += 2g }
+
+so workgroup w of a grid of g takes the steps w, w + g, w + 2g, ...; its DEPTH is the length of that list.  Depth 1-2 uses
+each register set once; at 3 and 4 a set is reloaded while the other is in flight (the first point at which a counted
+s_waitcnt can be wrong); at 5 and 6 the loop-back has been taken twice and both exits — behind an A evaluation at odd depth,
+behind a B evaluation at even depth — are reached from the steady state.  A batched kernel numbers its steps across all
+segments and each register set carries a cursor (segment, base, class pattern or box) that must be refreshed when the
+workgroup's next step lies in another segment.
+
+This module restates the launch arithmetic (apart from the .hip files, cited below), derives each workgroup's step list and
+a report of what that schedule reaches, and builds STEP-CODED data: a background no query matches, and in step s exactly
+m(s) matches of query value s mod 3, m pairwise distinct over the steps of any one workgroup — a doubled, dropped or
+mis-addressed step moves a count by an amount no other single error cancels.  Expected values always come from numpy
+compares on the finished arrays (class_count, time_count, box_count below), never from m(s).
+
+Restated from (adhoc-queries-pointclouds_amd/csrc):
+  K1 family  scan_tiles.h:11-13 (256-point tiles, 2 per step, 3 waves per CU); scan_count.hip:66 (steps), :375-377 (grid);
+             collectors.hip:267 (the points peeled in front of the first 16-byte aligned one)
+  K2         scan_tiles.h:14-15 (4 loads of 1 KiB per step, 4 waves per CU); scan_count.hip:403-409 (head, nvec, grid), :312
+  K3         scan_time.hip:17-18 (4 loads per step, 4 waves per CU), :110-114 (head, nvec, grid), :63
+  batches    scan_count.hip:450-456 (class segments), :468-471 (bounds segments), :481-482 (grid), :131 / :242 (seek);
+             scan_count_combined.hip:167-171 (segments), :187-188 (grid), :34 (seek)
+"""
+from collections import Counter, namedtuple
+
+import numpy as np
+
+Family = namedtuple("Family", "name waves_per_cu step")
+K1 = Family("K1", 3, 512)   # step: points (the positions; a class byte or a time per point rides along)
+K2 = Family("K2", 4, 4096)  # step: class bytes behind the head
+K3 = Family("K3", 4, 512)   # step: times behind the head (256 vectors of two)
+
+CU_COUNTS = (64, 256, 304)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# launch arithmetic
+# ---------------------------------------------------------------------------------------------------------------------
+def full_grid(fam, cus):
+    return fam.waves_per_cu * cus
+
+
+def per_file_grid(fam, cus, steps):
+    return min(full_grid(fam, cus), steps + 1)
+
+
+def batch_grid(fam, cus, steps, nseg):
+    return min(full_grid(fam, cus), steps + nseg)
+
+
+def class_layout(addr, n):
+    """(head, nvec, steps) of a class block of n bytes at byte address addr."""
+    head = min((16 - addr % 16) % 16, n)
+    nvec = (n - head) // 16
+    return head, nvec, nvec // 256
+
+
+def time_layout(addr, n):
+    """(head, nvec, steps) of n times at the 8-byte aligned address addr (n > 0)."""
+    assert addr % 8 == 0 and n > 0
+    head = 1 if addr % 16 else 0
+    nvec = (n - head) // 2
+    return head, nvec, nvec // 256
+
+
+def k1_layout(addr, n):
+    """(peel, tiles, steps): the points in front of the first 16-byte aligned point, then K1's whole tiles and steps."""
+    assert addr % 4 == 0
+    peel = min(addr % 16 // 4, n)
+    tiles = (n - peel) // 256
+    return peel, tiles, tiles // 2
+
+
+def tile_begin(seg_steps):
+    """The first step of every segment: the running sum of the segments' whole steps."""
+    seg_steps = np.asarray(seg_steps, dtype=np.int64)
+    return np.cumsum(seg_steps) - seg_steps
+
+
+def deep_steps(g):
+    """Depths 6 (the first g // 3 workgroups) and 5."""
+    return 5 * g + g // 3
+
+
+def shallow_steps(g):
+    """Depths 4 and, for the last workgroup alone, 3."""
+    return 4 * g - 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# schedules
+# ---------------------------------------------------------------------------------------------------------------------
+class Schedule:
+    """steps[w]: workgroup w's steps in order; seg[w]: the segment of each (batches; else None)."""
+
+    def __init__(self, grid, total, steps, seg, seg_steps, seg_n):
+        self.grid, self.total, self.steps, self.seg, self.seg_steps, self.seg_n = grid, total, steps, seg, seg_steps, seg_n
+
+
+def schedule(grid, total_steps, seg_steps=None, seg_n=None):
+    """Each workgroup's ordered step list.  With seg_steps (whole steps per segment, in batch order; seg_n: elements per
+    segment) also each step's segment: the last one whose tile_begin is not past the step, as the kernels' seek finds it."""
+    steps = [np.arange(w, total_steps, grid, dtype=np.int64) for w in range(grid)]
+    seg = None
+    if seg_steps is not None:
+        assert int(np.sum(seg_steps)) == total_steps and len(seg_n) == len(seg_steps)
+        begin = tile_begin(seg_steps)
+        seg = [np.searchsorted(begin, u, side="right") - 1 for u in steps]
+        for u, s in zip(steps, seg):  # every step lies inside the steps of its segment
+            assert np.all((u >= begin[s]) & (u < begin[s] + np.asarray(seg_steps)[s]))
+    return Schedule(grid, total_steps, steps, seg, None if seg_steps is None else list(seg_steps), None if seg_n is None else list(seg_n))
+
+
+def depth_report(sch):
+    """What a schedule reaches.  depths: Counter of list lengths (idle workgroups: 0).  exit_a / exit_b: the largest depth
+    at which the loop is left behind an A evaluation (odd depth) / a B evaluation (even depth); both_exits_deep: both >= 5.
+    Batches: cross_into_b / cross_into_a — a workgroup's next step lies in another segment when the cursor of B (from an
+    even position of its list to an odd one) / of A (odd to even) seeks; skipped: the segments some workgroup's consecutive
+    steps jump over entirely, with skips_stepped (one that has whole steps), skips_zero_step (elements but no whole step)
+    and skips_empty (n = 0)."""
+    depths = Counter(len(u) for u in sch.steps)
+    odd = [d for d in depths if d % 2 == 1]
+    even = [d for d in depths if d and d % 2 == 0]
+    rep = {"depths": depths, "exit_a": max(odd, default=0), "exit_b": max(even, default=0)}
+    rep["both_exits_deep"] = rep["exit_a"] >= 5 and rep["exit_b"] >= 5
+    if sch.seg is not None:
+        into_a = into_b = False
+        skipped = set()
+        for s in sch.seg:
+            change = np.flatnonzero(s[1:] != s[:-1])  # position k: between the k-th and the (k + 1)-th step
+            into_b |= bool(np.any(change % 2 == 0))
+            into_a |= bool(np.any(change % 2 == 1))
+            for k in change:
+                skipped.update(range(int(s[k]) + 1, int(s[k + 1])))
+        rep.update(cross_into_a=into_a, cross_into_b=into_b, skipped=skipped,
+                   skips_stepped=any(sch.seg_steps[i] > 0 for i in skipped),
+                   skips_zero_step=any(sch.seg_steps[i] == 0 and sch.seg_n[i] > 0 for i in skipped),
+                   skips_empty=any(sch.seg_n[i] == 0 for i in skipped))
+    return rep
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the batch plan: seventeen segments carved from one buffer
+# ---------------------------------------------------------------------------------------------------------------------
+Seg = namedtuple("Seg", "steps rest phase tiny")  # rest: elements behind the whole steps; tiny: n = rest, whatever the head
+
+
+def batch_plan(g):
+    """Large, sub-step (n = 1 and n = 0 among them), large, ...: a stride of g jumps over the small ones.  No large size
+    is a multiple of g steps, so the crossings fall in both transitions; >= 5g + g // 3 steps in all; byte phases 0..15."""
+    big = [g + g // 3 + 1, g + g // 7 + 2, g - g // 5, g + g // 11 + 3, g + g // 4, g // 2 + 5]
+    plan = [Seg(big[0], 777, 5, False), Seg(0, 1, 15, True), Seg(3, 77, 9, False), Seg(0, 0, 0, True),
+            Seg(big[1], 4000, 1, False), Seg(0, 1000, 2, False),
+            Seg(big[2], 53, 3, False), Seg(0, 255, 4, False), Seg(1, 0, 6, False),
+            Seg(big[3], 2049, 7, False), Seg(0, 0, 0, True), Seg(2, 300, 8, False),
+            Seg(big[4], 15, 10, False), Seg(0, 17, 11, False),
+            Seg(big[5], 3001, 12, False), Seg(0, 31, 13, False), Seg(1, 4095, 14, False)]
+    assert sum(s.steps for s in plan) >= deep_steps(g) and sorted({s.phase for s in plan}) == list(range(16))
+    return plan
+
+
+EMPTY_BOX_SEGMENT = 2  # (bounds and combined batches) three steps between two large segments
+
+
+def class_segment_bytes(seg):
+    return seg.rest if seg.tiny else (16 - seg.phase) % 16 + K2.step * seg.steps + seg.rest
+
+
+def point_segment_points(seg):
+    return seg.rest if seg.tiny else K1.step * seg.steps + seg.rest % K1.step
+
+
+def carve(sizes, phases, unit=1):
+    """Byte offsets of pieces of `sizes` elements of `unit` bytes in one buffer, piece k at byte phase phases[k] of a
+    16-byte line, and the buffer's size."""
+    off, q = [], 0
+    for n, ph in zip(sizes, phases):
+        q = (q + 15) // 16 * 16 + ph
+        off.append(q)
+        q += n * unit
+    return off, q
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# step-coded data
+# ---------------------------------------------------------------------------------------------------------------------
+def planted(s, g):
+    """m(s): 1..37 by the step, plus 40 per turn of the grid — distinct along s, s + g, s + 2g, ..."""
+    s = np.asarray(s, dtype=np.int64)
+    return 1 + s % 37 + 40 * (s // g)
+
+
+def check_counts(s, m, g, nq, room):
+    """The properties the tests lean on: at least one match per step, no more than fit, and pairwise distinct counts over
+    the steps of any one workgroup (s mod g) for each query value (s mod nq)."""
+    s, m = np.asarray(s, dtype=np.int64), np.asarray(m, dtype=np.int64)
+    if len(s) == 0:
+        return
+    assert m.min() >= 1 and m.max() <= room, (int(m.min()), int(m.max()), room)
+    key = ((s % g) * nq + s % nq) * (int(m.max()) + 1) + m
+    assert len(np.unique(key)) == len(key), "two steps of one workgroup carry the same count for one query value"
+
+
+def plant(rng, g, nsteps, step_len, first_step=0, nq=3):
+    """(element index behind the head, query index) of the matches of steps first_step .. first_step + nsteps - 1 of a
+    body of nsteps x step_len elements: m(s) distinct random places in step s (a random start and a random odd stride
+    modulo the power-of-two step)."""
+    assert step_len & (step_len - 1) == 0
+    s = first_step + np.arange(nsteps, dtype=np.int64)
+    m = planted(s, g)
+    check_counts(s, m, g, nq, step_len)
+    start = rng.integers(0, step_len, nsteps)
+    odd = 2 * rng.integers(0, step_len // 2, nsteps) + 1
+    rep = np.repeat(np.arange(nsteps, dtype=np.int64), m)
+    j = np.arange(int(m.sum()), dtype=np.int64) - np.repeat(np.cumsum(m) - m, m)
+    return rep * step_len + (start[rep] + j * odd[rep]) % step_len, s[rep] % nq
+
+
+def _edges(rng, lo0, hi0, lo1, hi1):
+    """About a third of the elements of [lo0, hi0) and [lo1, hi1) — the head, and what lies behind the whole steps — and
+    always the first and the last of each."""
+    e = np.r_[lo0:hi0, lo1:hi1].astype(np.int64)
+    pick = rng.random(len(e)) < 0.3
+    for lo, hi in ((lo0, hi0), (lo1, hi1)):
+        if hi > lo:
+            pick[np.searchsorted(e, lo)] = pick[np.searchsorted(e, hi - 1)] = True
+    return e[pick]
+
+
+def class_file(rng, g, steps, head, rest, queries, background, first_step=0):
+    """head + 4096 * steps + rest class bytes: `background` values everywhere, m(s) bytes of queries[s mod nq] in step s,
+    and matches in the head and behind the last whole step (leftover vectors and tail bytes)."""
+    n = head + K2.step * steps + rest
+    a = rng.choice(np.asarray(background, dtype=np.uint8), n)
+    q = np.asarray(queries, dtype=np.uint8)
+    assert not set(q.tolist()) & set(int(b) for b in background)
+    idx, r = plant(rng, g, steps, K2.step, first_step, len(q))
+    a[head + idx] = q[r]
+    e = _edges(rng, 0, head, head + K2.step * steps, n)
+    a[e] = q[rng.integers(0, len(q), len(e))]
+    return a
+
+
+def _range_hits(ranges):
+    """Per range: its start, the last double below its end, its middle."""
+    return np.array([[a, np.nextafter(b, -np.inf), (a + b) / 2] for a, b in ranges])
+
+
+def _range_misses(ranges):
+    out = [-5.0, 1e9, np.nan, np.nan, np.inf, -np.inf]
+    for a, b in ranges:
+        out += [b, np.nextafter(a, -np.inf)]  # the end itself is no match
+    return np.array(out)
+
+
+def time_file(rng, g, steps, head, rest, ranges, first_step=0):
+    """head + 512 * steps + rest times: a background outside every range (NaN, infinities, each range's end and the double
+    below its start among it), m(s) times of ranges[s mod nq] in step s — on the start, just below the end, in the middle —
+    and matches in the head and behind the last whole step."""
+    n = head + K3.step * steps + rest
+    hits, misses = _range_hits(ranges), _range_misses(ranges)
+    for a, b in ranges:
+        assert not np.any((misses >= a) & (misses < b))
+    t = rng.choice(misses, n)
+    idx, r = plant(rng, g, steps, K3.step, first_step, len(ranges))
+    t[head + idx] = hits[r, rng.integers(0, 3, len(r))]
+    e = _edges(rng, 0, head, head + K3.step * steps, n)
+    t[e] = hits[rng.integers(0, len(ranges), len(e)), rng.integers(0, 3, len(e))]
+    return t
+
+
+class PointQueries:
+    """The boxes, classes and ranges of one positions file (or batch segment), shifted along x by `shift`.
+
+    box: what the combined queries ask.  sub[r] (inside box): where the matches of query value r lie, and nothing else —
+    the plain bounds queries.  inside (inside box, apart from every sub): the background that passes only the box; it
+    carries other_classes and times outside every range.  outside: boxes apart from `box`, for the background that passes
+    only the column; it carries the queried classes and times inside the ranges."""
+
+    def __init__(self, shift=0, classes=(2, 6, 9), other_classes=(1, 7), ranges=((100.0, 200.0), (300.0, 400.0), (500.0, 600.0)),
+                 more_outside=()):
+        x = shift
+        self.box = ([x - 1000, -1000, -1000], [x + 1000, 1000, 1000])
+        self.sub = [([x + 100 * r, 0, 0], [x + 100 * r + 50, 50, 50]) for r in range(len(classes))]
+        self.inside = ([x - 1000, -1000, -1000], [x - 1, 1000, 1000])
+        self.outside = [([x + 1001, -1000, -1000], [x + 3000, 1000, 1000]), ([x - 1000, -3000, -1000], [x + 1000, -1001, 1000]),
+                        ([x - 1000, -1000, 1001], [x + 1000, 1000, 3000])] + list(more_outside)
+        self.classes, self.other_classes, self.ranges = tuple(classes), tuple(other_classes), tuple(ranges)
+        assert not set(classes) & set(other_classes)
+
+
+def _uniform(rng, box, n):
+    lo, hi = box
+    return np.stack([rng.integers(lo[a], hi[a] + 1, n) for a in range(3)], axis=1).astype(np.int32)
+
+
+def points_file(rng, g, steps, peel, rest, q, first_step=0):
+    """(xyz, cls, t) of peel + 512 * steps + rest points.  In step s, m(s) points inside q.sub[s mod nq] with class
+    q.classes[s mod nq] and a time in q.ranges[s mod nq]: they pass both tests.  Every other point passes exactly one: half
+    lie in the box with a class and a time no query asks for, half outside it with a queried class and a time inside a range
+    — a verdict word left over from the other register set would let the first kind through."""
+    n = peel + K1.step * steps + rest
+    nq = len(q.classes)
+    hits, misses = _range_hits(q.ranges), _range_misses(q.ranges)
+    box_only = rng.random(n) < 0.5
+    xyz = _uniform(rng, q.inside, n)
+    where = rng.integers(0, len(q.outside), n)
+    for i, bx in enumerate(q.outside):
+        sel = ~box_only & (where == i)
+        xyz[sel] = _uniform(rng, bx, int(sel.sum()))
+    cls = np.where(box_only, rng.choice(np.asarray(q.other_classes, dtype=np.uint8), n), rng.choice(np.asarray(q.classes, dtype=np.uint8), n))
+    t = np.where(box_only, rng.choice(misses, n), hits[rng.integers(0, len(q.ranges), n), rng.integers(0, 3, n)])
+    idx, r = plant(rng, g, steps, K1.step, first_step, nq)
+    e = _edges(rng, 0, peel, peel + K1.step * steps, n)
+    idx, r = np.r_[peel + idx, e], np.r_[r, rng.integers(0, nq, len(e))]
+    for k in range(nq):
+        sel = idx[r == k]
+        xyz[sel] = _uniform(rng, q.sub[k], len(sel))
+    cls[idx] = np.asarray(q.classes, dtype=np.uint8)[r]
+    t[idx] = hits[r % len(q.ranges), rng.integers(0, 3, len(r))]
+    return xyz, cls.astype(np.uint8), t
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# expected values: plain numpy on the finished arrays
+# ---------------------------------------------------------------------------------------------------------------------
+def class_count(cls, c):
+    return int((cls == c).sum())
+
+
+def in_range(t, start, end):
+    return (t >= start) & (t < end)  # float64; NaN compares false
+
+
+def time_count(t, start, end):
+    return int(in_range(t, start, end).sum())
+
+
+def in_box(xyz, lmin, lmax):
+    """lmin <= (x, y, z) <= lmax per axis, in int64 (xyz: int32, or already widened by the caller)."""
+    x = np.asarray(xyz, dtype=np.int64)
+    sel = np.ones(len(x), dtype=bool)
+    for a in range(3):
+        sel &= (x[:, a] >= int(lmin[a])) & (x[:, a] <= int(lmax[a]))
+    return sel
+
+
+def box_count(xyz, lmin, lmax):
+    return int(in_box(xyz, lmin, lmax).sum())
+
+
+def walk(sch, per_step, skip_b_from=None, eval_tail_prefetch=False):
+    """The kernels' loop walked over a schedule: the sum of per_step[u] (the matches of step u) over every workgroup's
+    list.  Two faults for the CPU test, to show that step-coded counts do not cancel: skip_b_from = d drops the B
+    evaluations from depth d on; eval_tail_prefetch counts every workgroup's clamped last prefetch, its last step again."""
+    total = 0
+    for u in sch.steps:
+        for k, s in enumerate(u):
+            if skip_b_from is not None and k % 2 == 1 and k + 1 >= skip_b_from:
+                continue
+            total += int(per_step[s])
+        if eval_tail_prefetch and len(u):
+            total += int(per_step[u[-1]])
+    return total
