@@ -215,6 +215,7 @@ def load_library() -> C.CDLL:
         "pcq_index_get_stats": (C.c_int, [vp, P(IndexStats)]),
         "pcq_scan_dev_indexed": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
         "pcq_scan_dev_indexed_combined": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
+        "pcq_scan_dev_indexed_time": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
         "pcq_device_alloc": (C.c_int, [vp, u64, P(vp)]),
         "pcq_device_free": (C.c_int, [vp, vp]),
         "pcq_copy_to_device": (C.c_int, [vp, vp, vp, u64]),
@@ -470,6 +471,11 @@ class Context:
         """Box AND class through both parts of the chunk index (boxes and class histograms)."""
         _check(self.lib.pcq_scan_dev_indexed_combined(self.handle, C.byref(cols), C.byref(pred), C.c_void_p(ix), coll.handle,
                                                       C.c_void_p(stream)))
+
+    def scan_dev_indexed_time(self, cols: Columns, pred: Predicate, ix: int, coll: Collector, stream: Optional[int] = None) -> None:
+        """GPS time in [start, end) through the time part of the chunk index (min, max and NaN count per 4096 times)."""
+        _check(self.lib.pcq_scan_dev_indexed_time(self.handle, C.byref(cols), C.byref(pred), C.c_void_p(ix), coll.handle,
+                                                  C.c_void_p(stream)))
 
     def synth_fill(self, spec: SynthSpec, first: int, count: int, d_xyz: Optional[int], d_cls: Optional[int],
                    stream: Optional[int] = None) -> None:

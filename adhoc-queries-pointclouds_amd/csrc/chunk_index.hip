@@ -12,6 +12,10 @@
 //     mask-algebra tile kernel as K1 (scan_count.hip).
 //   * class: the first class scan writes a 256-bin histogram per 65536-point chunk; later class
 //     counts are sums of one bin per chunk and read no classification bytes at all.
+//   * time (pcq_scan_dev_indexed_time): the first time scan writes the minimum and maximum of every 4096-point chunk's non-NaN
+//     GPS times and the number of its NaNs (24 B per 32 KiB of times).  Later time scans classify each chunk against
+//     [start, end) (index_time_state): a file in acquisition order is close to monotone in time, so all but a handful of chunks
+//     are disjoint.
 //   * buffer collectors (the records of the matches): the index is built the same way (boxes or histograms alone), then the
 //     emit of scan_generic.hip runs with its count pass taking each 2048-point tile's state from the index first
 //     (k_tile_counts with IDX): disjoint tiles and contained tiles are not read there, disjoint ones not by the emit either.
@@ -239,6 +243,117 @@ __global__ __launch_bounds__(BLOCK) void k_index_count_class(const uint32_t *__r
     if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
 }
 
+// ---- GPS time (pcq_scan_dev_indexed_time) ----------------------------------------------------------------------------------
+// A chunk's 4096 times are 2048 16-byte vectors of two times: eight loads per thread of a 256-thread block.
+constexpr int TIME_LOADS = (int)(CHUNK_POINTS / 2 / BLOCK);
+static_assert(TIME_LOADS * 2 * BLOCK == (int)CHUNK_POINTS, "a block reads a time chunk in whole loads");
+
+__device__ __forceinline__ double f64_of(int lo, int hi) {
+    return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+}
+__device__ __forceinline__ bool in_range(double t, double t0, double t1) { return (t >= t0) & (t < t1); }  // (scan_time.hip)
+__device__ __forceinline__ void load_time_chunk(v4i (&v)[TIME_LOADS], const v4i *__restrict__ base, uint64_t ch) {
+    const v4i *p = base + ch * (CHUNK_POINTS / 2) + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < TIME_LOADS; k++) v[k] = ld_nt(p + k * BLOCK);
+}
+__device__ __forceinline__ uint32_t count_time_chunk(const v4i (&v)[TIME_LOADS], double t0, double t1) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < TIME_LOADS; k++) c += (uint32_t)in_range(f64_of(v[k][0], v[k][1]), t0, t1) + (uint32_t)in_range(f64_of(v[k][2], v[k][3]), t0, t1);
+    return c;
+}
+// per-thread counts -> partials[blockIdx.x]; `whole` (thread 0): points of the chunks counted without being read
+__device__ __forceinline__ void block_count_out(uint32_t cnt, uint64_t whole, uint64_t *__restrict__ partials) {
+    __shared__ uint64_t s_cnt[WAVES];
+    uint64_t t = cnt;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor((unsigned long long)t, off, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] + whole;
+}
+
+// First time scan: count + per-chunk {min, max, NaNs} in one pass.  A NaN loses every compare, so it moves neither extreme.
+__global__ __launch_bounds__(BLOCK) void k_index_build_time(const v4i *__restrict__ base, uint64_t nchunks, DevPred pred,
+                                                            ChunkTime *__restrict__ recs, uint64_t *__restrict__ partials) {
+    __shared__ double s_mn[WAVES], s_mx[WAVES];
+    __shared__ uint32_t s_nan[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double t0 = pred.wmin[0], t1 = pred.wmax[0];
+    uint32_t cnt = 0;
+    for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        v4i v[TIME_LOADS];
+        load_time_chunk(v, base, ch);
+        if (!pred.empty) cnt += count_time_chunk(v, t0, t1);
+        double mn = __longlong_as_double(0x7ff0000000000000ll), mx = -mn;  // +inf, -inf
+        uint32_t nans = 0;
+#pragma unroll
+        for (int k = 0; k < TIME_LOADS; k++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const double t = f64_of(v[k][2 * h], v[k][2 * h + 1]);
+                mn = t < mn ? t : mn;
+                mx = t > mx ? t : mx;
+                nans += t != t;
+            }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double a = __shfl_xor(mn, off, 64), b = __shfl_xor(mx, off, 64);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+            nans += __shfl_xor(nans, off, 64);
+        }
+        if (lane == 0) s_mn[wave] = mn, s_mx[wave] = mx, s_nan[wave] = nans;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            ChunkTime ct;
+            ct.mn = s_mn[0], ct.mx = s_mx[0], ct.nans = s_nan[0], ct._pad = 0;
+            for (int w = 1; w < WAVES; w++) {
+                ct.mn = s_mn[w] < ct.mn ? s_mn[w] : ct.mn;
+                ct.mx = s_mx[w] > ct.mx ? s_mx[w] : ct.mx;
+                ct.nans += s_nan[w];
+            }
+            recs[ch] = ct;
+        }
+        __syncthreads();
+    }
+    block_count_out(cnt, 0, partials);
+}
+
+// Later time scans: classify each chunk (block-uniform), read only the straddling ones.  stats[0..2] += chunks skipped /
+// counted whole / scanned.
+__global__ __launch_bounds__(BLOCK) void k_index_count_time(const v4i *__restrict__ base, uint64_t nchunks, DevPred pred,
+                                                            const ChunkTime *__restrict__ recs, uint64_t *__restrict__ partials,
+                                                            unsigned long long *__restrict__ stats) {
+    const double t0 = pred.wmin[0], t1 = pred.wmax[0];
+    uint32_t cnt = 0;
+    uint64_t whole = 0;
+    uint32_t n_skip = 0, n_full = 0, n_scan = 0;
+    for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        const int st = index_time_state(recs[ch], t0, t1);  // block-uniform
+        if (st == CHUNK_NONE) {
+            n_skip++;
+            continue;
+        }
+        if (st == CHUNK_ALL) {
+            whole += CHUNK_POINTS;
+            n_full++;
+            continue;
+        }
+        n_scan++;
+        v4i v[TIME_LOADS];
+        load_time_chunk(v, base, ch);
+        cnt += count_time_chunk(v, t0, t1);
+    }
+    block_count_out(cnt, whole, partials);
+    if (threadIdx.x == 0) {
+        if (n_skip) atomicAdd(&stats[0], (unsigned long long)n_skip);
+        if (n_full) atomicAdd(&stats[1], (unsigned long long)n_full);
+        if (n_scan) atomicAdd(&stats[2], (unsigned long long)n_scan);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restrict__ partials, int nblocks, uint64_t *__restrict__ d_count) {
     __shared__ uint64_t s[BLOCK];
     uint64_t t = 0;
@@ -254,13 +369,17 @@ __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restri
 
 // Statistics of an indexed buffer scan in index-chunk units: stats[0..2] += chunks disjoint from the predicate (not read by
 // the count pass) / contained (not read by the count pass) / straddling (read) — the classification k_tile_counts<.., IDX> took
-// its tile states from.  boxes alone: a bounds scan; hist alone: a class scan (class chunks); both: box AND class (bounds chunks).  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
-__global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__restrict__ boxes, const uint32_t *__restrict__ hist, uint64_t nchunks,
-                                                            uint64_t n, DevPred pred, unsigned long long *__restrict__ stats) {
+// its tile states from.  boxes alone: a bounds scan; hist alone: a class scan (class chunks); both: box AND class (bounds chunks);
+// times alone: a time scan (time chunks).  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
+__global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__restrict__ boxes, const uint32_t *__restrict__ hist,
+                                                            const ChunkTime *__restrict__ times, uint64_t nchunks, uint64_t n, DevPred pred,
+                                                            unsigned long long *__restrict__ stats) {
     uint32_t k[3] = {0, 0, 0};
     for (uint64_t ch = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; ch < nchunks; ch += (uint64_t)gridDim.x * BLOCK) {
         int st;
-        if (boxes) {
+        if (times) {
+            st = index_time_state(times[ch], pred.wmin[0], pred.wmax[0]);
+        } else if (boxes) {
             const ChunkBox cb = boxes[ch];
             st = index_box_state(cb.mn, cb.mx, pred);
             if (hist) {  // box AND class, in bounds chunks
@@ -296,12 +415,16 @@ struct pcq_index {
     const void *cls = nullptr;
     uint64_t n_cls = 0, ncchunks = 0;
     uint32_t *d_hist = nullptr;
+    // time part
+    const void *times = nullptr;
+    uint64_t n_times = 0, ntchunks = 0;
+    ChunkTime *d_times = nullptr;
     // statistics of the last indexed bounds scan
     unsigned long long *d_stats = nullptr;
     pcq_index_stats last = {};
     hipStream_t stats_stream = nullptr;  // non-null: `last` must be completed from d_stats (fetched lazily)
-    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds count) · 1 / 2 / 3: a bounds / class / box AND class buffer
-    DevPred stats_pred = {};             //    scan, classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
+    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds or time count) · 1 / 2 / 3 / 4: a bounds / class / box AND
+    DevPred stats_pred = {};             //    class / time buffer scan, classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
 };
 
 extern "C" int pcq_index_new(pcq_ctx *ctx, pcq_index **out) {
@@ -326,6 +449,7 @@ extern "C" int pcq_index_free(pcq_index *ix) {
     (void)hipDeviceSynchronize();
     if (ix->d_boxes) (void)hipFree(ix->d_boxes);
     if (ix->d_hist) (void)hipFree(ix->d_hist);
+    if (ix->d_times) (void)hipFree(ix->d_times);
     if (ix->d_stats) (void)hipFree(ix->d_stats);
     delete ix;
     return PCQ_OK;
@@ -337,12 +461,14 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     if (ix->stats_stream) {  // the counters of the last indexed bounds scan are still on the device
         unsigned long long h[3] = {0, 0, 0};
         if (ix->stats_kind) {
-            const uint64_t nch = ix->stats_kind == 2 ? ix->ncchunks : ix->nchunks;
+            const bool time = ix->stats_kind == 4;
+            const uint64_t nch = time ? ix->ntchunks : (ix->stats_kind == 2 ? ix->ncchunks : ix->nchunks);
             const int grid = (int)((nch + BLOCK - 1) / BLOCK < (uint64_t)ix->ctx->num_cus ? (nch + BLOCK - 1) / BLOCK : (uint64_t)ix->ctx->num_cus);
             PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), ix->stats_stream));
             if (grid > 0)
-                hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream, ix->stats_kind != 2 ? ix->d_boxes : nullptr,
-                                   ix->stats_kind != 1 ? ix->d_hist : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
+                hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream,
+                                   !time && ix->stats_kind != 2 ? ix->d_boxes : nullptr, !time && ix->stats_kind != 1 ? ix->d_hist : nullptr,
+                                   time ? ix->d_times : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
             PCQ_HIP(hipGetLastError());
         }
         PCQ_HIP(hipStreamSynchronize(ix->stats_stream));
@@ -546,6 +672,99 @@ extern "C" int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *co
         tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
         tail.cls = (const uint8_t *)cols->cls + rest_first;
         tail.cls_stride = 1;
+        tail.rgb = nullptr;
+        tail.n = cols->n - rest_first;
+        return pcq_scan_dev(ctx, &tail, pred, c, stream);
+    }
+    return PCQ_OK;
+}
+
+// The time part: packed f64 times, 16-byte aligned (two times per load), with at least one whole chunk.
+static bool time_index_covers(const pcq_columns *cols) {
+    return cols->cls && cols->cls_stride == 8 && ((uintptr_t)cols->cls & 15) == 0 && cols->n >= CHUNK_POINTS;
+}
+// The records of the `chunks` whole chunks of the time column cols->cls, as ensure_boxes builds the boxes.
+static int ensure_times(pcq_ctx *ctx, pcq_index *ix, const pcq_columns *cols, uint64_t chunks, int grid, const DevPred &build_with,
+                        hipStream_t s, bool *had) {
+    *had = ix->d_times && ix->times == cols->cls && ix->n_times == cols->n;
+    if (*had) return PCQ_OK;
+    if (ix->d_times) PCQ_HIP(hipFree(ix->d_times));
+    ix->d_times = nullptr;
+    PCQ_HIP(hipMalloc((void **)&ix->d_times, chunks * sizeof(ChunkTime)));
+    hipLaunchKernelGGL(k_index_build_time, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->cls), chunks, build_with,
+                       ix->d_times, ctx->d_partials);
+    PCQ_HIP(hipGetLastError());
+    ix->times = cols->cls;
+    ix->n_times = cols->n;
+    ix->ntchunks = chunks;
+    return PCQ_OK;
+}
+
+// GPS time in [start, end) through the time part of the index; the bounds and class parts are neither read nor changed.
+extern "C" int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                                         pcq_collector *c, void *stream) {
+    PCQ_ON_DEVICE_OF_CTX(ctx);
+    if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_time: null argument");
+    if (pred->kind != PCQ_PRED_TIME) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_time: predicate kind %d (PCQ_PRED_TIME only)", pred->kind);
+    if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_time: count and buffer collectors only");
+    int rc = pcq_validate_scan(cols, pred, c);  // (before the index or the collector is touched: the kernels below trust the columns)
+    if (rc) return rc;
+    if (!time_index_covers(cols)) {  // layout the index does not cover: plain scan, statistics that claim nothing
+        ix->last = pcq_index_stats{};
+        ix->stats_stream = nullptr;
+        ix->stats_kind = 0;
+        return pcq_scan_dev(ctx, cols, pred, c, stream);
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    DevPred dp;
+    rc = pcq_make_dev_pred(pred, &dp);
+    if (rc) return rc;
+    rc = pcq_scratch_stream(ctx, s);
+    if (rc) return rc;
+    const bool count = c->kind == COLL_COUNT;
+    const uint64_t chunks = cols->n / CHUNK_POINTS;
+    const int max_blocks = ctx->num_cus * 8;
+    const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+    rc = pcq_ensure_partials(ctx, (size_t)grid);
+    if (rc) return rc;
+    DevPred build_with = dp;
+    if (!count) build_with.empty = 1;  // the records alone: the emit counts
+    bool had;
+    rc = ensure_times(ctx, ix, cols, chunks, grid, build_with, s, &had);
+    if (rc) return rc;
+    ix->last = pcq_index_stats{};
+    ix->last.chunks = chunks;
+    ix->stats_stream = nullptr;
+    ix->stats_kind = 0;
+    if (!had) {  // the build read every chunk
+        ix->last.built = 1;
+        ix->last.scanned = chunks;
+    }
+    if (!count) {
+        if (had) {
+            ix->stats_stream = s;  // classified and fetched by pcq_index_get_stats: nothing on the scan path
+            ix->stats_kind = 4;
+            ix->stats_pred = dp;
+        }
+        EmitIndex eix = {};
+        eix.times = ix->d_times;
+        eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
+        return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+    }
+    c->last_stream = s;
+    if (had) {
+        PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_index_count_time, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->cls), chunks, dp, ix->d_times,
+                           ctx->d_partials, ix->d_stats);
+        ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
+    }
+    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    PCQ_HIP(hipGetLastError());
+    const uint64_t rest_first = chunks * CHUNK_POINTS;
+    if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS times (and positions, when present)
+        pcq_columns tail = *cols;
+        tail.cls = (const uint8_t *)cols->cls + 8 * rest_first;
+        tail.xyz = cols->xyz ? (const uint8_t *)cols->xyz + 12 * rest_first : nullptr;
         tail.rgb = nullptr;
         tail.n = cols->n - rest_first;
         return pcq_scan_dev(ctx, &tail, pred, c, stream);

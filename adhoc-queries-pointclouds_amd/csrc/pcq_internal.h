@@ -126,11 +126,17 @@ struct DevGrid {
 };
 
 // The chunk index (chunk_index.hip) as the buffer emit's count pass sees it: the state of the index chunk a tile of 2048
-// points lies in.  Bounds chunks hold 4096 points (tiles 2c, 2c + 1), class chunks 65536 (tiles 32c .. 32c + 31); both start
-// at point 0.  Tiles from `covered_tiles` on (the ragged tail) are always counted.
+// points lies in.  Bounds and time chunks hold 4096 points (tiles 2c, 2c + 1), class chunks 65536 (tiles 32c .. 32c + 31); all
+// start at point 0.  Tiles from `covered_tiles` on (the ragged tail) are always counted.
+struct ChunkTime {  // GPS times of one 4096-point chunk: extremes over its non-NaN times (+inf / -inf when it has none)
+    double mn, mx;
+    uint32_t nans;  // times that are NaN
+    uint32_t _pad;
+};
 struct EmitIndex {
     const int32_t *boxes;    // bounds: {mn[3], mx[3]} per chunk (integer AABB), or nullptr
     const uint32_t *hist;    // class: 256 bins per chunk, or nullptr   (box AND class: both)
+    const ChunkTime *times;  // time: one record per chunk, or nullptr (alone)
     uint64_t covered_tiles;
 };
 enum { CHUNK_SCAN = 0, CHUNK_NONE = 1, CHUNK_ALL = 2 };  // straddling: read it · disjoint: no match · contained: every point matches
@@ -149,6 +155,13 @@ __device__ __forceinline__ int index_box_state(const int32_t (&mn)[3], const int
 // A class chunk of `points` points whose histogram bin for the predicate's class is `bin`.
 __device__ __forceinline__ int index_class_state(uint32_t bin, uint64_t points) {
     return bin == 0 ? CHUNK_NONE : ((uint64_t)bin == points ? CHUNK_ALL : CHUNK_SCAN);
+}
+// A time chunk against [t0, t1): Range<f64>::contains (pcq.h, PCQ_PRED_TIME) restated on the chunk's extremes, in IEEE f64
+// compares only.  An empty range (t0 >= t1, or a NaN bound) and a chunk of NaNs match nothing; a chunk is contained only when
+// none of its times is NaN.
+__device__ __forceinline__ int index_time_state(const ChunkTime &ct, double t0, double t1) {
+    if (!(t0 < t1) || ct.nans == (uint32_t)INDEX_BOUNDS_CHUNK || ct.mx < t0 || ct.mn >= t1) return CHUNK_NONE;
+    return ct.nans == 0 && ct.mn >= t0 && ct.mx < t1 ? CHUNK_ALL : CHUNK_SCAN;
 }
 // Box AND class: a bounds chunk's box state with the state of the class chunk it lies in.  Nothing matches where either
 // part has no match, every point matches only where both say so, and everything else is read.
@@ -339,7 +352,7 @@ int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const D
 // scan_generic.hip
 int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred,
                              uint64_t *d_count, hipStream_t s);
-// ix (optional): the count pass takes each tile's state from the chunk index first (bounds or class predicates)
+// ix (optional): the count pass takes each tile's state from the chunk index first (bounds, class, box AND class or time predicates)
 int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint8_t *d_out31, const uint64_t *d_npoints_in,
                            uint64_t *d_npoints_out, hipStream_t s, const EmitIndex *ix = nullptr);
 // collectors.hip: pcq_scan_dev on stream s; ix (optional) is handed to the buffer collector's emit

@@ -266,7 +266,7 @@ struct pcq_host_resident {
     std::unique_ptr<ResidentDataset> ds;
     int device = -1;
 };
-static int resident_load(int device, const char *const *files, size_t nfiles, pcq_host_resident **out, bool with_points) {
+static int resident_load(int device, const char *const *files, size_t nfiles, pcq_host_resident **out, bool with_points, bool with_times = false) {
     if (!out || (!files && nfiles)) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     *out = nullptr;
     for (size_t i = 0; i < nfiles; i++)
@@ -278,7 +278,7 @@ static int resident_load(int device, const char *const *files, size_t nfiles, pc
     for (size_t i = 0; i < nfiles; i++) v.emplace_back(files[i]);
     auto h = std::make_unique<pcq_host_resident>();
     h->device = device;
-    st = ResidentDataset::load(ctx, v, &h->ds, with_points);
+    st = ResidentDataset::load(ctx, v, &h->ds, with_points, with_times);
     if (!st.ok()) return done(st);
     *out = h.release();
     return PCQ_OK;
@@ -288,6 +288,10 @@ extern "C" int pcq_query_resident_load(int device, const char *const *files, siz
 }
 extern "C" int pcq_query_resident_load_points(int device, const char *const *files, size_t nfiles, pcq_host_resident **out) {
     return resident_load(device, files, nfiles, out, true);
+}
+extern "C" int pcq_query_resident_load_with(int device, const char *const *files, size_t nfiles, unsigned blocks, pcq_host_resident **out) {
+    if (blocks & ~(unsigned)(PCQ_RESIDENT_COLOUR | PCQ_RESIDENT_TIME)) return done(Status::Err(PCQ_ERR_ARG, "unknown resident block " + std::to_string(blocks)));
+    return resident_load(device, files, nfiles, out, (blocks & PCQ_RESIDENT_COLOUR) != 0, (blocks & PCQ_RESIDENT_TIME) != 0);
 }
 static Status resident_collector_ok(const pcq_host_resident *r, const pcq_host_collector *c) {
     if (c->device != r->device)
@@ -308,6 +312,12 @@ extern "C" int pcq_query_resident_search_class(pcq_host_resident *r, uint8_t cls
     Status st = resident_collector_ok(r, c);
     if (!st.ok()) return done(st);
     return done(r->ds->search_class(cls, *c->c));
+}
+extern "C" int pcq_query_resident_search_time(pcq_host_resident *r, double start, double end, pcq_host_collector *c) {
+    if (!r || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    Status st = resident_collector_ok(r, c);
+    if (!st.ok()) return done(st);
+    return done(r->ds->search_time(start, end, *c->c));
 }
 extern "C" int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out) {
     if (!r || !out) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

@@ -377,6 +377,7 @@ struct ResidentFile {
     LasHeader header;
     void *xyz = nullptr, *cls = nullptr;  // device blocks
     void *rgb = nullptr;                  // colour block (load with points, formats with colour)
+    void *time = nullptr;                 // GPS time block (load with times)
     pcq_index *index = nullptr;           // chunk index of the blocks (first search_* of the file)
 };
 class ResidentDataset {
@@ -385,7 +386,9 @@ public:
     ResidentDataset(const ResidentDataset &) = delete;
     ResidentDataset &operator=(const ResidentDataset &) = delete;
     // with_points: the colour blocks too, so that buffer and grid collectors can be served
-    static Status load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points = false);
+    // with_times: the GPS time blocks too (every file must have one: the errors of the LAST time search's prologue), for search_time
+    static Status load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points = false,
+                       bool with_times = false);
     Status count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
@@ -393,6 +396,7 @@ public:
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
     Status search_bounds_class(const AABB &bounds, uint8_t cls, ResultCollector &rc);
+    Status search_time(double start, double end, ResultCollector &rc);  // (a dataset loaded with_times; any collector)
     // chunk-index statistics of the last search_*, summed over the files it scanned through the index
     Status last_stats(pcq_index_stats *out);
     size_t files() const { return files_.size(); }
@@ -403,7 +407,7 @@ private:
     Status run(const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches);
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     pcq_ctx *ctx_ = nullptr;
-    bool with_points_ = false;
+    bool with_points_ = false, with_times_ = false;
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;

@@ -14,6 +14,9 @@
 //
 // Box AND class (count_bounds_class / search_bounds_class): both blocks of a file lie in HBM side by side, so the count is one
 // pcq_scan_dev_count_batch_combined and the search goes through both parts of the file's index (pcq_scan_dev_indexed_combined).
+//
+// GPS time (search_time): a dataset loaded with its time blocks answers the LAST time search over them, count and buffer
+// collectors through the time part of the file's index (pcq_scan_dev_indexed_time).
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -25,6 +28,7 @@ ResidentDataset::~ResidentDataset() {
         if (f.xyz) pcq_device_free(ctx_, f.xyz);
         if (f.cls) pcq_device_free(ctx_, f.cls);
         if (f.rgb) pcq_device_free(ctx_, f.rgb);
+        if (f.time) pcq_device_free(ctx_, f.time);
         if (f.index) pcq_index_free(f.index);
     }
     if (counter_) pcq_device_free(ctx_, counter_);
@@ -32,10 +36,14 @@ ResidentDataset::~ResidentDataset() {
 
 // Loads the positions and classification blocks of every .last file (last.rs:68-90 for the offsets) into HBM.
 // with_points: the colour block as well (last.rs:83-90), for the records of buffer and grid collectors.
-Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points) {
+// with_times: the GPS time block as well, where the LAST time search finds it — its plan (search.cpp) is made first, so a file
+// fails here as it fails there: no GPS times (formats 0, 2), a format above 10, a block that reaches past the file.
+Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points,
+                             bool with_times) {
     auto ds = std::unique_ptr<ResidentDataset>(new ResidentDataset());
     ds->ctx_ = ctx;
     ds->with_points_ = with_points;
+    ds->with_times_ = with_times;
     void *p = nullptr;
     Status st = Status::FromLib(pcq_device_alloc(ctx, 16, &p));
     if (!st.ok()) return st;
@@ -43,6 +51,12 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
     for (const auto &path : paths) {
         if (path.size() < 5 || path.compare(path.size() - 5, 5, ".last") != 0)
             return Status::Err(PCQ_ERR_EXTENSION, "resident datasets hold LAST files: " + path);
+        uint64_t time_block = 0;
+        if (with_times) {
+            FilePlan plan = plan_last_file_by_time_range_optimized(path, 0.0, 0.0);
+            if (!plan.status.ok()) return plan.status;
+            time_block = (uint64_t)(uintptr_t)plan.cols.cls;  // (a plan's column pointers are file offsets; a file of 0 points has none)
+        }
         MappedFile file;
         st = file.open(path);
         if (!st.ok()) return st;
@@ -64,6 +78,8 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
             st = Status::FromLib(pcq_device_alloc(ctx, n * 12, &rf.xyz));
             if (st.ok()) st = Status::FromLib(pcq_device_alloc(ctx, n, &rf.cls));
             if (st.ok() && colours) st = Status::FromLib(pcq_device_alloc(ctx, n * 6, &rf.rgb));
+            if (st.ok() && with_times) st = Status::FromLib(pcq_device_alloc(ctx, n * 8, &rf.time));
+            if (st.ok() && with_times) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), time_block, n * 8, rf.time));
             if (st.ok()) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), otp, n * 12, rf.xyz));
             if (st.ok()) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), cls_block, n, rf.cls));
             if (st.ok() && colours) st = Status::FromLib(pcq_read_fd_to_device(ctx, file.fd(), col_block, n * 6, rf.rgb));
@@ -155,13 +171,15 @@ Status ResidentDataset::count_bounds_class(const AABB &bounds, uint8_t cls, uint
     return Status::FromLib(rc);
 }
 
-// One file of search_bounds / search_class: execute_plan (search.cpp) with the resident blocks in place of the file.
+// One file of the search_* : execute_plan (search.cpp) with the resident blocks in place of the file.
 Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc) {
     const uint64_t n = f.header.number_of_points;
+    const bool time = pred.kind == PCQ_PRED_TIME;
     pcq_columns c{};
     c.xyz = f.xyz, c.xyz_stride = 12;  // last.rs:114-121
     c.cls = f.cls, c.cls_stride = 1;   // :138-142
     c.rgb = f.rgb, c.rgb_stride = 6;   // :145-153
+    if (time) c.cls = f.time, c.cls_stride = 8, c.rgb = nullptr;  // the predicate's column; a time record has no class and no colour
     c.n = n;
     c.first_index = rc.next_index;
     for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];  // :156-160
@@ -173,8 +191,9 @@ Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultC
             r = pcq_index_new(ctx_, &f.index);
             if (r) return Status::FromLib(r);
         }
-        r = pred.kind == PCQ_PRED_BOUNDS_CLASS ? pcq_scan_dev_indexed_combined(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
-                                               : pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
+        r = time                                 ? pcq_scan_dev_indexed_time(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
+            : pred.kind == PCQ_PRED_BOUNDS_CLASS ? pcq_scan_dev_indexed_combined(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
+                                                 : pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
         if (!r) last_indices_.push_back(f.index);
     }
     rc.next_index += n;
@@ -230,6 +249,24 @@ Status ResidentDataset::search_bounds_class(const AABB &bounds, uint8_t cls, Res
         const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
         if (brc) return Status::FromLib(brc);
         if (f.header.number_of_points == 0) continue;
+        Status st = scan(f, pred, rc);
+        if (!st.ok()) return st;
+    }
+    return Status::Ok();
+}
+
+// search_last_file_by_time_range_optimized (search.cpp) for every file: no file-level early-out (a header has no time bounds).
+// Any collector: a time record's colour is (0,0,0), so no colour block is needed.
+Status ResidentDataset::search_time(double start, double end, ResultCollector &rc) {
+    if (!with_times_)
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
+    last_indices_.clear();
+    for (auto &f : files_) {
+        if (f.header.number_of_points == 0) continue;
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_TIME;
+        pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
+        pred.wmax[0] = end;
         Status st = scan(f, pred, rc);
         if (!st.ok()) return st;
     }

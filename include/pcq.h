@@ -293,6 +293,21 @@ int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predic
  * scanned, built = 1 when this call built either part. */
 int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
                                   pcq_collector *c, void *stream);
+/* PCQ_PRED_TIME (only; other kinds PCQ_ERR_ARG) through a third part of the same index object, count and buffer collectors
+ * (grid: PCQ_ERR_ARG): per 4096-point chunk of the time column (pcq_columns.cls, the chunk of the bounds part) the minimum and
+ * the maximum of its non-NaN times and the number of its NaNs.  The first call for a column (pointer and n) builds the part
+ * while it scans (built = 1, scanned = chunks); later calls take each chunk's state against [wmin[0], wmax[0]) from it, in
+ * IEEE f64 compares only: an empty range (start >= end, or a NaN bound), a chunk of NaNs, max < start or min >= end -> skipped,
+ * nothing read; no NaN and start <= min and max < end -> counted whole, nothing read; everything else -> its 32 KiB of times
+ * are read.  A file in acquisition order is close to monotone in time: a range then reads a handful of chunks.  Results and
+ * records are pcq_scan_dev's for PCQ_PRED_TIME, byte for byte and in order (position, class 0, colour (0,0,0)), behind what the
+ * collector holds; the ragged tail behind the last whole chunk is always read.  Covered: a packed time column (cls_stride 8),
+ * 16-byte aligned, at least 4096 points — `xyz` may be NULL for a count collector, as for pcq_scan_dev; any other layout (LAS
+ * records, a column aligned to 8 bytes only, fewer points) falls through to pcq_scan_dev with all-zero statistics and leaves
+ * the index untouched.  Statistics in time chunks: chunks = n / 4096 = skipped + whole + scanned.  This entry neither reads nor
+ * changes the bounds and class parts, and pcq_scan_dev_indexed / _combined neither read nor change the time part. */
+int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                              pcq_collector *c, void *stream);
 
 /* The one collective of the path (main.rs:164-180) for callers that drive n GPUs from ONE process:
  * recv[i][0] = the sum over i of send[i][0] (8 bytes each in ctxs[i]'s HBM, e.g. the counter of

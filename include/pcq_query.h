@@ -118,6 +118,19 @@ int pcq_query_resident_search_class(pcq_host_resident *r, uint8_t cls, pcq_host_
  * grid collectors through pcq_scan_dev. */
 int pcq_query_resident_search_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
                                            pcq_host_collector *c);
+/* The loader with the blocks named: `blocks` is a set of the bits below.  0 = pcq_query_resident_load, PCQ_RESIDENT_COLOUR =
+ * pcq_query_resident_load_points; PCQ_RESIDENT_TIME adds every file's GPS time block, found as the LAST time search finds it
+ * (pcq_query_search_file_time): at offset_to_point_data + n*20 (formats 1, 3-5) or + n*22 (6-10).  With that bit a file of
+ * format 0 or 2 ("File {path} does not contain GPS times!") or above 10 is PCQ_ERR_FORMAT and a block reaching past the file
+ * PCQ_ERR_EOF; the load fails as a whole on the first such file.  Any other bit is PCQ_ERR_ARG. */
+#define PCQ_RESIDENT_COLOUR 1u
+#define PCQ_RESIDENT_TIME 2u
+int pcq_query_resident_load_with(int device, const char *const *files, size_t nfiles, unsigned blocks, pcq_host_resident **out);
+/* == pcq_query_search_file_time(path, start, end, optimized=1, c) for every loaded file, in load order, into ONE collector (no
+ * file-level early-out: a header has no time bounds).  Count and buffer collectors go through the time part of each file's
+ * chunk index (pcq_scan_dev_indexed_time), grid collectors through pcq_scan_dev.  Needs a dataset loaded with
+ * PCQ_RESIDENT_TIME (else PCQ_ERR_ARG) and no colour blocks, whatever the collector: a time record's colour is (0,0,0). */
+int pcq_query_resident_search_time(pcq_host_resident *r, double start, double end, pcq_host_collector *c);
 /* Index statistics of the last resident search, summed over its files (those it scanned through an index; none for a grid
  * collector).  Waits for the search's scans. */
 int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out);
