@@ -207,6 +207,7 @@ def load_library() -> C.CDLL:
         "pcq_prepare_host_scans": (C.c_int, [vp]),
         "pcq_scan_dev_count_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_combined": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
+        "pcq_scan_dev_count_batch_bounds_time": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -216,6 +217,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_indexed": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
         "pcq_scan_dev_indexed_combined": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
         "pcq_scan_dev_indexed_time": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
+        "pcq_scan_dev_indexed_bounds_time": (C.c_int, [vp, P(Columns), P(Predicate), vp, vp, vp]),
         "pcq_device_alloc": (C.c_int, [vp, u64, P(vp)]),
         "pcq_device_free": (C.c_int, [vp, vp]),
         "pcq_copy_to_device": (C.c_int, [vp, vp, vp, u64]),
@@ -449,6 +451,15 @@ class Context:
         pa = (Predicate * n)(*preds)
         _check(self.lib.pcq_scan_dev_count_batch_combined(self.handle, ca, pa, n, C.c_void_p(device_total), C.c_void_p(stream)))
 
+    def scan_dev_count_batch_bounds_time(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_total: int,
+                                         stream: Optional[int] = None) -> None:
+        """Box AND GPS time range (Predicate kind PCQ_PRED_BOUNDS_TIME; the times in Columns.cls, stride 8) over many resident
+        LAST files in one launch; += into device_total."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        _check(self.lib.pcq_scan_dev_count_batch_bounds_time(self.handle, ca, pa, n, C.c_void_p(device_total), C.c_void_p(stream)))
+
     # chunk index --------------------------------------------------------------------------------
     def index_new(self) -> int:
         h = C.c_void_p()
@@ -476,6 +487,11 @@ class Context:
         """GPS time in [start, end) through the time part of the chunk index (min, max and NaN count per 4096 times)."""
         _check(self.lib.pcq_scan_dev_indexed_time(self.handle, C.byref(cols), C.byref(pred), C.c_void_p(ix), coll.handle,
                                                   C.c_void_p(stream)))
+
+    def scan_dev_indexed_bounds_time(self, cols: Columns, pred: Predicate, ix: int, coll: Collector, stream: Optional[int] = None) -> None:
+        """Box AND GPS time range through the bounds part and the time part of the chunk index (the same 4096-point chunks)."""
+        _check(self.lib.pcq_scan_dev_indexed_bounds_time(self.handle, C.byref(cols), C.byref(pred), C.c_void_p(ix), coll.handle,
+                                                         C.c_void_p(stream)))
 
     def synth_fill(self, spec: SynthSpec, first: int, count: int, d_xyz: Optional[int], d_cls: Optional[int],
                    stream: Optional[int] = None) -> None:

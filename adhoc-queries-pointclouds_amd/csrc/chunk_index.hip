@@ -16,6 +16,8 @@
 //     GPS times and the number of its NaNs (24 B per 32 KiB of times).  Later time scans classify each chunk against
 //     [start, end) (index_time_state): a file in acquisition order is close to monotone in time, so all but a handful of chunks
 //     are disjoint.
+//   * box AND time (pcq_scan_dev_indexed_bounds_time): the boxes and the time records of the same 4096-point chunks, combined
+//     as box AND class combines its parts; a file in acquisition order is coherent in space and in time at once.
 //   * buffer collectors (the records of the matches): the index is built the same way (boxes or histograms alone), then the
 //     emit of scan_generic.hip runs with its count pass taking each 2048-point tile's state from the index first
 //     (k_tile_counts with IDX): disjoint tiles and contained tiles are not read there, disjoint ones not by the emit either.
@@ -354,6 +356,57 @@ __global__ __launch_bounds__(BLOCK) void k_index_count_time(const v4i *__restric
     }
 }
 
+// Box AND time (pcq_scan_dev_indexed_bounds_time): each 4096-point chunk takes its box state together with the state of its own
+// time record (index_combined_state; both parts have the same chunks).  Only SCAN chunks are read: their 48 KiB of positions and
+// their 32 KiB of times, tested tile by tile as K1 does with its second column (scan_tiles.h, COL_F64).  The shape of
+// k_index_count_bounds_class: a tile's five loads are issued together and evaluated before the next tile's.
+__global__ __launch_bounds__(BLOCK) void k_index_count_bounds_time(const v4i *__restrict__ base, const uint8_t *__restrict__ times, uint64_t nchunks,
+                                                                   DevPred pred, const ChunkBox *__restrict__ boxes,
+                                                                   const ChunkTime *__restrict__ recs, uint64_t *__restrict__ partials,
+                                                                   unsigned long long *__restrict__ stats) {
+    __shared__ uint64_t s_cnt[WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const LaneBox lb = rotate_box(pred.lo, pred.width, lane);
+    const Col2<COL_F64> c2 = col2_setup(times, pred, lane, IntC<COL_F64>{});
+    uint64_t total = 0;
+    uint32_t n_skip = 0, n_full = 0, n_scan = 0;
+    for (uint64_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        const ChunkBox cb = boxes[ch];  // block-uniform
+        const int st = index_combined_state(index_box_state(cb.mn, cb.mx, pred), index_time_state(recs[ch], c2.t0, c2.t1));
+        if (st == CHUNK_NONE) {
+            n_skip++;
+            continue;
+        }
+        if (st == CHUNK_ALL) {
+            if (threadIdx.x == 0) total += CHUNK_POINTS;
+            n_full++;
+            continue;
+        }
+        n_scan++;
+#pragma unroll
+        for (int q = 0; q < CHUNK_TILES / WAVES; q++) {
+            const uint64_t t = ch * CHUNK_TILES + (uint64_t)wave * (CHUNK_TILES / WAVES) + q;
+            const v4i *tile = base + t * 192;
+            v4i v[3];
+            v[0] = ld_nt(tile + lane);
+            v[1] = ld_nt(tile + 64 + lane);
+            v[2] = ld_nt(tile + 128 + lane);
+            Col2Regs<COL_F64> r;
+            col2_load_plain(r, c2, t);
+            const uint32_t c = tile_count_regs<COL_F64>(v, lb, c2, verdict_word(r, c2));
+            if (lane == 0) total += c;
+        }
+    }
+    if (lane == 0) s_cnt[wave] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        if (n_skip) atomicAdd(&stats[0], (unsigned long long)n_skip);
+        if (n_full) atomicAdd(&stats[1], (unsigned long long)n_full);
+        if (n_scan) atomicAdd(&stats[2], (unsigned long long)n_scan);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restrict__ partials, int nblocks, uint64_t *__restrict__ d_count) {
     __shared__ uint64_t s[BLOCK];
     uint64_t t = 0;
@@ -370,22 +423,24 @@ __global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restri
 // Statistics of an indexed buffer scan in index-chunk units: stats[0..2] += chunks disjoint from the predicate (not read by
 // the count pass) / contained (not read by the count pass) / straddling (read) — the classification k_tile_counts<.., IDX> took
 // its tile states from.  boxes alone: a bounds scan; hist alone: a class scan (class chunks); both: box AND class (bounds chunks);
-// times alone: a time scan (time chunks).  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
+// times alone: a time scan (time chunks); boxes and times: box AND time (the chunks of both).  Launched by pcq_index_get_stats when the statistics are asked for, never on the scan path.
 __global__ __launch_bounds__(BLOCK) void k_index_emit_stats(const ChunkBox *__restrict__ boxes, const uint32_t *__restrict__ hist,
                                                             const ChunkTime *__restrict__ times, uint64_t nchunks, uint64_t n, DevPred pred,
                                                             unsigned long long *__restrict__ stats) {
     uint32_t k[3] = {0, 0, 0};
     for (uint64_t ch = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; ch < nchunks; ch += (uint64_t)gridDim.x * BLOCK) {
         int st;
-        if (times) {
-            st = index_time_state(times[ch], pred.wmin[0], pred.wmax[0]);
-        } else if (boxes) {
+        if (boxes) {
             const ChunkBox cb = boxes[ch];
             st = index_box_state(cb.mn, cb.mx, pred);
             if (hist) {  // box AND class, in bounds chunks
                 const uint64_t cch = ch / (CLASS_CHUNK / CHUNK_POINTS), first = cch * CLASS_CHUNK;
                 st = index_combined_state(st, index_class_state(hist[cch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK));
+            } else if (times) {  // box AND time
+                st = index_combined_state(st, index_time_state(times[ch], pred.wmin[0], pred.wmax[0]));
             }
+        } else if (times) {
+            st = index_time_state(times[ch], pred.wmin[0], pred.wmax[0]);
         } else {
             const uint64_t first = ch * CLASS_CHUNK;
             st = index_class_state(hist[ch * 256 + (pred.cls & 255u)], n - first < CLASS_CHUNK ? n - first : CLASS_CHUNK);
@@ -423,8 +478,8 @@ struct pcq_index {
     unsigned long long *d_stats = nullptr;
     pcq_index_stats last = {};
     hipStream_t stats_stream = nullptr;  // non-null: `last` must be completed from d_stats (fetched lazily)
-    int stats_kind = 0;                  // 0: the scan writes d_stats itself (bounds or time count) · 1 / 2 / 3 / 4: a bounds / class / box AND
-    DevPred stats_pred = {};             //    class / time buffer scan, classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
+    int stats_kind = 0;                  // 0: the scan writes d_stats itself (a count) · 1 / 2 / 3 / 4 / 5: a bounds / class / box AND
+    DevPred stats_pred = {};             //    class / time / box AND time buffer scan, classified from the index with stats_pred by pcq_index_get_stats (k_index_emit_stats)
 };
 
 extern "C" int pcq_index_new(pcq_ctx *ctx, pcq_index **out) {
@@ -461,14 +516,14 @@ extern "C" int pcq_index_get_stats(pcq_index *ix, pcq_index_stats *out) {
     if (ix->stats_stream) {  // the counters of the last indexed bounds scan are still on the device
         unsigned long long h[3] = {0, 0, 0};
         if (ix->stats_kind) {
-            const bool time = ix->stats_kind == 4;
+            const bool time = ix->stats_kind == 4, box_time = ix->stats_kind == 5;
             const uint64_t nch = time ? ix->ntchunks : (ix->stats_kind == 2 ? ix->ncchunks : ix->nchunks);
             const int grid = (int)((nch + BLOCK - 1) / BLOCK < (uint64_t)ix->ctx->num_cus ? (nch + BLOCK - 1) / BLOCK : (uint64_t)ix->ctx->num_cus);
             PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), ix->stats_stream));
             if (grid > 0)
                 hipLaunchKernelGGL(k_index_emit_stats, dim3(grid), dim3(BLOCK), 0, ix->stats_stream,
-                                   !time && ix->stats_kind != 2 ? ix->d_boxes : nullptr, !time && ix->stats_kind != 1 ? ix->d_hist : nullptr,
-                                   time ? ix->d_times : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
+                                   !time && ix->stats_kind != 2 ? ix->d_boxes : nullptr,
+                                   !time && !box_time && ix->stats_kind != 1 ? ix->d_hist : nullptr, time || box_time ? ix->d_times : nullptr, nch, ix->n_cls, ix->stats_pred, ix->d_stats);
             PCQ_HIP(hipGetLastError());
         }
         PCQ_HIP(hipStreamSynchronize(ix->stats_stream));
@@ -765,6 +820,75 @@ extern "C" int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, 
         pcq_columns tail = *cols;
         tail.cls = (const uint8_t *)cols->cls + 8 * rest_first;
         tail.xyz = cols->xyz ? (const uint8_t *)cols->xyz + 12 * rest_first : nullptr;
+        tail.rgb = nullptr;
+        tail.n = cols->n - rest_first;
+        return pcq_scan_dev(ctx, &tail, pred, c, stream);
+    }
+    return PCQ_OK;
+}
+
+// Box AND time through the boxes and the time records of the same index object.  Parts missing for these columns are built first
+// (without a count: each builder knows its own column only), then the pruned pass always runs.
+extern "C" int pcq_scan_dev_indexed_bounds_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                                                pcq_collector *c, void *stream) {
+    PCQ_ON_DEVICE_OF_CTX(ctx);
+    if (!ctx || !cols || !pred || !ix || !c) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_bounds_time: null argument");
+    if (pred->kind != PCQ_PRED_BOUNDS_TIME)
+        return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_bounds_time: predicate kind %d (PCQ_PRED_BOUNDS_TIME only)", pred->kind);
+    if (c->kind == COLL_GRID) return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_indexed_bounds_time: count and buffer collectors only");
+    int rc = pcq_validate_scan(cols, pred, c);  // (before the index or the collector is touched: the kernels below trust the columns)
+    if (rc) return rc;
+    DevPred dp;
+    rc = pcq_make_dev_pred(pred, &dp);
+    if (rc) return rc;
+    // a layout the index does not cover, or a predicate that can match nothing (a box outside the i32 range, an empty or NaN
+    // range): the plain scan, statistics that claim nothing
+    if (!(bounds_index_covers(cols) && time_index_covers(cols)) || dp.empty || !(dp.wmin[0] < dp.wmax[0])) {
+        ix->last = pcq_index_stats{};
+        ix->stats_stream = nullptr;
+        ix->stats_kind = 0;
+        return pcq_scan_dev(ctx, cols, pred, c, stream);
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    rc = pcq_scratch_stream(ctx, s);
+    if (rc) return rc;
+    const uint64_t chunks = cols->n / CHUNK_POINTS;  // of both parts
+    const int max_blocks = ctx->num_cus * 8;
+    const int grid = (int)(chunks < (uint64_t)max_blocks ? chunks : (uint64_t)max_blocks);
+    rc = pcq_ensure_partials(ctx, (size_t)grid);
+    if (rc) return rc;
+    bool had_boxes, had_times;
+    DevPred build_only = dp;
+    build_only.empty = 1;
+    rc = ensure_boxes(ctx, ix, cols, chunks, grid, build_only, s, &had_boxes);
+    if (!rc) rc = ensure_times(ctx, ix, cols, chunks, grid, build_only, s, &had_times);
+    if (rc) return rc;
+    ix->last = pcq_index_stats{};
+    ix->last.chunks = chunks;
+    ix->last.built = !had_boxes || !had_times;
+    ix->stats_stream = s;  // completed by pcq_index_get_stats: no sync on the scan path
+    if (c->kind != COLL_COUNT) {
+        ix->stats_kind = 5;  // classified from the index when asked for
+        ix->stats_pred = dp;
+        EmitIndex eix = {};
+        eix.boxes = reinterpret_cast<const int32_t *>(ix->d_boxes);
+        eix.times = ix->d_times;
+        eix.covered_tiles = chunks * (CHUNK_POINTS / EMIT_TILE_POINTS);
+        return pcq_scan_dev_impl(ctx, cols, pred, c, s, &eix);
+    }
+    ix->stats_kind = 0;
+    c->last_stream = s;
+    PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
+    // (both builders wrote the partials; the pruned count writes every one of the `grid` again before they are summed)
+    hipLaunchKernelGGL(k_index_count_bounds_time, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
+                       chunks, dp, ix->d_boxes, ix->d_times, ctx->d_partials, ix->d_stats);
+    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    PCQ_HIP(hipGetLastError());
+    const uint64_t rest_first = chunks * CHUNK_POINTS;
+    if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS positions and ITS times
+        pcq_columns tail = *cols;
+        tail.xyz = (const uint8_t *)cols->xyz + 12 * rest_first;
+        tail.cls = (const uint8_t *)cols->cls + 8 * rest_first;
         tail.rgb = nullptr;
         tail.n = cols->n - rest_first;
         return pcq_scan_dev(ctx, &tail, pred, c, stream);

@@ -112,6 +112,20 @@ struct DevCombinedSegment {
     uint32_t pat;          // class byte replicated x4
 };
 
+// One segment of a batched box AND time count launch (scan_count_bounds_time.hip): DevCombinedSegment with the time block in
+// place of the class block, and the range.  At its own pitch in the same buffers.
+struct DevBoundsTimeSegment {
+    const int4 *xyz;       // 16-byte aligned positions block
+    const uint8_t *times;  // packed f64 GPS times of the same points, 8-byte aligned
+    uint64_t n;            // points
+    uint64_t tile_begin;   // first global step of this segment
+    int32_t lo[3];
+    uint32_t width[3];
+    int32_t empty;
+    uint32_t _pad;
+    double t0, t1;         // [t0, t1)
+};
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -136,7 +150,7 @@ struct ChunkTime {  // GPS times of one 4096-point chunk: extremes over its non-
 struct EmitIndex {
     const int32_t *boxes;    // bounds: {mn[3], mx[3]} per chunk (integer AABB), or nullptr
     const uint32_t *hist;    // class: 256 bins per chunk, or nullptr   (box AND class: both)
-    const ChunkTime *times;  // time: one record per chunk, or nullptr (alone)
+    const ChunkTime *times;  // time: one record per chunk, or nullptr (alone; box AND time: with the boxes)
     uint64_t covered_tiles;
 };
 enum { CHUNK_SCAN = 0, CHUNK_NONE = 1, CHUNK_ALL = 2 };  // straddling: read it · disjoint: no match · contained: every point matches
@@ -352,7 +366,7 @@ int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const D
 // scan_generic.hip
 int pcq_launch_generic_count(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred,
                              uint64_t *d_count, hipStream_t s);
-// ix (optional): the count pass takes each tile's state from the chunk index first (bounds, class, box AND class or time predicates)
+// ix (optional): the count pass takes each tile's state from the chunk index first (bounds, class, time, box AND class or box AND time predicates)
 int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pred, uint8_t *d_out31, const uint64_t *d_npoints_in,
                            uint64_t *d_npoints_out, hipStream_t s, const EmitIndex *ix = nullptr);
 // collectors.hip: pcq_scan_dev on stream s; ix (optional) is handed to the buffer collector's emit

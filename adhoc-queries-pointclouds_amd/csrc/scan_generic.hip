@@ -173,17 +173,20 @@ __device__ __forceinline__ void tile_load_and_test(const DevCols &c, const DevPr
 // counted as without the index.
 // INDEX_BOUNDS_CLASS (PCQ_PRED_BOUNDS_CLASS, pcq_scan_dev_indexed_combined): both parts, combined by index_combined_state.
 // INDEX_TIME (PCQ_PRED_TIME, pcq_scan_dev_indexed_time): the time part, tile t in the 4096-point chunk t >> 1.
-enum { INDEX_NONE = 0, INDEX_BOUNDS = 1, INDEX_CLASS = 2, INDEX_BOUNDS_CLASS = 3, INDEX_TIME = 4 };
+// INDEX_BOUNDS_TIME (PCQ_PRED_BOUNDS_TIME, pcq_scan_dev_indexed_bounds_time): the boxes and the times of that same chunk, combined
+// by index_combined_state.
+enum { INDEX_NONE = 0, INDEX_BOUNDS = 1, INDEX_CLASS = 2, INDEX_BOUNDS_CLASS = 3, INDEX_TIME = 4, INDEX_BOUNDS_TIME = 5 };
 template <int IDX>
 __device__ __forceinline__ int tile_index_state(const EmitIndex &ix, const DevPred &pr, uint64_t n, uint64_t tile) {
     if (tile >= ix.covered_tiles) return CHUNK_SCAN;
     if (IDX == INDEX_TIME) return index_time_state(ix.times[tile >> 1], pr.wmin[0], pr.wmax[0]);
     int box_state = CHUNK_ALL;
-    if (IDX == INDEX_BOUNDS || IDX == INDEX_BOUNDS_CLASS) {
+    if (IDX == INDEX_BOUNDS || IDX == INDEX_BOUNDS_CLASS || IDX == INDEX_BOUNDS_TIME) {
         const int32_t *b = ix.boxes + (tile >> 1) * 6;  // 4096-point chunk = tiles 2c, 2c + 1
         const int32_t mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
         box_state = index_box_state(mn, mx, pr);
         if (IDX == INDEX_BOUNDS) return box_state;
+        if (IDX == INDEX_BOUNDS_TIME) return index_combined_state(box_state, index_time_state(ix.times[tile >> 1], pr.wmin[0], pr.wmax[0]));
     }
     const uint64_t ch = tile >> 5, first = ch * INDEX_CLASS_CHUNK;  // 65536-point chunk = tiles 32c .. 32c + 31
     const int class_state = index_class_state(ix.hist[ch * 256 + (pr.cls & 255u)], n - first < INDEX_CLASS_CHUNK ? n - first : INDEX_CLASS_CHUNK);
@@ -572,6 +575,8 @@ int pcq_launch_emit_points(pcq_ctx *ctx, const DevCols &cols, const DevPred &pre
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false, INDEX_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (ix && pred.kind == PCQ_PRED_BOUNDS_CLASS && ix->boxes && ix->hist)
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_CLASS, false, INDEX_BOUNDS_CLASS>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
+    else if (ix && pred.kind == PCQ_PRED_BOUNDS_TIME && ix->boxes && ix->times)
+        hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_BOUNDS_TIME, false, INDEX_BOUNDS_TIME>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (ix && pred.kind == PCQ_PRED_TIME && ix->times)
         hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_TIME, false, INDEX_TIME>), g, b, 0, s, cols, pred, counts, bits, park, park_max, *ix);
     else if (pred.kind == PCQ_PRED_CLASS) hipLaunchKernelGGL((k_tile_counts<PCQ_PRED_CLASS, false>), g, b, 0, s, cols, pred, counts, bits, park, park_max, EmitIndex{});

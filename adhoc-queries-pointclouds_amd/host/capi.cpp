@@ -357,3 +357,21 @@ extern "C" int pcq_query_resident_search_bounds_class(pcq_host_resident *r, cons
     if (!st.ok()) return done(st);
     return done(r->ds->search_bounds_class(b, cls, *c->c));
 }
+extern "C" int pcq_query_resident_count_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
+                                                    uint64_t *matches, uint64_t *points_scanned) {
+    if (!r || !bmin || !bmax || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);  // PCQ_ERR_PANIC for min > max
+    if (!st.ok()) return done(st);
+    return done(r->ds->count_bounds_time(b, start, end, matches, points_scanned));
+}
+extern "C" int pcq_query_resident_search_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
+                                                     pcq_host_collector *c) {
+    if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);  // PCQ_ERR_PANIC for min > max
+    if (!st.ok()) return done(st);
+    st = resident_collector_ok(r, c);
+    if (!st.ok()) return done(st);
+    return done(r->ds->search_bounds_time(b, start, end, *c->c));
+}

@@ -392,11 +392,13 @@ public:
     Status count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
+    Status count_bounds_time(const AABB &bounds, double start, double end, uint64_t *matches, uint64_t *points_scanned = nullptr);  // (with_times)
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
     Status search_bounds_class(const AABB &bounds, uint8_t cls, ResultCollector &rc);
     Status search_time(double start, double end, ResultCollector &rc);  // (a dataset loaded with_times; any collector)
+    Status search_bounds_time(const AABB &bounds, double start, double end, ResultCollector &rc);  // (the same)
     // chunk-index statistics of the last search_*, summed over the files it scanned through the index
     Status last_stats(pcq_index_stats *out);
     size_t files() const { return files_.size(); }

@@ -17,6 +17,10 @@
 //
 // GPS time (search_time): a dataset loaded with its time blocks answers the LAST time search over them, count and buffer
 // collectors through the time part of the file's index (pcq_scan_dev_indexed_time).
+//
+// Box AND time (count_bounds_time / search_bounds_time): the positions and time blocks of such a dataset side by side — the count is
+// one pcq_scan_dev_count_batch_bounds_time, the search goes through the bounds and time parts of the file's index
+// (pcq_scan_dev_indexed_bounds_time).
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -171,10 +175,42 @@ Status ResidentDataset::count_bounds_class(const AABB &bounds, uint8_t cls, uint
     return Status::FromLib(rc);
 }
 
+// `--combine --bounds --time` over the dataset, count only: the prologue of count_bounds_class per file, then one batched launch
+// over the positions and time blocks of the surviving files (pcq_scan_dev_count_batch_bounds_time).
+Status ResidentDataset::count_bounds_time(const AABB &bounds, double start, double end, uint64_t *matches, uint64_t *points_scanned) {
+    if (!with_times_)
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
+    std::vector<pcq_columns> cols;
+    std::vector<pcq_predicate> preds;
+    uint64_t scanned = 0;
+    for (const auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_BOUNDS_TIME;
+        pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
+        pred.wmax[0] = end;
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
+        pcq_columns c{};
+        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
+        c.cls = f.time, c.cls_stride = 8;
+        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
+        cols.push_back(c);
+        preds.push_back(pred);
+        scanned += c.n;
+    }
+    if (points_scanned) *points_scanned = scanned;
+    int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
+    if (!rc && !cols.empty()) rc = pcq_scan_dev_count_batch_bounds_time(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
+    if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
+    return Status::FromLib(rc);
+}
+
 // One file of the search_* : execute_plan (search.cpp) with the resident blocks in place of the file.
 Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc) {
     const uint64_t n = f.header.number_of_points;
-    const bool time = pred.kind == PCQ_PRED_TIME;
+    const bool time = pred.kind == PCQ_PRED_TIME || pred.kind == PCQ_PRED_BOUNDS_TIME;
     pcq_columns c{};
     c.xyz = f.xyz, c.xyz_stride = 12;  // last.rs:114-121
     c.cls = f.cls, c.cls_stride = 1;   // :138-142
@@ -191,7 +227,8 @@ Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultC
             r = pcq_index_new(ctx_, &f.index);
             if (r) return Status::FromLib(r);
         }
-        r = time                                 ? pcq_scan_dev_indexed_time(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
+        r = pred.kind == PCQ_PRED_TIME           ? pcq_scan_dev_indexed_time(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
+            : pred.kind == PCQ_PRED_BOUNDS_TIME  ? pcq_scan_dev_indexed_bounds_time(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
             : pred.kind == PCQ_PRED_BOUNDS_CLASS ? pcq_scan_dev_indexed_combined(ctx_, &c, &pred, f.index, rc.handle(), nullptr)
                                                  : pcq_scan_dev_indexed(ctx_, &c, &pred, f.index, rc.handle(), nullptr);
         if (!r) last_indices_.push_back(f.index);
@@ -267,6 +304,28 @@ Status ResidentDataset::search_time(double start, double end, ResultCollector &r
         pred.kind = PCQ_PRED_TIME;
         pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
         pred.wmax[0] = end;
+        Status st = scan(f, pred, rc);
+        if (!st.ok()) return st;
+    }
+    return Status::Ok();
+}
+
+// The combined time search of search.cpp for every file: the prologue of search_bounds (the header early-out leaves the
+// collector's file-order index where it was), then box AND time in one scan — through the bounds and time parts of the file's
+// chunk index for count and buffer collectors.  Any collector: the records carry class 0 and colour (0,0,0).
+Status ResidentDataset::search_bounds_time(const AABB &bounds, double start, double end, ResultCollector &rc) {
+    if (!with_times_)
+        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
+    last_indices_.clear();
+    for (auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
+        pcq_predicate pred{};
+        pred.kind = PCQ_PRED_BOUNDS_TIME;
+        pred.wmin[0] = start;
+        pred.wmax[0] = end;
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
         Status st = scan(f, pred, rc);
         if (!st.ok()) return st;
     }

@@ -247,6 +247,13 @@ int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_pr
  * other predicate kind or layout is refused (PCQ_ERR_ARG) before anything is launched. */
 int pcq_scan_dev_count_batch_combined(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
                                       size_t nsegments, uint64_t *device_total, void *stream);
+/* The same for box AND time: every predicate is PCQ_PRED_BOUNDS_TIME, and segment i — packed positions (xyz_stride 12, 16-byte
+ * aligned) beside the packed f64 GPS times of the same points in cols[i].cls (cls_stride 8, 8-byte aligned: 0 or 8 modulo 16,
+ * non-null when n > 0) — is counted with the box and the range [wmin[0], wmax[0]) of preds[i] (an empty or NaN range matches
+ * nothing); the total is ADDED to *device_total.  nsegments == 0 is PCQ_OK.  Any other predicate kind or layout is refused
+ * (PCQ_ERR_ARG) before anything is launched or uploaded. */
+int pcq_scan_dev_count_batch_bounds_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
+                                         size_t nsegments, uint64_t *device_total, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step
@@ -308,6 +315,20 @@ int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *cols, const p
  * changes the bounds and class parts, and pcq_scan_dev_indexed / _combined neither read nor change the time part. */
 int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
                               pcq_collector *c, void *stream);
+/* PCQ_PRED_BOUNDS_TIME (only; other kinds PCQ_ERR_ARG) through the bounds part AND the time part of the same index object, count
+ * and buffer collectors (grid: PCQ_ERR_ARG).  The parts are those of pcq_scan_dev_indexed / _combined (keyed on the positions
+ * pointer and n) and of pcq_scan_dev_indexed_time (keyed on the time pointer and n): a part an earlier scan built is used as it
+ * is, a missing part is built first and serves those entries later; then the pruned pass runs, on the building call too.  Both
+ * parts have the same 4096-point chunks; a chunk takes its box state together with its time state: no match in either ->
+ * skipped, nothing read; both contained -> counted whole, nothing read; everything else -> its 48 KiB of positions and its 32 KiB
+ * of times are read.  Results and records are pcq_scan_dev's for PCQ_PRED_BOUNDS_TIME, byte for byte and in order (position,
+ * class 0, colour (0,0,0)), behind what the collector holds; the ragged tail behind the last whole chunk is always read, with its
+ * own positions and times.  Covered: packed positions and a packed time column (pcq_columns.cls, cls_stride 8), each 16-byte
+ * aligned, at least 4096 points; any other layout, and a predicate that can match nothing (a box outside the i32 range, an
+ * empty or NaN range), falls through to pcq_scan_dev with all-zero statistics and leaves the index untouched.  Statistics in
+ * 4096-point chunks: chunks = n / 4096 = skipped + whole + scanned, built = 1 when this call built either part. */
+int pcq_scan_dev_indexed_bounds_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred, pcq_index *ix,
+                                     pcq_collector *c, void *stream);
 
 /* The one collective of the path (main.rs:164-180) for callers that drive n GPUs from ONE process:
  * recv[i][0] = the sum over i of send[i][0] (8 bytes each in ctxs[i]'s HBM, e.g. the counter of

@@ -131,6 +131,20 @@ int pcq_query_resident_load_with(int device, const char *const *files, size_t nf
  * chunk index (pcq_scan_dev_indexed_time), grid collectors through pcq_scan_dev.  Needs a dataset loaded with
  * PCQ_RESIDENT_TIME (else PCQ_ERR_ARG) and no colour blocks, whatever the collector: a time record's colour is (0,0,0). */
 int pcq_query_resident_search_time(pcq_host_resident *r, double start, double end, pcq_host_collector *c);
+/* Box AND time, count only (`--combine --bounds ... --time`): the per-file prologue of pcq_query_resident_count_bounds_class
+ * (header early-out, box conversion; PCQ_ERR_PANIC for min > max) + ONE batched launch over the positions and time blocks of
+ * the surviving files (pcq_scan_dev_count_batch_bounds_time).  points_scanned: the points of the files whose headers meet the
+ * box.  Needs a dataset loaded with PCQ_RESIDENT_TIME (else PCQ_ERR_ARG). */
+int pcq_query_resident_count_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
+                                         uint64_t *matches, uint64_t *points_scanned);
+/* == pcq_query_search_file_bounds_time(path, bmin, bmax, start, end, optimized=1, c) for every loaded file, in load order, into
+ * ONE collector: the same count, the same records byte for byte and in order (class 0, colour (0,0,0), whether or not colour
+ * blocks are loaded), the same grid cells and winners; the header early-out leaves the collector's file-order index where it
+ * was.  Count and buffer collectors go through the bounds and time parts of each file's chunk index
+ * (pcq_scan_dev_indexed_bounds_time: the parts are those of search_bounds and search_time, built by whichever comes first);
+ * grid collectors through pcq_scan_dev.  Needs a dataset loaded with PCQ_RESIDENT_TIME (else PCQ_ERR_ARG). */
+int pcq_query_resident_search_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
+                                          pcq_host_collector *c);
 /* Index statistics of the last resident search, summed over its files (those it scanned through an index; none for a grid
  * collector).  Waits for the search's scans. */
 int pcq_query_resident_last_stats(pcq_host_resident *r, pcq_index_stats *out);

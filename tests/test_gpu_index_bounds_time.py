@@ -1,0 +1,374 @@
+"""pcq_scan_dev_indexed_bounds_time: PCQ_PRED_BOUNDS_TIME through the bounds part AND the time part of the chunk index (an
+integer AABB and {min, max, NaN count} per 4096 points), against numpy, pcq_scan_dev on the same columns and the numpy model of
+the chunk states (_bounds_time_index_model.py), which gives the exact skipped / whole / scanned of every pruned scan.
+
+One column set of 12 x 4096 + 17 points, built chunk by chunk so that every state is there by construction:
+  chunks 0-8   the nine pairs (box state, time state) in {NONE, SCAN, ALL}^2.  In a SCAN chunk the box keeps the points with
+               j % 2 == 0 and the range those with j % 3 == 0, so AND differs from either side alone; in chunk 5 (box SCAN, time
+               ALL) the box keeps even j of the second 2048-point emit tile only.
+  chunk 9      box ALL, every time NaN                          -> NONE
+  chunk 10     box ALL, all times in range except one NaN       -> SCAN, 4095 matches
+  chunk 11     box ALL, max time == end exactly                 -> SCAN, 4095 matches
+  the tail     17 points with matches of their own (the column's first 17 points have none)
+"""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _bounds_time_index_model as bm  # noqa: E402
+import _time_images as ti  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+POINT_DTYPE = binding.POINT_DTYPE
+CH = bm.CHUNK
+NONE, SCAN, ALL = bm.NONE, bm.SCAN, bm.ALL
+N = 12 * CH + 17
+LO, HI = [0, -100, -100], [999, 100, 100]
+T0, T1 = 1000.0, 2000.0
+SC = dict(scale=list(ti.SCALE), offset=list(ti.OFFSET))
+PAIRS = [(b, t) for b in (NONE, SCAN, ALL) for t in (NONE, SCAN, ALL)]
+SECOND_TILE_ONLY = 5
+PCQ_ERR_ARG = -8
+
+
+class Dev:
+    """Device copies of host arrays, freed together."""
+
+    def __init__(self, ctx):
+        self.ctx, self.blocks = ctx, []
+
+    def put(self, arr, pad=0):
+        arr = np.ascontiguousarray(arr)
+        base = self.ctx.alloc(arr.nbytes + 64 + pad)
+        self.blocks.append(base)
+        self.ctx.to_device(base + pad, arr)
+        return base + pad
+
+    def free(self):
+        for b in self.blocks:
+            self.ctx.free(b)
+        self.blocks = []
+
+
+def chunk_x(state, j, second_tile_only=False):
+    if state == NONE:
+        return 5000 + j % 100
+    if state == ALL:
+        return j % 1000
+    keep = (j % 2 == 0) & ((j >= 2048) if second_tile_only else True)
+    return np.where(keep, j % 1000, 5000 + j)
+
+
+def chunk_t(state, j):
+    if state == NONE:
+        return 3000.0 + j * 0.001
+    if state == ALL:
+        return T0 + j * 0.1  # (min == start: a match)
+    return np.where(j % 3 == 0, 1500.0 + j * 0.01, 2500.0 + j * 0.01)
+
+
+def build():
+    rng = np.random.default_rng(99)
+    j = np.arange(CH)
+    xs, ts = [], []
+    for k, (b, t) in enumerate(PAIRS):
+        xs.append(chunk_x(b, j, k == SECOND_TILE_ONLY))
+        ts.append(chunk_t(t, j))
+    xs += [chunk_x(ALL, j)] * 3
+    ts.append(np.full(CH, np.nan))                     # chunk 9
+    one_nan = chunk_t(ALL, j)
+    one_nan[1234] = np.nan
+    ts.append(one_nan)                                 # chunk 10
+    ts.append(np.linspace(T0, T1, CH))                 # chunk 11: max == end
+    jt = np.arange(17)
+    xs.append(np.where(jt % 3 != 0, jt, 7000))         # the tail: inside for j % 3 != 0 ...
+    ts.append(np.where(jt % 2 == 0, 1200.0 + jt, 2600.0))  # ... in range for even j
+    x = np.concatenate(xs)
+    xyz = np.stack([x, rng.integers(-100, 101, N), rng.integers(-100, 101, N)], axis=1).astype(np.int32)
+    t = np.concatenate(ts).astype(np.float64)
+    assert len(t) == N == len(xyz)
+    return xyz, t
+
+
+def checked_data():
+    """The column set, with every state asserted from numpy's min / max before any GPU call."""
+    xyz, t = build()
+    sel = bm.select(xyz, t, LO, HI, T0, T1)
+    pairs = bm.pairs(xyz, t, LO, HI, T0, T1)
+    assert pairs[:9] == PAIRS
+    assert pairs[9:] == [(ALL, NONE), (ALL, SCAN), (ALL, SCAN)]
+    assert float(t[11 * CH: 12 * CH].max()) == T1 and np.isnan(t[9 * CH: 10 * CH]).all() and int(np.isnan(t[10 * CH: 11 * CH]).sum()) == 1
+    assert bm.classify(xyz[:9 * CH], t[:9 * CH], LO, HI, T0, T1) == (5, 1, 3)
+    assert bm.classify(xyz, t, LO, HI, T0, T1) == (6, 1, 5)
+    per = [int(sel[CH * c: CH * (c + 1)].sum()) for c in range(12)]
+    assert per[10] == CH - 1 and per[11] == CH - 1 and per[8] == CH and per[9] == 0
+    # AND differs from either side alone in the (SCAN, SCAN) chunk; chunk 5 matches in its second emit tile only
+    c = PAIRS.index((SCAN, SCAN))
+    assert per[c] == len(range(0, CH, 6)) and per[c] not in (CH // 2, len(range(0, CH, 3)))
+    assert int(sel[5 * CH: 5 * CH + 2048].sum()) == 0 and int(sel[5 * CH + 2048: 6 * CH].sum()) == 1024
+    assert 0 < int(sel[12 * CH:].sum()) < 17 and int(sel[:17].sum()) == 0
+    return xyz, t, sel
+
+
+@pytest.fixture(scope="module")
+def data():
+    return checked_data()
+
+
+def stats3(st):
+    return st["skipped"], st["whole"], st["scanned"]
+
+
+def run(ctx, cols, pred, kind, ix=None, stream=None, entry="bounds_time"):
+    """The count, or the records as bytes, of one scan into a fresh collector: plain (ix None) or through the index."""
+    g = ctx.count_collector() if kind == "count" else ctx.buffer_collector()
+    try:
+        if ix is None:
+            ctx.scan_dev(cols, pred, g, stream)
+        else:
+            {"bounds_time": ctx.scan_dev_indexed_bounds_time, "bounds": ctx.scan_dev_indexed, "time": ctx.scan_dev_indexed_time,
+             "combined": ctx.scan_dev_indexed_combined}[entry](cols, pred, ix, g, stream)
+        return g.point_count() if kind == "count" else g.points().tobytes()
+    finally:
+        g.free()
+
+
+def expected(xyz, t, lo, hi, start, end, kind):
+    sel = bm.select(xyz, t, lo, hi, start, end)
+    return int(sel.sum()) if kind == "count" else ti.expect_records(xyz, sel, POINT_DTYPE).tobytes()
+
+
+OTHER_QUERIES = [([0, -100, -100], [999, 100, 100], 1500.0, 1520.48),   # a short range: cuts the SCAN time chunks
+                 ([0, -50, -100], [499, 50, 100], T0, T1),             # a smaller box: no chunk is box ALL
+                 ([-2**31] * 3, [2**31 - 1] * 3, -np.inf, np.inf),     # everything but the NaNs
+                 ([0, -100, -100], [999, 100, 100], 2500.0, 2600.0),   # the other side of the SCAN time chunks
+                 ([5000, -100, -100], [5099, 100, 100], 3000.0, 3001.0)]  # the NONE, NONE chunk's points
+
+
+def test_count_on_the_building_call_and_later(gpu_ctx, data):
+    ctx = gpu_ctx
+    xyz, t, sel = data
+    want = int(sel.sum())
+    dev, ix = Dev(ctx), ctx.index_new()
+    try:
+        cols = binding.make_columns(xyz=dev.put(xyz), cls=dev.put(t), n=N, cls_stride=8, **SC)
+        pred = pkg.Predicate.bounds_time(LO, HI, T0, T1)
+        assert run(ctx, cols, pred, "count") == want
+        for k in range(3):
+            assert run(ctx, cols, pred, "count", ix) == want, k
+            st = ctx.index_stats(ix)
+            assert st == dict(chunks=12, skipped=6, whole=1, scanned=5, built=1 if k == 0 else 0), (k, st)
+        for lo, hi, start, end in OTHER_QUERIES:
+            p = pkg.Predicate.bounds_time(lo, hi, start, end)
+            got, st = run(ctx, cols, p, "count", ix), ctx.index_stats(ix)
+            assert got == expected(xyz, t, lo, hi, start, end, "count") == run(ctx, cols, p, "count"), (lo, hi, start, end)
+            assert st["built"] == 0 and st["chunks"] == 12 and stats3(st) == bm.classify(xyz, t, lo, hi, start, end), (lo, hi, start, end, st)
+    finally:
+        ctx.index_free(ix)
+        dev.free()
+
+
+def test_records_equal_the_plain_scan_behind_what_the_collector_holds_on_a_callers_stream(gpu_ctx, data):
+    import torch
+    ctx = gpu_ctx
+    xyz, t, sel = data
+    dev, ix = Dev(ctx), ctx.index_new()
+    ts = torch.cuda.Stream()
+    try:
+        # (a colour column is ignored: a time record's colour is (0,0,0))
+        rgb = np.full((N, 3), 777, dtype=np.uint16)
+        cols = binding.make_columns(xyz=dev.put(xyz), cls=dev.put(t), rgb=dev.put(rgb), n=N, cls_stride=8, **SC)
+        pred = pkg.Predicate.bounds_time(LO, HI, T0, T1)
+        plain = run(ctx, cols, pred, "buffer")
+        assert plain == ti.expect_records(xyz, sel, POINT_DTYPE).tobytes() and len(plain) == 31 * int(sel.sum())
+        for k in range(2):
+            assert run(ctx, cols, pred, "buffer", ix) == plain, k
+            st = ctx.index_stats(ix)
+            assert st == dict(chunks=12, skipped=6, whole=1, scanned=5, built=1 if k == 0 else 0), (k, st)
+        lo, hi, start, end = OTHER_QUERIES[0]
+        other = pkg.Predicate.bounds_time(lo, hi, start, end)
+        first = run(ctx, cols, other, "buffer")
+        assert first == expected(xyz, t, lo, hi, start, end, "buffer") and 0 < len(first) < len(plain)
+        gb = ctx.buffer_collector()
+        ctx.scan_dev(cols, other, gb)                                           # records of a plain scan first
+        ctx.scan_dev_indexed_bounds_time(cols, pred, ix, gb)                    # a pruned call appends
+        ctx.scan_dev_indexed_bounds_time(cols, other, ix, gb, ts.cuda_stream)   # ... and on the caller's stream
+        assert stats3(ctx.index_stats(ix)) == bm.classify(xyz, t, lo, hi, start, end)
+        ctx.scan_dev_indexed_bounds_time(cols, pred, ix, gb, ts.cuda_stream)
+        assert gb.points().tobytes() == first + plain + first + plain
+        gb.free()
+        cc = ctx.count_collector()
+        ctx.scan_dev_indexed_bounds_time(cols, pred, ix, cc, ts.cuda_stream)
+        ctx.scan_dev_indexed_bounds_time(cols, other, ix, cc)
+        assert cc.point_count() == (len(plain) + len(first)) // 31
+        cc.free()
+        for lo, hi, start, end in OTHER_QUERIES[1:]:
+            p = pkg.Predicate.bounds_time(lo, hi, start, end)
+            assert run(ctx, cols, p, "buffer", ix) == expected(xyz, t, lo, hi, start, end, "buffer") == run(ctx, cols, p, "buffer")
+            assert stats3(ctx.index_stats(ix)) == bm.classify(xyz, t, lo, hi, start, end)
+    finally:
+        ctx.index_free(ix)
+        dev.free()
+
+
+def test_the_parts_are_shared_with_the_bounds_and_time_scans_in_both_directions(gpu_ctx, data):
+    ctx = gpu_ctx
+    xyz, t, sel = data
+    want = int(sel.sum())
+    dev = Dev(ctx)
+    a, b, c = ctx.index_new(), ctx.index_new(), ctx.index_new()
+    try:
+        cols = binding.make_columns(xyz=dev.put(xyz), cls=dev.put(t), n=N, cls_stride=8, **SC)
+        pred, bpred, tpred = pkg.Predicate.bounds_time(LO, HI, T0, T1), pkg.Predicate.bounds(LO, HI), pkg.Predicate.time_range(T0, T1)
+        want_b = int(np.all((xyz >= np.asarray(LO)) & (xyz <= np.asarray(HI)), axis=1).sum())
+        want_t = int(ti.select(t, T0, T1).sum())
+        # built by the old entries, used by the new one
+        assert run(ctx, cols, bpred, "count", a, entry="bounds") == want_b and ctx.index_stats(a)["built"] == 1
+        assert run(ctx, cols, tpred, "count", a, entry="time") == want_t and ctx.index_stats(a)["built"] == 1
+        assert run(ctx, cols, pred, "count", a) == want
+        assert ctx.index_stats(a) == dict(chunks=12, skipped=6, whole=1, scanned=5, built=0)
+        # built by the new entry alone, used by the old ones
+        assert run(ctx, cols, pred, "count", b) == want and ctx.index_stats(b)["built"] == 1
+        assert run(ctx, cols, bpred, "count", b, entry="bounds") == want_b
+        st = ctx.index_stats(b)
+        assert st["built"] == 0 and sum(stats3(st)) == 12 and st["skipped"] == 3, st
+        assert run(ctx, cols, tpred, "count", b, entry="time") == want_t
+        st = ctx.index_stats(b)
+        assert st["built"] == 0 and sum(stats3(st)) == 12 and st["skipped"] == 4, st
+        # half an index: only the times exist -> the new entry builds the boxes (a buffer scan), which then serve a bounds scan
+        assert run(ctx, cols, tpred, "count", c, entry="time") == want_t
+        assert len(run(ctx, cols, pred, "buffer", c)) == 31 * want and ctx.index_stats(c)["built"] == 1
+        assert run(ctx, cols, bpred, "count", c, entry="bounds") == want_b and ctx.index_stats(c)["built"] == 0
+        assert run(ctx, cols, pred, "count", c) == want and ctx.index_stats(c)["built"] == 0
+    finally:
+        for ix in (a, b, c):
+            ctx.index_free(ix)
+        dev.free()
+
+
+def test_what_the_index_does_not_cover_falls_through_and_leaves_it_alone(gpu_ctx, data):
+    ctx = gpu_ctx
+    xyz, t, sel = data
+    dev = Dev(ctx)
+    ix, fresh = ctx.index_new(), ctx.index_new()
+    try:
+        d_xyz = dev.put(xyz)
+        cols = binding.make_columns(xyz=d_xyz, cls=dev.put(t), n=N, cls_stride=8, **SC)
+        pred = pkg.Predicate.bounds_time(LO, HI, T0, T1)
+        run(ctx, cols, pred, "count", ix)
+        assert run(ctx, cols, pred, "count", ix) == int(sel.sum())
+        before = ctx.index_stats(ix)
+        assert before == dict(chunks=12, skipped=6, whole=1, scanned=5, built=0)
+        rec = ti.records(1, xyz, np.zeros(N, dtype=np.uint8), np.zeros((N, 3), dtype=np.uint16), t)  # LAS format 1: the time at +20
+        p = dev.put(rec)
+        uncovered = [(binding.make_columns(xyz=d_xyz, cls=dev.put(t, pad=8), n=N, cls_stride=8, **SC), N, pred),   # times at 8 mod 16
+                     (binding.make_columns(xyz=dev.put(xyz, pad=4), cls=cols.cls, n=N, cls_stride=8, **SC), N, pred),  # positions off 16
+                     (binding.make_columns(xyz=d_xyz, cls=cols.cls, n=CH - 1, cls_stride=8, **SC), CH - 1, pred),    # no whole chunk
+                     (binding.make_columns(xyz=p, cls=p + 20, n=N, xyz_stride=28, cls_stride=28, **SC), N, pred)]    # LAS records
+        # covered columns, predicates that can match nothing: a box outside the i32 range, an empty, a reversed and a NaN range
+        for q in (pkg.Predicate.bounds_time([2**31, 0, 0], [2**31 + 5, 1, 1], T0, T1), pkg.Predicate.bounds_time(LO, HI, 1500.0, 1500.0),
+                  pkg.Predicate.bounds_time(LO, HI, T1, T0), pkg.Predicate.bounds_time(LO, HI, np.nan, T1),
+                  pkg.Predicate.bounds_time(LO, HI, T0, np.nan)):
+            uncovered.append((cols, N, q))
+        for which in (ix, fresh):
+            for c, m, q in uncovered:
+                want = int(sel[:m].sum()) if q is pred else 0
+                for kind in ("count", "buffer"):
+                    got = run(ctx, c, q, kind, which)
+                    assert got == run(ctx, c, q, kind)
+                    assert (got if kind == "count" else len(got) // 31) == want, (m, kind)
+                    assert not any(ctx.index_stats(which).values())
+        assert run(ctx, cols, pred, "count", ix) == int(sel.sum())
+        assert ctx.index_stats(ix) == before           # still the parts it had
+        assert run(ctx, cols, pred, "count", fresh) == int(sel.sum())
+        assert ctx.index_stats(fresh)["built"] == 1    # nothing had been built into it
+    finally:
+        ctx.index_free(ix)
+        ctx.index_free(fresh)
+        dev.free()
+
+
+def test_refusals_of_the_new_entry_and_of_the_old_ones(gpu_ctx, data):
+    ctx = gpu_ctx
+    xyz, t, sel = data
+    dev, ix = Dev(ctx), ctx.index_new()
+    try:
+        d_xyz = dev.put(xyz)
+        tcols = binding.make_columns(xyz=d_xyz, cls=dev.put(t), n=N, cls_stride=8, **SC)
+        ccols = binding.make_columns(xyz=d_xyz, cls=dev.put(np.full(N, 6, dtype=np.uint8)), n=N, **SC)
+        pred = pkg.Predicate.bounds_time(LO, HI, T0, T1)
+        cc, gb = ctx.count_collector(), ctx.buffer_collector()
+        gg = ctx.grid_collector([-1000.0] * 3, [1000.0] * 3, 10.0)
+        bad = [(ccols, pkg.Predicate.bounds(LO, HI), cc), (ccols, pkg.Predicate.classification(6), cc), (tcols, pkg.Predicate.time_range(T0, T1), cc),
+               (ccols, pkg.Predicate.bounds_class(LO, HI, 6), gb), (ccols, pkg.Predicate.bounds_f64([-1.0] * 3, [1.0] * 3), gb), (tcols, pred, gg)]
+        for cols, p, coll in bad:
+            with pytest.raises(binding.PcqError) as e:
+                ctx.scan_dev_indexed_bounds_time(cols, p, ix, coll)
+            assert e.value.code == PCQ_ERR_ARG, p.kind
+        args = [ctx.handle, C.byref(tcols), C.byref(pred), C.c_void_p(ix), cc.handle, None]
+        for k in range(5):
+            a = list(args)
+            a[k] = None
+            assert ctx.lib.pcq_scan_dev_indexed_bounds_time(*a) == PCQ_ERR_ARG, k
+        # the validation comes before the index or the collector is touched: no positions, no times
+        for broken in (binding.make_columns(cls=tcols.cls, n=N, cls_stride=8), binding.make_columns(xyz=d_xyz, n=N, cls_stride=8)):
+            with pytest.raises(binding.PcqError) as e:
+                ctx.scan_dev_indexed_bounds_time(broken, pred, ix, cc)
+            assert e.value.code == PCQ_ERR_ARG
+        # the old entries with this kind, as before: _combined and _time refuse it, the batched counts refuse it ...
+        for entry in ("combined", "time"):
+            with pytest.raises(binding.PcqError) as e:
+                run(ctx, tcols, pred, "count", ix, entry=entry)
+            assert e.value.code == PCQ_ERR_ARG, entry
+        d_total = ctx.alloc(64)
+        ctx.memset(d_total, 0, 8)
+        for batch in (ctx.scan_dev_count_batch, ctx.scan_dev_count_batch_combined):
+            with pytest.raises(binding.PcqError) as e:
+                batch([tcols], [pred], d_total)
+            assert e.value.code == PCQ_ERR_ARG
+        out = np.ones(1, dtype=np.uint64)
+        ctx.to_host(out, d_total)
+        ctx.free(d_total)
+        assert int(out[0]) == 0
+        assert cc.point_count() == 0 and gb.point_count() == 0 and gg.point_count() == 0
+        assert not any(ctx.index_stats(ix).values())
+        # ... and pcq_scan_dev_indexed serves it unindexed: the plain scan, statistics that claim nothing, nothing built
+        for kind in ("count", "buffer"):
+            assert run(ctx, tcols, pred, kind, ix, entry="bounds") == run(ctx, tcols, pred, kind)
+            assert not any(ctx.index_stats(ix).values())
+        assert run(ctx, tcols, pred, "count", ix) == int(sel.sum()) and ctx.index_stats(ix)["built"] == 1  # nothing had been built
+        cc.free(), gb.free(), gg.free()
+    finally:
+        ctx.index_free(ix)
+        dev.free()
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 8191, 8192])
+def test_seams_of_the_chunking(gpu_ctx, data, n):
+    """One chunk exactly, one point behind it, one point short of two, two exactly — over chunks 10 and 11 (a NaN, max == end)
+    and, for the tail, the start of the tail's own data: the last n points of the column set."""
+    ctx = gpu_ctx
+    xyz, t = data[0][N - n:], data[1][N - n:]
+    dev, ix, ix2 = Dev(ctx), ctx.index_new(), ctx.index_new()
+    try:
+        cols = binding.make_columns(xyz=dev.put(xyz), cls=dev.put(t), n=n, cls_stride=8, **SC)
+        for lo, hi, start, end in [(LO, HI, T0, T1)] + OTHER_QUERIES[:3]:
+            pred = pkg.Predicate.bounds_time(lo, hi, start, end)
+            for which, kind in ((ix, "count"), (ix2, "buffer")):
+                got = run(ctx, cols, pred, kind, which)
+                st = ctx.index_stats(which)
+                assert got == expected(xyz, t, lo, hi, start, end, kind) == run(ctx, cols, pred, kind), (kind, lo, hi, start, end)
+                assert st["chunks"] == n // CH and stats3(st) == bm.classify(xyz, t, lo, hi, start, end), (kind, st)
+        assert ctx.index_stats(ix)["built"] == 0 and ctx.index_stats(ix2)["built"] == 0
+    finally:
+        ctx.index_free(ix)
+        ctx.index_free(ix2)
+        dev.free()
