@@ -407,19 +407,6 @@ __global__ __launch_bounds__(BLOCK) void k_index_count_bounds_time(const v4i *__
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_index_finish(const uint64_t *__restrict__ partials, int nblocks, uint64_t *__restrict__ d_count) {
-    __shared__ uint64_t s[BLOCK];
-    uint64_t t = 0;
-    for (int i = threadIdx.x; i < nblocks; i += BLOCK) t += partials[i];
-    s[threadIdx.x] = t;
-    __syncthreads();
-    for (int off = BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
-}
-
 // Statistics of an indexed buffer scan in index-chunk units: stats[0..2] += chunks disjoint from the predicate (not read by
 // the count pass) / contained (not read by the count pass) / straddling (read) — the classification k_tile_counts<.., IDX> took
 // its tile states from.  boxes alone: a bounds scan; hist alone: a class scan (class chunks); both: box AND class (bounds chunks);
@@ -652,7 +639,7 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
                            ix->d_boxes, ctx->d_partials, ix->d_stats);
         ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
     }
-    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
     PCQ_HIP(hipGetLastError());
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned
@@ -719,7 +706,7 @@ extern "C" int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *co
     PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_index_count_bounds_class, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
                        cols->n, chunks, dp, ix->d_boxes, ix->d_hist, ctx->d_partials, ix->d_stats);
-    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
     PCQ_HIP(hipGetLastError());
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS class bytes
@@ -813,7 +800,7 @@ extern "C" int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, 
                            ctx->d_partials, ix->d_stats);
         ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
     }
-    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
     PCQ_HIP(hipGetLastError());
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS times (and positions, when present)
@@ -882,7 +869,7 @@ extern "C" int pcq_scan_dev_indexed_bounds_time(pcq_ctx *ctx, const pcq_columns 
     // (both builders wrote the partials; the pruned count writes every one of the `grid` again before they are summed)
     hipLaunchKernelGGL(k_index_count_bounds_time, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
                        chunks, dp, ix->d_boxes, ix->d_times, ctx->d_partials, ix->d_stats);
-    hipLaunchKernelGGL(k_index_finish, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
+    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
     PCQ_HIP(hipGetLastError());
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS positions and ITS times

@@ -1024,14 +1024,9 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         const int src = pcq_scratch_stream(ctx, s);
         if (src) return src;
     }
-    {
-        const int trc = pcq_ensure_segment_table(ctx, nsegments * sizeof(DevSegment));
-        if (trc) return trc;
-    }
     static_assert(sizeof(DevClassSegment) <= sizeof(DevSegment), "the two segment tables share one buffer");
     const int kind = preds[0].kind;
-    // Build the segment table; it is uploaded only when it differs from the one already in HBM
-    // (a repeated query re-launches without touching the pinned buffer, so no host-side wait).
+    // Build the segment table (pcq_upload_segment_table: it travels only when it differs from the one already in HBM)
     std::vector<DevSegment> table(nsegments);
     memset(table.data(), 0, nsegments * sizeof(DevSegment));
     uint64_t tiles = 0, points = 0;
@@ -1069,13 +1064,9 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         tiles += cols[i].n / ((uint64_t)batch_tiles_per_step(ctx->batch_variant) * TILE_POINTS);
         points += cols[i].n;
     }
-    if (ctx->segments_uploaded != nsegments || ctx->segments_kind != kind ||
-        memcmp(ctx->h_segments, table.data(), nsegments * sizeof(DevSegment)) != 0) {
-        PCQ_HIP(hipStreamSynchronize(s));  // the previous upload from the pinned table must have been consumed
-        memcpy(ctx->h_segments, table.data(), nsegments * sizeof(DevSegment));
-        PCQ_HIP(hipMemcpyAsync(ctx->d_segments, ctx->h_segments, nsegments * sizeof(DevSegment), hipMemcpyHostToDevice, s));
-        ctx->segments_uploaded = nsegments;
-        ctx->segments_kind = kind;
+    {
+        const int urc = pcq_upload_segment_table(ctx, kind, nsegments, table.data(), nsegments * sizeof(DevSegment), s);
+        if (urc) return urc;
     }
     if (kind == PCQ_PRED_CLASS && ctx->class_batch_loads) {  // one wave per workgroup, class_batch_loads KiB per step
         uint64_t g = (uint64_t)ctx->num_cus * ctx->class_batch_waves_per_cu;

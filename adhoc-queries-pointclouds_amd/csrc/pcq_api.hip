@@ -223,8 +223,9 @@ int pcq_ensure_partials(pcq_ctx *ctx, size_t n) {
     return PCQ_OK;
 }
 
-// The segment tables of the batched count kernels (DevSegment, DevClassSegment, DevCombinedSegment) share one pinned buffer
-// and its device twin, sized in bytes.
+// The segment tables of the batched count kernels (DevSegment: box, DevClassSegment: class at DevSegment pitch,
+// DevCombinedSegment: box AND class, DevBoundsTimeSegment: box AND time) share one pinned buffer and its device twin, sized
+// in bytes.
 int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->segments_cap) return PCQ_OK;
     if (ctx->d_segments) (void)hipFree(ctx->d_segments);
@@ -237,6 +238,22 @@ int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes) {
     PCQ_HIP(hipMalloc((void **)&ctx->d_segments, cap));
     PCQ_HIP(hipHostMalloc((void **)&ctx->h_segments, cap, hipHostMallocDefault));
     ctx->segments_cap = cap;
+    return PCQ_OK;
+}
+
+// A batched count's table into d_segments, on stream s.  It travels only when it differs from the table already in HBM: a
+// repeated query re-launches without touching the pinned buffer, so no host-side wait.  The byte compare alone decides that
+// today: a table of another kind has another layout, so its bytes differ; the kind in the key only keeps this true should
+// two kinds ever share a layout.
+int pcq_upload_segment_table(pcq_ctx *ctx, int kind, size_t nsegments, const void *table, size_t bytes, hipStream_t s) {
+    const int rc = pcq_ensure_segment_table(ctx, bytes);
+    if (rc) return rc;
+    if (ctx->segments_uploaded == nsegments && ctx->segments_kind == kind && memcmp(ctx->h_segments, table, bytes) == 0) return PCQ_OK;
+    PCQ_HIP(hipStreamSynchronize(s));  // the previous upload from the pinned table must have been consumed
+    memcpy(ctx->h_segments, table, bytes);
+    PCQ_HIP(hipMemcpyAsync(ctx->d_segments, ctx->h_segments, bytes, hipMemcpyHostToDevice, s));
+    ctx->segments_uploaded = nsegments;
+    ctx->segments_kind = kind;
     return PCQ_OK;
 }
 

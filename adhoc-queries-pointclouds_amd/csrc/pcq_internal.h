@@ -99,7 +99,7 @@ struct DevClassSegment {
     uint32_t _pad;
 };
 
-// One segment of a batched box AND class count launch (scan_count_combined.hip): DevSegment with the class block beside it.
+// One segment of a batched box AND class count launch (scan_count_batch.hip): DevSegment with the class block beside it.
 // Tables of these live in the same d_segments / h_segments buffers at their own pitch.
 struct DevCombinedSegment {
     const int4 *xyz;       // 16-byte aligned positions block
@@ -112,7 +112,7 @@ struct DevCombinedSegment {
     uint32_t pat;          // class byte replicated x4
 };
 
-// One segment of a batched box AND time count launch (scan_count_bounds_time.hip): DevCombinedSegment with the time block in
+// One segment of a batched box AND time count launch (scan_count_batch.hip): DevCombinedSegment with the time block in
 // place of the class block, and the range.  At its own pitch in the same buffers.
 struct DevBoundsTimeSegment {
     const int4 *xyz;       // 16-byte aligned positions block
@@ -351,6 +351,9 @@ int pcq_collector_wait_last(const pcq_collector *c, hipStream_t s);
 int pcq_ensure_partials(pcq_ctx *ctx, size_t n);
 // pcq_api.hip: d_segments / h_segments hold at least `bytes` each (a table that grows forgets the uploaded one)
 int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes);
+// pcq_api.hip: the table (nsegments segments of `kind`, `bytes` long) is in d_segments once the work enqueued on s so far is
+// done; uploaded only when it differs from the one already there
+int pcq_upload_segment_table(pcq_ctx *ctx, int kind, size_t nsegments, const void *table, size_t bytes, hipStream_t s);
 
 // scan_count.hip
 int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,

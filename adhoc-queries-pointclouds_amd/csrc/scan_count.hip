@@ -24,6 +24,9 @@
 //    tile's 256 class bytes (one dword per lane) or 256 times (two dwordx4 per lane) are tested per lane into a verdict word;
 //    one ds_bpermute per (load, start phase) brings each point's verdict to the lane that holds its first dword, where it is
 //    ANDed into the mask algebra before the popcount.  13 / 20 B per point.
+// The batched K1 (k_bounds_count_batch_pipe<TILES, Col...>, the same pipeline with a cursor over the segments) and the finish
+//    reduction live in scan_tiles.h: pcq_scan_dev_count_batch below launches the box kind, scan_count_batch.hip the two kinds
+//    with a second column.  The batched K2 and the per-file kernels are here.
 // The kernel shapes these replaced (256-thread blocks, unpipelined one-wave forms, other tile counts) live
 // in csrc/lab/scan_count_lab.hip and are built only into libpcq_lab.so for the sweeps in tools/.
 #include <vector>
@@ -33,26 +36,7 @@
 
 namespace {
 
-// The second column as K1's last argument: none (the plain K1, k_bounds_count_w1_pipe<2>), ClassBytes (PCQ_PRED_BOUNDS_CLASS)
-// or GpsTimes (PCQ_PRED_BOUNDS_TIME), at the body's first point (class bytes: any alignment; times: 8-byte aligned).
-struct ClassBytes {
-    const uint8_t *p;
-};
-struct GpsTimes {
-    const uint8_t *p;
-};
-template <typename... Col>
-struct ColOf {
-    static constexpr int value = COL_NONE;
-};
-template <>
-struct ColOf<ClassBytes> {
-    static constexpr int value = COL_U8;
-};
-template <>
-struct ColOf<GpsTimes> {
-    static constexpr int value = COL_F64;
-};
+// the second column's address out of K1's last argument (scan_tiles.h: ClassBytes, GpsTimes), none: null
 __device__ __forceinline__ const uint8_t *col_ptr() { return nullptr; }
 template <typename C>
 __device__ __forceinline__ const uint8_t *col_ptr(C c) { return c.p; }
@@ -108,88 +92,6 @@ __global__ __launch_bounds__(64) void k_bounds_count_w1_pipe(const v4i *__restri
                 pass = ((uint32_t)(q[0] - pred.lo[0]) <= pred.width[0]) & ((uint32_t)(q[1] - pred.lo[1]) <= pred.width[1]) &
                        ((uint32_t)(q[2] - pred.lo[2]) <= pred.width[2]);
                 if constexpr (COL != COL_NONE) pass = pass && col2_point(c2, p);
-            }
-            total += (uint64_t)__popcll(__ballot(pass));
-        }
-    }
-    if (lane == 0) partials[blockIdx.x] = total;
-}
-
-// Batched K1, one wave per workgroup, TILES tiles per step, software-pipelined like variants 12..14: while the
-// tiles of step u are evaluated the loads of step u + stride are in flight.  Steps are numbered across all
-// segments (tile_begin counts steps); each of the two register sets remembers the segment its step came from.
-struct SegCursor {
-    int s;
-    uint64_t begin, end;
-    const v4i *base;
-    LaneBox lb;
-    bool empty;
-};
-template <int TILES>
-__device__ __forceinline__ void seg_seek(SegCursor &c, const DevSegment *__restrict__ segs, int nseg, uint64_t u, int lane) {
-    if (u < c.end) return;
-    while (c.s + 1 < nseg && u >= segs[c.s + 1].tile_begin) c.s++;
-    c.begin = segs[c.s].tile_begin;
-    c.end = c.begin + segs[c.s].n / ((uint64_t)TILES * TILE_POINTS);
-    c.base = reinterpret_cast<const v4i *>(segs[c.s].xyz);
-    c.empty = segs[c.s].empty != 0;
-    // the box through SGPRs: left to itself the compiler turns "select of table entries" into a per-lane address and
-    // a VECTOR load, and the s_waitcnt vmcnt(0) behind that load would drain the prefetched tiles
-    int32_t lo[3];
-    uint32_t w[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        lo[k] = segs[c.s].lo[k];
-        w[k] = segs[c.s].width[k];
-        asm volatile("" : "+s"(lo[k]), "+s"(w[k]));
-    }
-    c.lb = rotate_box(lo, w, lane);
-}
-
-template <int TILES>
-__global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment *__restrict__ segs, int nseg,
-                                                               uint64_t total_steps, uint64_t *__restrict__ partials) {
-    constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
-    uint64_t total = 0;
-    if (blockIdx.x < total_steps) {
-        PipeRegs<TILES> A, B;
-        SegCursor ca = {0, 0, 0, nullptr, {}, true}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES>(ca, segs, nseg, u, lane);
-        pipe_load<TILES>(A, ca.base, u - ca.begin, lane);
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane);  // clamped at the tail: an L2 hit
-            pipe_wait<TILES, 3 * TILES>(A);
-            if (!ca.empty) total += pipe_eval<TILES>(A, ca.lb);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane);
-            pipe_wait<TILES, 3 * TILES>(B);
-            if (!cb.empty) total += pipe_eval<TILES>(B, cb.lb);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<TILES, 0>(A);
-        pipe_wait<TILES, 0>(B);
-    }
-    for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i
-        if (segs[i].empty) continue;
-        const uint64_t n = segs[i].n;
-        const int *q0 = reinterpret_cast<const int *>(segs[i].xyz);
-        for (uint64_t p = (n / STEP_POINTS) * STEP_POINTS + lane; p < ((n + 63) & ~63ull); p += 64) {
-            bool pass = false;
-            if (p < n) {
-                const int *q = q0 + 3 * p;
-                pass = ((uint32_t)(q[0] - segs[i].lo[0]) <= segs[i].width[0]) &
-                       ((uint32_t)(q[1] - segs[i].lo[1]) <= segs[i].width[1]) &
-                       ((uint32_t)(q[2] - segs[i].lo[2]) <= segs[i].width[2]);
             }
             total += (uint64_t)__popcll(__ballot(pass));
         }
@@ -352,20 +254,6 @@ __global__ __launch_bounds__(64) void k_class_count_pipe(const uint8_t *__restri
     if (lane == 0) partials[blockIdx.x] = w;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_finish_count(const uint64_t *__restrict__ partials, int nblocks,
-                                                        uint64_t *__restrict__ d_count) {
-    __shared__ uint64_t s[BLOCK];
-    uint64_t t = 0;
-    for (int i = threadIdx.x; i < nblocks; i += BLOCK) t += partials[i];
-    s[threadIdx.x] = t;
-    __syncthreads();
-    for (int off = BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
-}
-
 }  // namespace
 
 template <typename... Col>
@@ -427,14 +315,9 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         const int src = pcq_scratch_stream(ctx, s);
         if (src) return src;
     }
-    {
-        const int trc = pcq_ensure_segment_table(ctx, nsegments * sizeof(DevSegment));
-        if (trc) return trc;
-    }
     static_assert(sizeof(DevClassSegment) <= sizeof(DevSegment), "the two segment tables share one buffer");
     const int kind = preds[0].kind;
-    // Build the segment table; it is uploaded only when it differs from the one already in HBM
-    // (a repeated query re-launches without touching the pinned buffer, so no host-side wait).
+    // Build the segment table (pcq_upload_segment_table: it travels only when it differs from the one already in HBM)
     std::vector<DevSegment> table(nsegments);
     memset(table.data(), 0, nsegments * sizeof(DevSegment));
     uint64_t steps = 0;
@@ -470,13 +353,9 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         g.empty = dp.empty;
         steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
     }
-    if (ctx->segments_uploaded != nsegments || ctx->segments_kind != kind ||
-        memcmp(ctx->h_segments, table.data(), nsegments * sizeof(DevSegment)) != 0) {
-        PCQ_HIP(hipStreamSynchronize(s));  // the previous upload from the pinned table must have been consumed
-        memcpy(ctx->h_segments, table.data(), nsegments * sizeof(DevSegment));
-        PCQ_HIP(hipMemcpyAsync(ctx->d_segments, ctx->h_segments, nsegments * sizeof(DevSegment), hipMemcpyHostToDevice, s));
-        ctx->segments_uploaded = nsegments;
-        ctx->segments_kind = kind;
+    {
+        const int urc = pcq_upload_segment_table(ctx, kind, nsegments, table.data(), nsegments * sizeof(DevSegment), s);
+        if (urc) return urc;
     }
     uint64_t g = (uint64_t)ctx->num_cus * (kind == PCQ_PRED_CLASS ? K2_WAVES_PER_CU : K1_WAVES_PER_CU);
     if (g > steps + nsegments) g = steps + nsegments;

@@ -1,6 +1,8 @@
 // scan_tiles.h — the wave-tile count of packed LAST positions, shared by the count kernels (scan_count.hip,
-// scan_count_combined.hip) and the chunk index (chunk_index.hip): the mask algebra of a 768-dword tile, K1's second column
-// (class bytes or GPS times) and the software-pipeline helpers.  See scan_count.hip for the design.
+// scan_count_batch.hip) and the chunk index (chunk_index.hip): the mask algebra of a 768-dword tile, K1's second column
+// (class bytes or GPS times), the software-pipeline helpers, the batched K1 itself (k_bounds_count_batch_pipe: one template for
+// the box, box AND class and box AND time kinds) and the finish reduction of every count (k_finish_count).  See scan_count.hip
+// for the design.
 #pragma once
 
 #include "pcq_internal.h"
@@ -275,6 +277,230 @@ __device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES, COL> &R, con
 template <int TILES>
 __device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES> &R, const LaneBox &lb) {
     return pipe_eval<TILES, COL_NONE>(R, lb, Col2<COL_NONE>{});
+}
+
+// The second column as a kernel's last template argument: none (the plain K1), ClassBytes (PCQ_PRED_BOUNDS_CLASS) or GpsTimes
+// (PCQ_PRED_BOUNDS_TIME).  The per-file K1 also takes it as its last argument: the column at the body's first point (class
+// bytes: any alignment; times: 8-byte aligned).
+struct ClassBytes {
+    const uint8_t *p;
+};
+struct GpsTimes {
+    const uint8_t *p;
+};
+template <typename... Col>
+struct ColOf {
+    static constexpr int value = COL_NONE;
+};
+template <>
+struct ColOf<ClassBytes> {
+    static constexpr int value = COL_U8;
+};
+template <>
+struct ColOf<GpsTimes> {
+    static constexpr int value = COL_F64;
+};
+
+// Batched K1 (k_bounds_count_batch_pipe<TILES, Col...>): box, box AND class, box AND time over many resident LAST blocks in
+// one launch.  One wave per workgroup, TILES tiles per step, software-pipelined like the per-file K1: while the tiles of step
+// u are evaluated the loads of step u + stride are in flight (TILES * (3 + col2_loads) per register set).  Steps are numbered
+// across all segments (tile_begin counts steps); each of the two register sets remembers the segment its step came from.
+// What changes with the segment passes through SGPRs at a seek: the box, and of the second column the class block's address
+// and class byte (COL_U8: base, shift, pat, lane 63's off_hi) or the time block's address and the range (COL_F64); the
+// addr_* / bit_* lane constants of Col2 are computed once.  The segment tables differ per kind (BatchSeg), each at its own
+// pitch in the context's d_segments.
+template <int COL>
+struct BatchSeg {
+    typedef DevSegment type;
+};
+template <>
+struct BatchSeg<COL_U8> {
+    typedef DevCombinedSegment type;
+};
+template <>
+struct BatchSeg<COL_F64> {
+    typedef DevBoundsTimeSegment type;
+};
+template <int COL>
+struct SegCol {};
+template <>
+struct SegCol<COL_U8> {
+    const uint8_t *cbase;  // the class bytes, rounded down to a dword (uniform)
+    uint32_t shift, pat;   // 8 x the misalignment; the class byte in every byte (uniform)
+    uint32_t off_hi;       // this lane's second dword of a tile (lane 63 of an aligned block: its first)
+};
+template <>
+struct SegCol<COL_F64> {
+    const uint8_t *tbase;  // the segment's times (uniform)
+    double t0, t1;         // its range (uniform)
+};
+template <int COL>
+struct SegCursor {
+    int s;
+    uint64_t begin, end;
+    const v4i *base;
+    LaneBox lb;
+    bool empty;
+    SegCol<COL> col;
+};
+// the second column of the cursor's segment, through SGPRs like the box (seg_seek)
+__device__ __forceinline__ void segcol_seek(SegCol<COL_NONE> &, const DevSegment &, int) {}
+__device__ __forceinline__ void segcol_seek(SegCol<COL_U8> &c, const DevCombinedSegment &g, int lane) {
+    uint64_t cls = (uint64_t)(uintptr_t)g.cls;
+    uint32_t pat = g.pat;
+    asm volatile("" : "+s"(cls), "+s"(pat));
+    const uint32_t mis = (uint32_t)cls & 3u;
+    c.cbase = reinterpret_cast<const uint8_t *>((uintptr_t)(cls - mis));
+    c.shift = 8 * mis;
+    c.pat = pat;
+    c.off_hi = lane == 63 && mis == 0 ? 4 * lane : 4 * lane + 4;  // (col2_setup: nothing of the tile lies behind an aligned block's dword 63)
+}
+__device__ __forceinline__ void segcol_seek(SegCol<COL_F64> &c, const DevBoundsTimeSegment &g, int) {
+    uint64_t times = (uint64_t)(uintptr_t)g.times;
+    uint64_t b0 = (uint64_t)__double_as_longlong(g.t0), b1 = (uint64_t)__double_as_longlong(g.t1);
+    asm volatile("" : "+s"(times), "+s"(b0), "+s"(b1));
+    c.tbase = reinterpret_cast<const uint8_t *>((uintptr_t)times);
+    c.t0 = __longlong_as_double((long long)b0);
+    c.t1 = __longlong_as_double((long long)b1);
+}
+template <int TILES, int COL>
+__device__ __forceinline__ void seg_seek(SegCursor<COL> &c, const typename BatchSeg<COL>::type *__restrict__ segs, int nseg, uint64_t u,
+                                         int lane) {
+    if (u < c.end) return;
+    while (c.s + 1 < nseg && u >= segs[c.s + 1].tile_begin) c.s++;
+    const typename BatchSeg<COL>::type &g = segs[c.s];
+    c.begin = g.tile_begin;
+    c.end = c.begin + g.n / ((uint64_t)TILES * TILE_POINTS);
+    c.base = reinterpret_cast<const v4i *>(g.xyz);
+    c.empty = g.empty != 0;
+    // everything of the segment through SGPRs: left to itself the compiler turns "select of table entries" into a per-lane
+    // address and a VECTOR load, and the s_waitcnt vmcnt(0) behind that load would drain the prefetched tiles.  The skip loop
+    // above is not covered: from its second iteration on the compiler reads tile_begin with a vector load and waits for it, so a
+    // workgroup that jumps over more than one segment drains both register sets once
+    int32_t lo[3];
+    uint32_t w[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        lo[k] = g.lo[k];
+        w[k] = g.width[k];
+        asm volatile("" : "+s"(lo[k]), "+s"(w[k]));
+    }
+    c.lb = rotate_box(lo, w, lane);
+    segcol_seek(c.col, g, lane);
+}
+// the lane constants with the cursor's segment
+__device__ __forceinline__ Col2<COL_NONE> col2_of(Col2<COL_NONE> lanes, const SegCol<COL_NONE> &) { return lanes; }
+__device__ __forceinline__ Col2<COL_U8> col2_of(Col2<COL_U8> lanes, const SegCol<COL_U8> &c) {
+    lanes.base = c.cbase;
+    lanes.off_hi = c.off_hi;
+    lanes.shift = c.shift;
+    lanes.pat = c.pat;
+    return lanes;
+}
+__device__ __forceinline__ Col2<COL_F64> col2_of(Col2<COL_F64> lanes, const SegCol<COL_F64> &c) {
+    lanes.base = c.tbase;
+    lanes.t0 = c.t0;
+    lanes.t1 = c.t1;
+    return lanes;
+}
+// the second column of a segment's leftover points, one lane per point: what the loop keeps in registers, and its test of point p
+template <int COL>
+struct SegTail {};
+template <>
+struct SegTail<COL_U8> {
+    const DevCombinedSegment &g;
+    uint8_t c8;
+};
+template <>
+struct SegTail<COL_F64> {
+    const double *tq;
+    double t0, t1;
+};
+__device__ __forceinline__ SegTail<COL_NONE> seg_tail(const DevSegment &) { return {}; }
+__device__ __forceinline__ SegTail<COL_U8> seg_tail(const DevCombinedSegment &g) { return {g, (uint8_t)(g.pat & 0xffu)}; }
+__device__ __forceinline__ SegTail<COL_F64> seg_tail(const DevBoundsTimeSegment &g) {
+    return {reinterpret_cast<const double *>(g.times), g.t0, g.t1};
+}
+__device__ __forceinline__ bool seg_point(const SegTail<COL_NONE> &, uint64_t) { return true; }
+__device__ __forceinline__ bool seg_point(const SegTail<COL_U8> &c, uint64_t p) { return c.g.cls[p] == c.c8; }
+__device__ __forceinline__ bool seg_point(const SegTail<COL_F64> &c, uint64_t p) {
+    const double t = c.tq[p];
+    return (t >= c.t0) & (t < c.t1);
+}
+
+template <int TILES, typename... Col>
+__global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment *__restrict__ raw, int nseg, uint64_t total_steps,
+                                                               uint64_t *__restrict__ partials) {
+    constexpr int COL = ColOf<Col...>::value;
+    static_assert(sizeof...(Col) <= 1, "one second column at most");
+    typedef typename BatchSeg<COL>::type Seg;
+    constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
+    constexpr int LOADS = TILES * (3 + col2_loads(COL));  // per register set
+    const Seg *__restrict__ segs = reinterpret_cast<const Seg *>(raw);
+    const int lane = threadIdx.x;
+    const uint64_t stride = gridDim.x;
+    uint64_t total = 0;
+    if (blockIdx.x < total_steps) {
+        Col2<COL> lanes{};
+        if constexpr (COL == COL_U8) lanes.off_lo = 4 * lane;
+        if constexpr (COL != COL_NONE) col2_lanes<COL>(lanes, lane);
+        PipeRegs<TILES, COL> A, B;
+        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
+        uint64_t u = blockIdx.x;
+        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
+        pipe_load<TILES, COL>(A, ca.base, u - ca.begin, lane, col2_of(lanes, ca.col));
+        for (;;) {
+            const uint64_t u1 = u + stride;
+            cb = ca;
+            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
+            pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
+            pipe_wait<TILES, LOADS, COL>(A);
+            if (!ca.empty) total += pipe_eval<TILES, COL>(A, ca.lb, col2_of(lanes, ca.col));
+            if (u1 >= total_steps) break;
+            const uint64_t u2 = u1 + stride;
+            ca = cb;
+            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
+            pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
+            pipe_wait<TILES, LOADS, COL>(B);
+            if (!cb.empty) total += pipe_eval<TILES, COL>(B, cb.lb, col2_of(lanes, cb.col));
+            if (u2 >= total_steps) break;
+            u = u2;
+        }
+        pipe_wait<TILES, 0, COL>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<TILES, 0, COL>(B);
+    }
+    for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
+        const Seg &g = segs[i];
+        if (g.empty) continue;
+        const uint64_t n = g.n;
+        const int *q0 = reinterpret_cast<const int *>(g.xyz);
+        const SegTail<COL> tail = seg_tail(g);
+        for (uint64_t p = (n / STEP_POINTS) * STEP_POINTS + lane; p < ((n + 63) & ~63ull); p += 64) {
+            bool pass = false;
+            if (p < n) {
+                const int *q = q0 + 3 * p;
+                pass = ((uint32_t)(q[0] - g.lo[0]) <= g.width[0]) & ((uint32_t)(q[1] - g.lo[1]) <= g.width[1]) &
+                       ((uint32_t)(q[2] - g.lo[2]) <= g.width[2]) & seg_point(tail, p);
+            }
+            total += (uint64_t)__popcll(__ballot(pass));
+        }
+    }
+    if (lane == 0) partials[blockIdx.x] = total;
+}
+
+// Folds the per-workgroup partial counts of any of the count kernels: one block, += into *d_count.
+__global__ __launch_bounds__(BLOCK) void k_finish_count(const uint64_t *__restrict__ partials, int nblocks,
+                                                        uint64_t *__restrict__ d_count) {
+    __shared__ uint64_t s[BLOCK];
+    uint64_t t = 0;
+    for (int i = threadIdx.x; i < nblocks; i += BLOCK) t += partials[i];
+    s[threadIdx.x] = t;
+    __syncthreads();
+    for (int off = BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
 }
 
 }  // namespace

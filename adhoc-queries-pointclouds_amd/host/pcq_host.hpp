@@ -406,7 +406,8 @@ public:
 
 private:
     ResidentDataset() = default;
-    Status run(const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches);
+    Status run(int kind, const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches);
+    Status count_box(const AABB &bounds, pcq_predicate pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     pcq_ctx *ctx_ = nullptr;
     bool with_points_ = false, with_times_ = false;

@@ -96,34 +96,47 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
     return Status::Ok();
 }
 
-Status ResidentDataset::run(const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches) {
+// One batched launch of the kind's entry over the segments, the total into the dataset's counter and back.
+Status ResidentDataset::run(int kind, const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches) {
+    const auto entry = kind == PCQ_PRED_BOUNDS_CLASS  ? pcq_scan_dev_count_batch_combined
+                       : kind == PCQ_PRED_BOUNDS_TIME ? pcq_scan_dev_count_batch_bounds_time
+                                                      : pcq_scan_dev_count_batch;
     int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
-    if (!rc && !cols.empty()) rc = pcq_scan_dev_count_batch(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
+    if (!rc && !cols.empty()) rc = entry(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
     if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
     return Status::FromLib(rc);
 }
 
-// `--bounds` over the dataset, count only: BoundsSearcher + CountCollector + the sum of main.rs:164-180.
-Status ResidentDataset::count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned) {
+// The three box counts: per file the prologue the reference runs before its loop, then one batched launch over the surviving
+// files.  `pred` brings the kind and what it tests besides the box (cls; [wmin[0], wmax[0])); the kind picks the second column
+// (PCQ_PRED_BOUNDS_CLASS: the classification block, PCQ_PRED_BOUNDS_TIME: the time block).
+Status ResidentDataset::count_box(const AABB &bounds, pcq_predicate pred, uint64_t *matches, uint64_t *points_scanned) {
     std::vector<pcq_columns> cols;
     std::vector<pcq_predicate> preds;
     uint64_t scanned = 0;
     for (const auto &f : files_) {
         if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS;
         const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
         if (brc) return Status::FromLib(brc);
         if (f.header.number_of_points == 0) continue;
         pcq_columns c{};
         c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
+        if (pred.kind == PCQ_PRED_BOUNDS_CLASS) c.cls = f.cls, c.cls_stride = 1;
+        if (pred.kind == PCQ_PRED_BOUNDS_TIME) c.cls = f.time, c.cls_stride = 8;
         for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
         cols.push_back(c);
         preds.push_back(pred);
         scanned += c.n;
     }
     if (points_scanned) *points_scanned = scanned;
-    return run(cols, preds, matches);
+    return run(pred.kind, cols, preds, matches);
+}
+
+// `--bounds` over the dataset, count only: BoundsSearcher + CountCollector + the sum of main.rs:164-180.
+Status ResidentDataset::count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned) {
+    pcq_predicate pred{};
+    pred.kind = PCQ_PRED_BOUNDS;
+    return count_box(bounds, pred, matches, points_scanned);
 }
 
 // `--class` over the dataset, count only (last.rs:253-262: whole byte, no file-level early-out).
@@ -143,68 +156,28 @@ Status ResidentDataset::count_class(uint8_t cls, uint64_t *matches, uint64_t *po
         scanned += c.n;
     }
     if (points_scanned) *points_scanned = scanned;
-    return run(cols, preds, matches);
+    return run(PCQ_PRED_CLASS, cols, preds, matches);
 }
 
-// `--combine --bounds --class` over the dataset, count only: the prologue of count_bounds per file, then one batched launch
-// over the positions and classification blocks of the surviving files (pcq_scan_dev_count_batch_combined).
+// `--combine --bounds --class` over the dataset, count only (pcq_scan_dev_count_batch_combined over the positions and
+// classification blocks).
 Status ResidentDataset::count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
-    std::vector<pcq_columns> cols;
-    std::vector<pcq_predicate> preds;
-    uint64_t scanned = 0;
-    for (const auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS_CLASS;
-        pred.cls = cls;
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
-        if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        pcq_columns c{};
-        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
-        c.cls = f.cls, c.cls_stride = 1;
-        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
-        cols.push_back(c);
-        preds.push_back(pred);
-        scanned += c.n;
-    }
-    if (points_scanned) *points_scanned = scanned;
-    int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
-    if (!rc && !cols.empty()) rc = pcq_scan_dev_count_batch_combined(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
-    if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
-    return Status::FromLib(rc);
+    pcq_predicate pred{};
+    pred.kind = PCQ_PRED_BOUNDS_CLASS;
+    pred.cls = cls;
+    return count_box(bounds, pred, matches, points_scanned);
 }
 
-// `--combine --bounds --time` over the dataset, count only: the prologue of count_bounds_class per file, then one batched launch
-// over the positions and time blocks of the surviving files (pcq_scan_dev_count_batch_bounds_time).
+// `--combine --bounds --time` over the dataset, count only (pcq_scan_dev_count_batch_bounds_time over the positions and time
+// blocks).
 Status ResidentDataset::count_bounds_time(const AABB &bounds, double start, double end, uint64_t *matches, uint64_t *points_scanned) {
     if (!with_times_)
         return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
-    std::vector<pcq_columns> cols;
-    std::vector<pcq_predicate> preds;
-    uint64_t scanned = 0;
-    for (const auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS_TIME;
-        pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
-        pred.wmax[0] = end;
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
-        if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        pcq_columns c{};
-        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
-        c.cls = f.time, c.cls_stride = 8;
-        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
-        cols.push_back(c);
-        preds.push_back(pred);
-        scanned += c.n;
-    }
-    if (points_scanned) *points_scanned = scanned;
-    int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
-    if (!rc && !cols.empty()) rc = pcq_scan_dev_count_batch_bounds_time(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
-    if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
-    return Status::FromLib(rc);
+    pcq_predicate pred{};
+    pred.kind = PCQ_PRED_BOUNDS_TIME;
+    pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
+    pred.wmax[0] = end;
+    return count_box(bounds, pred, matches, points_scanned);
 }
 
 // One file of the search_* : execute_plan (search.cpp) with the resident blocks in place of the file.

@@ -19,12 +19,12 @@ mis-addressed step moves a count by an amount no other single error cancels.  Ex
 compares on the finished arrays (class_count, time_count, box_count below), never from m(s).
 
 Restated from (adhoc-queries-pointclouds_amd/csrc):
-  K1 family  scan_tiles.h:11-13 (256-point tiles, 2 per step, 3 waves per CU); scan_count.hip:66 (steps), :375-377 (grid);
+  K1 family  scan_tiles.h:13-15 (256-point tiles, 2 per step, 3 waves per CU); scan_count.hip:50 (steps), :263-265 (grid);
              collectors.hip:267 (the points peeled in front of the first 16-byte aligned one)
-  K2         scan_tiles.h:14-15 (4 loads of 1 KiB per step, 4 waves per CU); scan_count.hip:403-409 (head, nvec, grid), :312
+  K2         scan_tiles.h:16-17 (4 loads of 1 KiB per step, 4 waves per CU); scan_count.hip:291-297 (head, nvec, grid), :214
   K3         scan_time.hip:17-18 (4 loads per step, 4 waves per CU), :110-114 (head, nvec, grid), :63
-  batches    scan_count.hip:450-456 (class segments), :468-471 (bounds segments), :481-482 (grid), :131 / :242 (seek);
-             scan_count_combined.hip:167-171 (segments), :187-188 (grid), :34 (seek)
+  batches    scan_count.hip:333-339 (class segments), :351-354 (bounds segments), :360-361 (grid), :144 (K2's seek);
+             scan_count_batch.hip:68-72 (segments with a second column), :78-79 (grid); scan_tiles.h:370 (K1's seek)
 """
 from collections import Counter, namedtuple
 

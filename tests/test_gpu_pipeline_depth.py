@@ -343,7 +343,7 @@ def test_bounds_batch(gpu_ctx, point_segments):
 
 
 def test_combined_batch(gpu_ctx, point_segments):
-    """k_bounds_class_count_batch_pipe<2>: every segment's large box and class; one box with lmin > lmax."""
+    """k_bounds_count_batch_pipe<2, ClassBytes>: every segment's large box and class; one box with lmin > lmax."""
     boxes = [q.box for q in point_segments.q]
     boxes[pp.EMPTY_BOX_SEGMENT] = ([5, 5, 5], [4, 4, 4])
     b = point_segments.batch(gpu_ctx, "combined", gpu_ctx.scan_dev_count_batch_combined, boxes, [q.classes[0] for q in point_segments.q])

@@ -1,4 +1,4 @@
-"""k_bounds_time_count_batch_pipe<2> (pcq_scan_dev_count_batch_bounds_time) beyond its pipeline's second step, on step-coded
+"""k_bounds_count_batch_pipe<2, GpsTimes> (pcq_scan_dev_count_batch_bounds_time) beyond its pipeline's second step, on step-coded
 data, against numpy.
 
 The plan, the schedule report and the step-coded data are those of tests/_pipeline_plan.py, as test_gpu_pipeline_depth.py uses them: one

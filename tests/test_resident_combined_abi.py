@@ -33,7 +33,7 @@ def test_abi_number_and_pinned_kernel_names_are_unchanged():
     syms = subprocess.run(["nm", "-C", pkg.lib_path()], capture_output=True, text=True).stdout
     for kernel in ("k_bounds_count_batch_pipe<2>", "k_bounds_count_w1_pipe<2>"):
         assert kernel in syms, kernel
-    assert "k_bounds_class_count_batch_pipe<2>" in syms and "k_index_count_bounds_class" in syms
+    assert "k_bounds_count_batch_pipe<2, (anonymous namespace)::ClassBytes>" in syms and "k_index_count_bounds_class" in syms
 
 
 def test_binding_has_the_two_context_methods():
