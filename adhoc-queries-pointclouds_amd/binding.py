@@ -208,6 +208,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_count_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_combined": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_bounds_time": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
+        "pcq_scan_dev_count_batch_multi": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -459,6 +460,21 @@ class Context:
         ca = (Columns * n)(*cols)
         pa = (Predicate * n)(*preds)
         _check(self.lib.pcq_scan_dev_count_batch_bounds_time(self.handle, ca, pa, n, C.c_void_p(device_total), C.c_void_p(stream)))
+
+    def scan_dev_count_batch_multi(self, cols: Sequence[Columns], pred_rows: Sequence[Sequence[Predicate]], device_totals: int,
+                                   stream: Optional[int] = None, nqueries: Optional[int] = None) -> None:
+        """Up to PCQ_MULTI_BOX_MAX boxes (Predicate kind PCQ_PRED_BOUNDS) asked of many resident LAST files in ONE pass:
+        pred_rows[i][q] is box q of segment i (an empty box: not asked of that segment); the count of box q is += into word q of
+        device_totals.  nqueries: the row length, for a call without segments."""
+        n = len(cols)
+        if len(pred_rows) != n:
+            raise ValueError("one row of predicates per segment")
+        nq = (len(pred_rows[0]) if n else 0) if nqueries is None else nqueries
+        if any(len(row) != nq for row in pred_rows):
+            raise ValueError("every row holds nqueries predicates")
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * (n * nq))(*[p for row in pred_rows for p in row])
+        _check(self.lib.pcq_scan_dev_count_batch_multi(self.handle, ca, pa, n, nq, C.c_void_p(device_totals), C.c_void_p(stream)))
 
     # chunk index --------------------------------------------------------------------------------
     def index_new(self) -> int:

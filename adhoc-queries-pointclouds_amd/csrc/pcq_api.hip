@@ -341,6 +341,7 @@ static const Option k_options[] = {
     {"class_batch_loads", &pcq_ctx::class_batch_loads, 0, 12, OPT_SET},  // (only 0, 4, 6, 8 and 12, below)
     {"class_batch_pipe", &pcq_ctx::class_batch_pipe, 0, 1, OPT_SET | OPT_BOOL},
     {"class_batch_waves_per_cu", &pcq_ctx::class_batch_waves_per_cu, 1, 32, OPT_SET},
+    {"multi_waves_per_cu", &pcq_ctx::multi_waves_per_cu, 0, 32, OPT_SET},
 #endif
 };
 #undef DIAG

@@ -126,6 +126,21 @@ struct DevBoundsTimeSegment {
     double t0, t1;         // [t0, t1)
 };
 
+// One segment of a multi-box batched count launch (scan_count_multi.hip): up to PCQ_MULTI_BOX_MAX boxes are asked of the
+// segment while its tiles are in registers.  One pitch whatever the number of boxes of the launch; slots that are not live
+// hold zeros.  Its tables travel under PCQ_SEGMENTS_MULTI, a kind of the segment table outside pcq_predicate_kind.
+struct DevMultiSegment {
+    const int4 *xyz;       // 16-byte aligned positions block
+    uint64_t n;            // points
+    uint64_t tile_begin;   // first global step of this segment
+    uint32_t live;         // bit q: box q is asked of this segment and is not empty
+    uint32_t _pad;
+    int32_t lo[PCQ_MULTI_BOX_MAX][3];
+    uint32_t width[PCQ_MULTI_BOX_MAX][3];
+};
+static_assert(PCQ_MULTI_BOX_MAX == 8 && sizeof(DevMultiSegment) == 224, "DevMultiSegment: eight boxes at one pitch");
+constexpr int PCQ_SEGMENTS_MULTI = 0x4d42;  // ("MB") no pcq_predicate_kind: the key of a multi-box table equals no other table's
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -304,6 +319,7 @@ struct pcq_ctx {
     int class_batch_loads = 4;
     int class_batch_waves_per_cu = 4;
     int class_batch_pipe = 1;
+    int multi_waves_per_cu = 0;   // multi-box K1 (scan_count_multi.hip): workgroups per CU (0 = the product's: MULTI_WAVES_PER_CU)
 #endif
     int numa_node = -1;               // NUMA node the GPU hangs off (sysfs), -1 if unknown
     cpu_set_t node_cpus;              // its CPUs (empty if unknown)

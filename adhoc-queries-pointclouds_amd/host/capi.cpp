@@ -335,6 +335,12 @@ extern "C" int pcq_query_resident_count_bounds(pcq_host_resident *r, const doubl
     if (!st.ok()) return done(st);
     return done(r->ds->count_bounds(b, matches, points_scanned));
 }
+extern "C" int pcq_query_resident_count_bounds_many(pcq_host_resident *r, size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches,
+                                                    uint64_t *points_scanned, uint64_t *points_read) {
+    if (!r || !bmin || !bmax || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nboxes == 0) return PCQ_OK;
+    return done(r->ds->count_bounds_many(nboxes, bmin, bmax, matches, points_scanned, points_read));
+}
 extern "C" int pcq_query_resident_count_class(pcq_host_resident *r, uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
     if (!r || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
     return done(r->ds->count_class(cls, matches, points_scanned));

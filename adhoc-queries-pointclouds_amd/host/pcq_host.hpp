@@ -393,6 +393,10 @@ public:
     Status count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned = nullptr);
     Status count_bounds_time(const AABB &bounds, double start, double end, uint64_t *matches, uint64_t *points_scanned = nullptr);  // (with_times)
+    // count_bounds for nboxes boxes (bmin, bmax: [nboxes][3]) in one pass per group of PCQ_MULTI_BOX_MAX boxes: matches[q] and
+    // points_scanned[q] are what count_bounds gives for box q; points_read: the points of the segments of every launch, summed
+    Status count_bounds_many(size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches, uint64_t *points_scanned = nullptr,
+                             uint64_t *points_read = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
@@ -414,6 +418,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
+    size_t counter_words_ = 2;  // (count_bounds_many grows it to a word per box)
     uint64_t points_ = 0;
 };
 

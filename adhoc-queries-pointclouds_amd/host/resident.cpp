@@ -139,6 +139,82 @@ Status ResidentDataset::count_bounds(const AABB &bounds, uint64_t *matches, uint
     return count_box(bounds, pred, matches, points_scanned);
 }
 
+// Many boxes, one pass per group of PCQ_MULTI_BOX_MAX (pcq_scan_dev_count_batch_multi).  First the prologue of count_box for every
+// box and file, boxes outermost: the first failure is that of the lowest box whose own call fails, found before anything is
+// enqueued or written.  A file whose header misses box q carries an EMPTY predicate in slot q — also where its points would
+// match in integer space: the early-out decides, as in the reference; a file no box of a group meets is no segment of that
+// group's launch.  All launches go to the context's stream, the counts into a word per box of the dataset's counter; the host
+// waits for the copy of the counts at the end, and once per group whose table differs from the one in HBM (pcq_upload_segment_table).
+Status ResidentDataset::count_bounds_many(size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches, uint64_t *points_scanned,
+                                          uint64_t *points_read) {
+    if (nboxes == 0) return Status::Ok();
+    const size_t nfiles = files_.size();
+    pcq_predicate none{};  // "not asked of this file"
+    none.kind = PCQ_PRED_BOUNDS;
+    for (int a = 0; a < 3; a++) none.lmin[a] = 1, none.lmax[a] = 0;
+    std::vector<pcq_predicate> local(nboxes * nfiles, none);  // [box][file]
+    std::vector<uint8_t> asked(nboxes * nfiles, 0);
+    std::vector<uint64_t> scanned(nboxes, 0), counts(nboxes, 0);
+    for (size_t q = 0; q < nboxes; q++) {
+        AABB bounds;
+        Status st = AABB::from_min_max(bmin + 3 * q, bmax + 3 * q, &bounds);
+        if (!st.ok()) return st;
+        for (size_t i = 0; i < nfiles; i++) {
+            const ResidentFile &f = files_[i];
+            if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
+            pcq_predicate pred{};
+            pred.kind = PCQ_PRED_BOUNDS;
+            const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+            if (brc) return Status::FromLib(brc);
+            if (f.header.number_of_points == 0) continue;
+            local[q * nfiles + i] = pred;
+            asked[q * nfiles + i] = 1;
+            scanned[q] += f.header.number_of_points;
+        }
+    }
+    if (nboxes > counter_words_) {
+        void *p = nullptr;
+        int rc = pcq_device_alloc(ctx_, nboxes * 8, &p);
+        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed between two groups has left launches that add into the old counter)
+        if (rc) {
+            if (p) pcq_device_free(ctx_, p);
+            return Status::FromLib(rc);
+        }
+        pcq_device_free(ctx_, counter_);
+        counter_ = (uint64_t *)p;
+        counter_words_ = nboxes;
+    }
+    int rc = pcq_device_memset(ctx_, counter_, 0, nboxes * 8, nullptr);
+    uint64_t read = 0;
+    std::vector<pcq_columns> cols;
+    std::vector<pcq_predicate> preds;
+    for (size_t q0 = 0; q0 < nboxes && !rc; q0 += PCQ_MULTI_BOX_MAX) {
+        const size_t nq = nboxes - q0 < PCQ_MULTI_BOX_MAX ? nboxes - q0 : (size_t)PCQ_MULTI_BOX_MAX;
+        cols.clear();
+        preds.clear();
+        for (size_t i = 0; i < nfiles; i++) {
+            const ResidentFile &f = files_[i];
+            bool met = false;
+            for (size_t q = q0; q < q0 + nq; q++) met |= asked[q * nfiles + i] != 0;
+            if (!met) continue;
+            pcq_columns c{};
+            c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
+            for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
+            cols.push_back(c);
+            for (size_t q = q0; q < q0 + nq; q++) preds.push_back(local[q * nfiles + i]);
+            read += c.n;
+        }
+        if (!cols.empty()) rc = pcq_scan_dev_count_batch_multi(ctx_, cols.data(), preds.data(), cols.size(), nq, counter_ + q0, nullptr);
+    }
+    if (!rc) rc = pcq_copy_to_host(ctx_, counts.data(), counter_, nboxes * 8);  // waits for the context's stream (a group whose table differs from the one in HBM has waited once before its upload)
+    if (rc) return Status::FromLib(rc);
+    for (size_t q = 0; q < nboxes; q++) matches[q] = counts[q];
+    if (points_scanned)
+        for (size_t q = 0; q < nboxes; q++) points_scanned[q] = scanned[q];
+    if (points_read) *points_read = read;
+    return Status::Ok();
+}
+
 // `--class` over the dataset, count only (last.rs:253-262: whole byte, no file-level early-out).
 Status ResidentDataset::count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
     std::vector<pcq_columns> cols;

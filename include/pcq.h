@@ -254,6 +254,17 @@ int pcq_scan_dev_count_batch_combined(pcq_ctx *ctx, const pcq_columns *cols, con
  * (PCQ_ERR_ARG) before anything is launched or uploaded. */
 int pcq_scan_dev_count_batch_bounds_time(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
                                          size_t nsegments, uint64_t *device_total, void *stream);
+/* Many boxes in ONE pass: nqueries (1 .. PCQ_MULTI_BOX_MAX) boxes are asked of every segment while its positions are in
+ * registers, so the data is read once instead of nqueries times.  preds is row-major [nsegments][nqueries], every entry
+ * PCQ_PRED_BOUNDS; the count of segment i under preds[i * nqueries + q] is ADDED to device_totals[q] (nqueries device words).
+ * A predicate that is empty (lmin > lmax on an axis, or a box outside the i32 value range) says "box q is not asked of
+ * segment i": it contributes 0 and costs no evaluation.  The layout is that of pcq_scan_dev_count_batch: xyz_stride 12,
+ * 16-byte aligned, non-null when n > 0.  nqueries == 1 is pcq_scan_dev_count_batch.  nsegments == 0 is PCQ_OK.  nqueries == 0
+ * or above PCQ_MULTI_BOX_MAX, any other predicate kind and any other layout are refused (PCQ_ERR_ARG) before anything is
+ * uploaded or launched. */
+#define PCQ_MULTI_BOX_MAX 8
+int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
+                                   size_t nqueries, uint64_t *device_totals, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

@@ -99,6 +99,17 @@ int pcq_query_resident_count_class(pcq_host_resident *r, uint8_t cls, uint64_t *
  * surviving files (pcq_scan_dev_count_batch_combined).  points_scanned: the points of the files whose headers meet the box. */
 int pcq_query_resident_count_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
                                           uint64_t *matches, uint64_t *points_scanned);
+/* Many boxes in one pass (`--bounds`, count only, nboxes times): bmin and bmax are [nboxes][3]; matches[q] and
+ * points_scanned[q] (NULL: not wanted) are what pcq_query_resident_count_bounds(r, bmin + 3q, bmax + 3q, ...) returns, for every
+ * q.  Per file and box the prologue of that entry (header early-out, box conversion); a file whose header misses box q is not
+ * asked box q, a file no box of a group meets is not read.  The boxes are taken in their order in groups of
+ * PCQ_MULTI_BOX_MAX (pcq.h), ONE launch per group (pcq_scan_dev_count_batch_multi): the positions of the files a group meets
+ * are read once, not once per box.  points_read (NULL: not wanted): the points of the segments of every launch, summed — what
+ * HBM served.  nboxes == 0 is PCQ_OK with nothing written.  A null r, bmin, bmax or matches is PCQ_ERR_ARG before any device
+ * is touched.  If some box's own call would fail (PCQ_ERR_PANIC: min > max) the status of the lowest such box is returned,
+ * nothing is launched and nothing is written. */
+int pcq_query_resident_count_bounds_many(pcq_host_resident *r, size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches,
+                                         uint64_t *points_scanned, uint64_t *points_read);
 /* Point and density queries over a resident dataset: the per-file searches over every loaded file, in load order, into ONE
  * collector.  Count and buffer collectors go through each file's chunk index (pcq_scan_dev_indexed: the first query of a
  * kind builds it, later ones read only the chunks that straddle the box); grid collectors through pcq_scan_dev, unpruned.

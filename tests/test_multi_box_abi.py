@@ -1,0 +1,68 @@
+"""Many boxes in one pass: the libpcq entry (include/pcq.h: pcq_scan_dev_count_batch_multi) and the host entry
+(include/pcq_query.h: pcq_query_resident_count_bounds_many) are declared and exported beside the old batch entries, the binding
+has the method, the ABI number is what it was, and the host entry refuses null arguments and answers nboxes == 0 before any
+device is touched.  No GPU call."""
+import ctypes as C
+import importlib
+import os
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+PCQ_ERR_ARG = -8
+LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time"]
+QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time"]
+
+
+def test_both_entries_are_declared_and_exported_beside_the_old_ones():
+    declared = pkg.declared_symbols(["pcq.h"])
+    exported = pkg.exported_symbols(pkg.lib_path())
+    for name in ["pcq_scan_dev_count_batch_multi"] + LIB_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    declared = pkg.declared_symbols(["pcq_query.h"])
+    exported = pkg.exported_symbols(os.path.join(PKG, "libpcq_query.so"))
+    for name in ["pcq_query_resident_count_bounds_many"] + QUERY_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    with open(os.path.join(ROOT, "include", "pcq.h")) as f:
+        assert "#define PCQ_MULTI_BOX_MAX 8" in f.read()
+
+
+def test_abi_number_is_unchanged_and_the_binding_has_the_method():
+    assert pkg.load_library().pcq_abi_version() == 6
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    assert callable(binding.Context.scan_dev_count_batch_multi)
+    assert callable(binding.Context.scan_dev_count_batch)
+
+
+def host_lib():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    lib.pcq_query_resident_count_bounds_many.argtypes = [C.c_void_p, C.c_size_t, dd, dd, u64p, u64p, u64p]
+    return lib
+
+
+def test_host_entry_refuses_null_arguments_without_a_device():
+    lib = host_lib()
+    dummy = C.c_void_p(1)  # never dereferenced: another argument is null
+    lo, hi = (C.c_double * 6)(0, 0, 0, 0, 0, 0), (C.c_double * 6)(1, 1, 1, 1, 1, 1)
+    m = (C.c_uint64 * 2)(7, 9)
+    s = (C.c_uint64 * 2)(11, 13)
+    r = C.c_uint64(15)
+    for args in ((None, 2, lo, hi, m, s, C.byref(r)), (dummy, 2, None, hi, m, s, C.byref(r)), (dummy, 2, lo, None, m, s, C.byref(r)),
+                 (dummy, 2, lo, hi, None, s, C.byref(r))):
+        assert lib.pcq_query_resident_count_bounds_many(*args) == PCQ_ERR_ARG
+        assert b"null argument" in lib.pcq_query_last_error()
+        assert list(m) == [7, 9] and list(s) == [11, 13] and r.value == 15
+
+
+def test_no_boxes_is_ok_without_a_device_and_writes_nothing():
+    lib = host_lib()
+    dummy = C.c_void_p(1)  # never dereferenced: there is nothing to ask
+    lo, hi = (C.c_double * 3)(0, 0, 0), (C.c_double * 3)(1, 1, 1)
+    m, s, r = C.c_uint64(7), C.c_uint64(11), C.c_uint64(15)
+    assert lib.pcq_query_resident_count_bounds_many(dummy, 0, lo, hi, C.byref(m), C.byref(s), C.byref(r)) == 0
+    assert (m.value, s.value, r.value) == (7, 11, 15)
