@@ -209,6 +209,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_count_batch_combined": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_bounds_time": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_multi": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, C.c_size_t, vp, vp]),
+        "pcq_scan_dev_class_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -451,6 +452,16 @@ class Context:
         ca = (Columns * n)(*cols)
         pa = (Predicate * n)(*preds)
         _check(self.lib.pcq_scan_dev_count_batch_combined(self.handle, ca, pa, n, C.c_void_p(device_total), C.c_void_p(stream)))
+
+    def scan_dev_class_hist_batch(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_hist: int,
+                                  stream: Optional[int] = None) -> None:
+        """The class histogram of a box (Predicate kind PCQ_PRED_BOUNDS; segments laid out as for scan_dev_count_batch_combined)
+        over many resident LAST files in ONE pass: for every point inside its segment's box, += 1 into the word of its class
+        byte among the PCQ_CLASS_BINS (256) words of device_hist."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        _check(self.lib.pcq_scan_dev_class_hist_batch(self.handle, ca, pa, n, C.c_void_p(device_hist), C.c_void_p(stream)))
 
     def scan_dev_count_batch_bounds_time(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_total: int,
                                          stream: Optional[int] = None) -> None:

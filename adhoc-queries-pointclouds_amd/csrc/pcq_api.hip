@@ -342,6 +342,8 @@ static const Option k_options[] = {
     {"class_batch_pipe", &pcq_ctx::class_batch_pipe, 0, 1, OPT_SET | OPT_BOOL},
     {"class_batch_waves_per_cu", &pcq_ctx::class_batch_waves_per_cu, 1, 32, OPT_SET},
     {"multi_waves_per_cu", &pcq_ctx::multi_waves_per_cu, 0, 32, OPT_SET},
+    {"class_hist_waves_per_cu", &pcq_ctx::class_hist_waves_per_cu, 0, 32, OPT_SET},
+    {"class_hist_copies", &pcq_ctx::class_hist_copies, 0, 16, OPT_SET},  // (only 0, 1, 2, 4, 8 and 16: scan_class_hist.hip)
 #endif
 };
 #undef DIAG

@@ -141,6 +141,10 @@ struct DevMultiSegment {
 static_assert(PCQ_MULTI_BOX_MAX == 8 && sizeof(DevMultiSegment) == 224, "DevMultiSegment: eight boxes at one pitch");
 constexpr int PCQ_SEGMENTS_MULTI = 0x4d42;  // ("MB") no pcq_predicate_kind: the key of a multi-box table equals no other table's
 
+// The class histogram of a box (scan_class_hist.hip) reads tables of DevCombinedSegment (`pat` unused) under a kind of its own:
+// the same bytes under PCQ_PRED_BOUNDS_CLASS are another batch entry's table.
+constexpr int PCQ_SEGMENTS_CLASS_HIST = 0x4348;  // ("CH") no pcq_predicate_kind
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -320,6 +324,8 @@ struct pcq_ctx {
     int class_batch_waves_per_cu = 4;
     int class_batch_pipe = 1;
     int multi_waves_per_cu = 0;   // multi-box K1 (scan_count_multi.hip): workgroups per CU (0 = the product's: MULTI_WAVES_PER_CU)
+    int class_hist_waves_per_cu = 0;  // class histogram (scan_class_hist.hip): workgroups per CU (0 = the product's: CLASS_HIST_WAVES_PER_CU)
+    int class_hist_copies = 0;    // ... and copies of the LDS histogram per wave, 1 / 2 / 4 / 8 / 16 (0 = the product's: CLASS_HIST_COPIES)
 #endif
     int numa_node = -1;               // NUMA node the GPU hangs off (sysfs), -1 if unknown
     cpu_set_t node_cpus;              // its CPUs (empty if unknown)
@@ -380,6 +386,8 @@ int pcq_launch_bounds_count_xyz12_col(pcq_ctx *ctx, const void *d_xyz, const voi
                                       hipStream_t s);
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls,
                               uint64_t *d_count, hipStream_t s);
+// scan_count_multi.hip: k_finish_counts on s — block q folds slice q (nblocks words) of the context's partials, += into d_counts[q]
+int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d_counts, hipStream_t s);
 // scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)
 int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s);
 // scan_generic.hip

@@ -141,7 +141,8 @@ __global__ __launch_bounds__(64) void k_bounds_count_multi_pipe(const DevMultiSe
     }
 }
 
-// Folds the multi-box kernel's partial counts: block q folds slice q (nblocks words), += into d_counts[q].
+// Folds the partial counts of the multi-box kernel and of the class histogram (scan_class_hist.hip, through
+// pcq_launch_finish_counts): block q folds slice q (nblocks words), += into d_counts[q].
 __global__ __launch_bounds__(BLOCK) void k_finish_counts(const uint64_t *__restrict__ partials, int nblocks, uint64_t *__restrict__ d_counts) {
     __shared__ uint64_t s[BLOCK];
     const uint64_t *slice = partials + (uint64_t)blockIdx.x * (uint64_t)nblocks;
@@ -221,7 +222,11 @@ extern "C" int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *c
     if (nq == 2) launch_multi<2>(ctx, (unsigned)g, (int)nsegments, steps, s);
     else if (nq == 4) launch_multi<4>(ctx, (unsigned)g, (int)nsegments, steps, s);
     else launch_multi<8>(ctx, (unsigned)g, (int)nsegments, steps, s);
-    hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)nqueries), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, device_totals);
+    return pcq_launch_finish_counts(ctx, (int)nqueries, (int)g, device_totals, s);
+}
+
+int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d_counts, hipStream_t s) {
+    hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)nslices), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_counts);
     PCQ_HIP(hipGetLastError());
     return PCQ_OK;
 }

@@ -179,6 +179,35 @@ __device__ __forceinline__ uint32_t tile_count_regs(const v4i (&v)[3], const Lan
     return cnt;
 }
 
+// The verdicts of a tile's points, not counted (scan_class_hist.hip): bit l of t[k][j] says that the three dwords from dword
+// (k, l, j) of the tile on pass the tests of x, y and z in this order — the box verdict of the point that starts there.  It
+// means nothing where no point starts (tile_count_regs ANDs start_lanes into it; a caller that looks a point up by its first
+// dword needs no such mask).  The mask algebra is that of tile_count_regs.
+__device__ __forceinline__ void tile_start_masks(const v4i (&v)[3], const LaneBox &b, uint64_t (&t)[3][4]) {
+    uint64_t m[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int c = (k + j) % 3;
+            m[k][j] = __ballot((uint32_t)(v[k][j] - b.lo[c]) <= b.w[c]);
+        }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint64_t m0 = m[k][0], m1 = m[k][1], m2 = m[k][2], m3 = m[k][3];
+        const uint64_t c0 = k < 2 ? m[k < 2 ? k + 1 : k][0] : 0ull;  // (nothing is carried out of k == 2: the tile ends on a point boundary)
+        const uint64_t c1 = k < 2 ? m[k < 2 ? k + 1 : k][1] : 0ull;
+        const uint64_t n0 = (m0 >> 1) | (c0 << 63);
+        const uint64_t n1 = (m1 >> 1) | (c1 << 63);
+        const uint64_t a = m1 & m2;
+        const uint64_t bb = m3 & n0;
+        t[k][0] = m0 & a;    // dwords j=0,1,2 of lane l
+        t[k][1] = a & m3;    // j=1,2,3
+        t[k][2] = m2 & bb;   // j=2,3 and next lane's 0
+        t[k][3] = bb & n1;   // j=3 and next lane's 0,1
+    }
+}
+
 __device__ __forceinline__ uint32_t tile_count_masks(const v4i *tile, int lane, const LaneBox &b) {
     v4i v[3];
     v[0] = ld_nt(tile + lane);

@@ -353,6 +353,14 @@ extern "C" int pcq_query_resident_count_bounds_class(pcq_host_resident *r, const
     if (!st.ok()) return done(st);
     return done(r->ds->count_bounds_class(b, cls, matches, points_scanned));
 }
+extern "C" int pcq_query_resident_count_bounds_by_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint64_t hist[256],
+                                                        uint64_t *points_scanned) {
+    if (!r || !bmin || !bmax || !hist) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    AABB b;
+    Status st = AABB::from_min_max(bmin, bmax, &b);
+    if (!st.ok()) return done(st);
+    return done(r->ds->count_bounds_by_class(b, hist, points_scanned));
+}
 extern "C" int pcq_query_resident_search_bounds_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint8_t cls,
                                                       pcq_host_collector *c) {
     if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

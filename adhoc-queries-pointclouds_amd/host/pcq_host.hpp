@@ -397,6 +397,8 @@ public:
     // points_scanned[q] are what count_bounds gives for box q; points_read: the points of the segments of every launch, summed
     Status count_bounds_many(size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches, uint64_t *points_scanned = nullptr,
                              uint64_t *points_read = nullptr);
+    // the class histogram of a box: hist[c] (PCQ_CLASS_BINS words) is what count_bounds_class gives for class c, from ONE pass
+    Status count_bounds_by_class(const AABB &bounds, uint64_t *hist, uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
@@ -418,7 +420,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (count_bounds_many grows it to a word per box)
+    size_t counter_words_ = 2;  // (count_bounds_many grows it to a word per box, count_bounds_by_class to a word per class)
     uint64_t points_ = 0;
 };
 

@@ -21,6 +21,9 @@
 // Box AND time (count_bounds_time / search_bounds_time): the positions and time blocks of such a dataset side by side — the count is
 // one pcq_scan_dev_count_batch_bounds_time, the search goes through the bounds and time parts of the file's index
 // (pcq_scan_dev_indexed_bounds_time).
+//
+// The class histogram of a box (count_bounds_by_class): the per-class breakdown of count_bounds_class for all 256 classes from
+// one pcq_scan_dev_class_hist_batch, instead of one combined count per class.
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -212,6 +215,50 @@ Status ResidentDataset::count_bounds_many(size_t nboxes, const double *bmin, con
     if (points_scanned)
         for (size_t q = 0; q < nboxes; q++) points_scanned[q] = scanned[q];
     if (points_read) *points_read = read;
+    return Status::Ok();
+}
+
+// What is in this box, by class: the prologue of count_box with a plain box predicate, then ONE pcq_scan_dev_class_hist_batch over
+// the positions and class blocks of the surviving files into PCQ_CLASS_BINS words of the dataset's counter.  `hist` is written
+// only when everything has succeeded.
+Status ResidentDataset::count_bounds_by_class(const AABB &bounds, uint64_t *hist, uint64_t *points_scanned) {
+    pcq_predicate pred{};
+    pred.kind = PCQ_PRED_BOUNDS;
+    std::vector<pcq_columns> cols;
+    std::vector<pcq_predicate> preds;
+    uint64_t scanned = 0;
+    for (const auto &f : files_) {
+        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
+        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        if (brc) return Status::FromLib(brc);
+        if (f.header.number_of_points == 0) continue;
+        pcq_columns c{};
+        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
+        c.cls = f.cls, c.cls_stride = 1;
+        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
+        cols.push_back(c);
+        preds.push_back(pred);
+        scanned += c.n;
+    }
+    if (counter_words_ < PCQ_CLASS_BINS) {
+        void *p = nullptr;
+        int rc = pcq_device_alloc(ctx_, PCQ_CLASS_BINS * 8, &p);
+        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed may have left launches that add into the old counter)
+        if (rc) {
+            if (p) pcq_device_free(ctx_, p);
+            return Status::FromLib(rc);
+        }
+        pcq_device_free(ctx_, counter_);
+        counter_ = (uint64_t *)p;
+        counter_words_ = PCQ_CLASS_BINS;
+    }
+    uint64_t bins[PCQ_CLASS_BINS];
+    int rc = pcq_device_memset(ctx_, counter_, 0, PCQ_CLASS_BINS * 8, nullptr);
+    if (!rc && !cols.empty()) rc = pcq_scan_dev_class_hist_batch(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
+    if (!rc) rc = pcq_copy_to_host(ctx_, bins, counter_, PCQ_CLASS_BINS * 8);  // waits for the context's stream
+    if (rc) return Status::FromLib(rc);
+    memcpy(hist, bins, sizeof bins);
+    if (points_scanned) *points_scanned = scanned;
     return Status::Ok();
 }
 

@@ -265,6 +265,18 @@ int pcq_scan_dev_count_batch_bounds_time(pcq_ctx *ctx, const pcq_columns *cols, 
 #define PCQ_MULTI_BOX_MAX 8
 int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
                                    size_t nqueries, uint64_t *device_totals, void *stream);
+/* The class histogram of a box in ONE pass: "what is in this box, by class?".  Every predicate is PCQ_PRED_BOUNDS, and segment
+ * i has the layout of pcq_scan_dev_count_batch_combined — packed positions (xyz_stride 12, 16-byte aligned) beside the packed
+ * class bytes of the same points (cls_stride 1, any alignment), both non-null when n > 0.  For every point of segment i inside
+ * the box of preds[i], device_hist[its class byte] is incremented: the counts are ADDED to PCQ_CLASS_BINS device words, so
+ * that device_hist[c] grows by what pcq_scan_dev_count_batch_combined counts for class c on the same segments and boxes, for
+ * every c at once and from one read of the data.  A predicate that is empty (lmin > lmax on an axis, or a box outside the i32
+ * value range) matches nothing and its segment is not evaluated.  nsegments == 0 is PCQ_OK.  A null argument, any other
+ * predicate kind (PCQ_PRED_BOUNDS_CLASS included) and any other layout are refused (PCQ_ERR_ARG) before anything is uploaded
+ * or launched: device_hist is untouched. */
+#define PCQ_CLASS_BINS 256
+int pcq_scan_dev_class_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
+                                  uint64_t *device_hist, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

@@ -110,6 +110,15 @@ int pcq_query_resident_count_bounds_class(pcq_host_resident *r, const double bmi
  * nothing is launched and nothing is written. */
 int pcq_query_resident_count_bounds_many(pcq_host_resident *r, size_t nboxes, const double *bmin, const double *bmax, uint64_t *matches,
                                          uint64_t *points_scanned, uint64_t *points_read);
+/* What is in this box, by class (`--combine --bounds ... --class c`, count only, for every c at once): hist[c] is what
+ * pcq_query_resident_count_bounds_class(r, bmin, bmax, c, ...) returns as matches, for every c in 0 .. 255, zeros included, and
+ * points_scanned (NULL: not wanted) is what that entry reports.  The per-file prologue of the bounds count (header early-out,
+ * box conversion; PCQ_ERR_PANIC for min > max) + ONE launch over the positions and classification blocks of the surviving
+ * files (pcq_scan_dev_class_hist_batch): the data is read once, not once per class, and the caller need not know which classes
+ * occur.  Works on a dataset from any of the loaders.  A null r, bmin, bmax or hist is PCQ_ERR_ARG before any device is
+ * touched; on any failure hist is left as it was. */
+int pcq_query_resident_count_bounds_by_class(pcq_host_resident *r, const double bmin[3], const double bmax[3], uint64_t hist[256],
+                                             uint64_t *points_scanned);
 /* Point and density queries over a resident dataset: the per-file searches over every loaded file, in load order, into ONE
  * collector.  Count and buffer collectors go through each file's chunk index (pcq_scan_dev_indexed: the first query of a
  * kind builds it, later ones read only the chunks that straddle the box); grid collectors through pcq_scan_dev, unpruned.

@@ -1,0 +1,76 @@
+"""The class histogram of a box: the libpcq entry (include/pcq.h: pcq_scan_dev_class_hist_batch) and the host entry
+(include/pcq_query.h: pcq_query_resident_count_bounds_by_class) are declared and exported beside the old batch entries, the
+binding has the method, the ABI number is what it was, and the host entry refuses null arguments before any device is touched —
+from python, and from a stand-alone driver built with ASan and UBSan (tests/native/class_hist_asan_driver.cpp).  No GPU call."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+PCQ_ERR_ARG = -8
+LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
+           "pcq_scan_dev_count_batch_multi"]
+QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
+             "pcq_query_resident_count_bounds_many"]
+
+
+def test_both_entries_are_declared_and_exported_beside_the_old_ones():
+    declared = pkg.declared_symbols(["pcq.h"])
+    exported = pkg.exported_symbols(pkg.lib_path())
+    for name in ["pcq_scan_dev_class_hist_batch"] + LIB_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    declared = pkg.declared_symbols(["pcq_query.h"])
+    exported = pkg.exported_symbols(os.path.join(PKG, "libpcq_query.so"))
+    for name in ["pcq_query_resident_count_bounds_by_class"] + QUERY_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    with open(os.path.join(ROOT, "include", "pcq.h")) as f:
+        assert "#define PCQ_CLASS_BINS 256" in f.read()
+
+
+def test_abi_number_is_unchanged_and_the_binding_has_the_method():
+    assert pkg.load_library().pcq_abi_version() == 6
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    assert callable(binding.Context.scan_dev_class_hist_batch)
+    assert callable(binding.Context.scan_dev_count_batch_combined)
+
+
+def test_host_entry_refuses_null_arguments_without_a_device():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    lib.pcq_query_resident_count_bounds_by_class.argtypes = [C.c_void_p, dd, dd, u64p, u64p]
+    dummy = C.c_void_p(1)  # never dereferenced: another argument is null
+    lo, hi = (C.c_double * 3)(0, 0, 0), (C.c_double * 3)(1, 1, 1)
+    sentinel = [1000 + 7 * c for c in range(256)]
+    hist = (C.c_uint64 * 256)(*sentinel)
+    s = C.c_uint64(15)
+    for args in ((None, lo, hi, hist, C.byref(s)), (dummy, None, hi, hist, C.byref(s)), (dummy, lo, None, hist, C.byref(s)),
+                 (dummy, lo, hi, None, C.byref(s)), (None, lo, hi, hist, None)):
+        assert lib.pcq_query_resident_count_bounds_by_class(*args) == PCQ_ERR_ARG
+        assert b"null argument" in lib.pcq_query_last_error()
+        assert list(hist) == sentinel and s.value == 15
+
+
+def test_host_entry_under_address_sanitizer(tmp_path):
+    """The null-argument paths of the new host entry under ASan + UBSan, through a stand-alone program (nothing sanitized is
+    loaded into python; no device is touched).  The two translation units the entry lives in — capi.cpp and resident.cpp — are
+    built sanitized into the program, where their definitions come first; the rest of the host layer is the libpcq_query.so
+    beside them, which keeps the build to a few seconds."""
+    host = os.path.join(PKG, "host")
+    exe = str(tmp_path / "class_hist_asan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
+           "-I" + os.path.join(ROOT, "include"), "-I" + host, os.path.join(ROOT, "tests", "native", "class_hist_asan_driver.cpp"),
+           os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG,
+           "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
+    assert r.stdout.split() == ["ok", "10"]
