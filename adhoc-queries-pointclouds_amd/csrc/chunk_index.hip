@@ -639,8 +639,8 @@ extern "C" int pcq_scan_dev_indexed(pcq_ctx *ctx, const pcq_columns *cols, const
                            ix->d_boxes, ctx->d_partials, ix->d_stats);
         ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
     }
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
-    PCQ_HIP(hipGetLastError());
+    rc = pcq_launch_finish_counts(ctx, 1, grid, c->d_count, s);
+    if (rc) return rc;
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned
         pcq_columns tail = *cols;
@@ -706,8 +706,8 @@ extern "C" int pcq_scan_dev_indexed_combined(pcq_ctx *ctx, const pcq_columns *co
     PCQ_HIP(hipMemsetAsync(ix->d_stats, 0, 4 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_index_count_bounds_class, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
                        cols->n, chunks, dp, ix->d_boxes, ix->d_hist, ctx->d_partials, ix->d_stats);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
-    PCQ_HIP(hipGetLastError());
+    rc = pcq_launch_finish_counts(ctx, 1, grid, c->d_count, s);
+    if (rc) return rc;
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS class bytes
         pcq_columns tail = *cols;
@@ -800,8 +800,8 @@ extern "C" int pcq_scan_dev_indexed_time(pcq_ctx *ctx, const pcq_columns *cols, 
                            ctx->d_partials, ix->d_stats);
         ix->stats_stream = s;  // fetched lazily by pcq_index_get_stats: no sync on the scan path
     }
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
-    PCQ_HIP(hipGetLastError());
+    rc = pcq_launch_finish_counts(ctx, 1, grid, c->d_count, s);
+    if (rc) return rc;
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS times (and positions, when present)
         pcq_columns tail = *cols;
@@ -869,8 +869,8 @@ extern "C" int pcq_scan_dev_indexed_bounds_time(pcq_ctx *ctx, const pcq_columns 
     // (both builders wrote the partials; the pruned count writes every one of the `grid` again before they are summed)
     hipLaunchKernelGGL(k_index_count_bounds_time, dim3(grid), dim3(BLOCK), 0, s, reinterpret_cast<const v4i *>(cols->xyz), (const uint8_t *)cols->cls,
                        chunks, dp, ix->d_boxes, ix->d_times, ctx->d_partials, ix->d_stats);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, grid, c->d_count);
-    PCQ_HIP(hipGetLastError());
+    rc = pcq_launch_finish_counts(ctx, 1, grid, c->d_count, s);
+    if (rc) return rc;
     const uint64_t rest_first = chunks * CHUNK_POINTS;
     if (rest_first < cols->n) {  // the ragged end (< one chunk) is always scanned, with ITS positions and ITS times
         pcq_columns tail = *cols;

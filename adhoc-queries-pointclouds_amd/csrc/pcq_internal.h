@@ -386,7 +386,8 @@ int pcq_launch_bounds_count_xyz12_col(pcq_ctx *ctx, const void *d_xyz, const voi
                                       hipStream_t s);
 int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8_t cls,
                               uint64_t *d_count, hipStream_t s);
-// scan_count_multi.hip: k_finish_counts on s — block q folds slice q (nblocks words) of the context's partials, += into d_counts[q]
+// scan_count_multi.hip: the finish reduction of every count kernel, k_finish_counts on s — block q folds slice q (nblocks words) of
+// the context's partials, += into d_counts[q]; nslices = 1 for the one-count kernels
 int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d_counts, hipStream_t s);
 // scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)
 int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s);

@@ -24,18 +24,13 @@
 // segments: less than (points + 512 x segments) / g + 1024.  With the full grid (4 x 256 CUs = 1024 workgroups on the MI355X) that
 // reaches 2^32 only above 4 x 10^12 points, or segments x 512, in all, and HBM (288 GB) holds 2 x 10^10 points at 13 B/point;
 // with the grid capped at steps + segments every wave has one step and one segment's leftovers at most.
-#include <vector>
-
 #include "pcq_internal.h"
-// (the one-box kinds' finish reduction k_finish_count of scan_tiles.h is not launched here: pcq_launch_finish_counts is)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
+#include "scan_batch_host.h"
 #include "scan_tiles.h"
-#pragma clang diagnostic pop
 
 namespace {
 
-// Workgroups (of one wave) per CU.  The kernel does more per tile than K1 (scan_count_multi.hip:25-29 has that case), but it stays
+// Workgroups (of one wave) per CU.  The kernel does more per tile than K1 (MULTI_WAVES_PER_CU in scan_count_multi.hip has that case), but it stays
 // bound by HBM: 16 files x 163 M points, every point inside the box, synth-doc classes, by workgroups per CU: 3: 5.41 ms, 4: 4.95,
 // 5: 5.34, 6: 5.28, 8: 5.30, 12: 5.26, 16: 5.41 (profiles/class_hist_rate_sweep.log; 32 uniform classes alike).  4 is one wave on
 // each SIMD of a CU; the box AND class count with K1's 3 takes 5.16 ms on the same data.
@@ -118,20 +113,20 @@ __global__ __launch_bounds__(64) void k_bounds_class_hist_pipe(const DevCombined
             cb = ca;
             if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
             pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<TILES, LOADS, COL>(A);
+            pipe_wait<LOADS>(A);
             if (!ca.empty) hist_eval<TILES, R>(A, ca, hl, hist, lane);
             if (u1 >= total_steps) break;
             const uint64_t u2 = u1 + stride;
             ca = cb;
             if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
             pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<TILES, LOADS, COL>(B);
+            pipe_wait<LOADS>(B);
             if (!cb.empty) hist_eval<TILES, R>(B, cb, hl, hist, lane);
             if (u2 >= total_steps) break;
             u = u2;
         }
-        pipe_wait<TILES, 0, COL>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<TILES, 0, COL>(B);
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
     }
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const DevCombinedSegment &g = segs[i];
@@ -169,54 +164,42 @@ extern "C" int pcq_scan_dev_class_hist_batch(pcq_ctx *ctx, const pcq_columns *co
         return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_class_hist_batch: null argument");
     if (nsegments == 0) return PCQ_OK;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the table first: nothing is touched when a segment is refused
-    std::vector<DevCombinedSegment> table(nsegments);
-    memset(table.data(), 0, nsegments * sizeof(DevCombinedSegment));
-    uint64_t steps = 0;
-    for (size_t i = 0; i < nsegments; i++) {
-        if (preds[i].kind != PCQ_PRED_BOUNDS)
-            return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i);
-        if (cols[i].xyz_stride != 12) return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: LAST positions blocks only (stride 12)");
-        if (((uintptr_t)cols[i].xyz & 15) != 0 || (!cols[i].xyz && cols[i].n))
-            return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: positions block %zu not 16-byte aligned", i);
-        if (cols[i].cls_stride != 1 || (!cols[i].cls && cols[i].n))
-            return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: LAST classification blocks only (stride 1), segment %zu", i);
-        DevPred dp;
-        const int rc = pcq_make_dev_pred(&preds[i], &dp);
-        if (rc) return rc;
-        DevCombinedSegment &g = table[i];
-        g.xyz = reinterpret_cast<const int4 *>(cols[i].xyz);
-        g.cls = (const uint8_t *)cols[i].cls;
-        g.n = cols[i].n;
-        g.tile_begin = steps;
-        for (int a = 0; a < 3; a++) g.lo[a] = dp.lo[a], g.width[a] = dp.width[a];
-        g.empty = dp.empty;
-        steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
-    }
-    int rc = pcq_scratch_stream(ctx, s);
-    if (rc) return rc;
-    rc = pcq_upload_segment_table(ctx, PCQ_SEGMENTS_CLASS_HIST, nsegments, table.data(), nsegments * sizeof(DevCombinedSegment), s);
-    if (rc) return rc;
     int waves = CLASS_HIST_WAVES_PER_CU;
 #ifdef PCQ_LAB  // (tools/resident_class_hist_rate.py sweeps both)
     if (ctx->class_hist_waves_per_cu) waves = ctx->class_hist_waves_per_cu;
     const int copies = ctx->class_hist_copies ? ctx->class_hist_copies : CLASS_HIST_COPIES;
 #endif
-    uint64_t g = (uint64_t)ctx->num_cus * (uint64_t)waves;
-    if (g > steps + nsegments) g = steps + nsegments;
-    rc = pcq_ensure_partials(ctx, (size_t)g * PCQ_CLASS_BINS);
-    if (rc) return rc;
+    const K1Batch b = {"class_hist_batch", PCQ_SEGMENTS_CLASS_HIST, waves, PCQ_CLASS_BINS, PCQ_CLASS_BINS, /*null_refused=*/true};
+    return k1_batch_launch<DevCombinedSegment>(
+        ctx, b, cols, nsegments, device_hist, s,
+        [&](size_t i) {
+            return preds[i].kind != PCQ_PRED_BOUNDS
+                       ? pcq_fail(PCQ_ERR_ARG, "class_hist_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
+                       : (int)PCQ_OK;
+        },
+        [&](DevCombinedSegment &g, size_t i) {
+            if (cols[i].cls_stride != 1 || (!cols[i].cls && cols[i].n))
+                return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: LAST classification blocks only (stride 1), segment %zu", i);
+            DevPred dp;
+            const int prc = pcq_make_dev_pred(&preds[i], &dp);
+            if (prc) return prc;
+            g.cls = (const uint8_t *)cols[i].cls;
+            seg_box(g, dp);
+            return (int)PCQ_OK;
+        },
+        [&](unsigned g, uint64_t steps) {
 #ifdef PCQ_LAB
-    switch (copies) {
-    case 1: launch_hist<1>(ctx, (unsigned)g, (int)nsegments, steps, s); break;
-    case 2: launch_hist<2>(ctx, (unsigned)g, (int)nsegments, steps, s); break;
-    case 4: launch_hist<4>(ctx, (unsigned)g, (int)nsegments, steps, s); break;
-    case 8: launch_hist<8>(ctx, (unsigned)g, (int)nsegments, steps, s); break;
-    case 16: launch_hist<16>(ctx, (unsigned)g, (int)nsegments, steps, s); break;
-    default: return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: option class_hist_copies %d (1, 2, 4, 8 or 16)", copies);
-    }
+            switch (copies) {
+            case 1: launch_hist<1>(ctx, g, (int)nsegments, steps, s); break;
+            case 2: launch_hist<2>(ctx, g, (int)nsegments, steps, s); break;
+            case 4: launch_hist<4>(ctx, g, (int)nsegments, steps, s); break;
+            case 8: launch_hist<8>(ctx, g, (int)nsegments, steps, s); break;
+            case 16: launch_hist<16>(ctx, g, (int)nsegments, steps, s); break;
+            default: return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: option class_hist_copies %d (1, 2, 4, 8 or 16)", copies);
+            }
 #else
-    launch_hist<CLASS_HIST_COPIES>(ctx, (unsigned)g, (int)nsegments, steps, s);
+            launch_hist<CLASS_HIST_COPIES>(ctx, g, (int)nsegments, steps, s);
 #endif
-    return pcq_launch_finish_counts(ctx, PCQ_CLASS_BINS, (int)g, device_hist, s);
+            return (int)PCQ_OK;
+        });
 }

@@ -24,14 +24,19 @@
 //    tile's 256 class bytes (one dword per lane) or 256 times (two dwordx4 per lane) are tested per lane into a verdict word;
 //    one ds_bpermute per (load, start phase) brings each point's verdict to the lane that holds its first dword, where it is
 //    ANDed into the mask algebra before the popcount.  13 / 20 B per point.
-// The batched K1 (k_bounds_count_batch_pipe<TILES, Col...>, the same pipeline with a cursor over the segments) and the finish
-//    reduction live in scan_tiles.h: pcq_scan_dev_count_batch below launches the box kind, scan_count_batch.hip the two kinds
-//    with a second column.  The batched K2 and the per-file kernels are here.
+// The loop of the software pipeline is written out in every kernel: a shared driver with the kernels as its stages compiled to
+//    the same vector code, but its other scalar code measured slower than this form in alternated runs ("The
+//    software pipeline").  The register sets, their loads and their counted waits are shared (scan_tiles.h: PipeRegs, VecRegs).
+// The batched K1 (k_bounds_count_batch_pipe<TILES, Col...>, the same loop written out) and the host side of its launch
+//    (k1_batch_launch, scan_batch_host.h) live in headers: pcq_scan_dev_count_batch below launches the box kind, scan_count_batch.hip the two
+//    kinds with a second column.  The batched K2 and the per-file kernels are here; the finish reduction of every count is
+//    pcq_launch_finish_counts (scan_count_multi.hip).
 // The kernel shapes these replaced (256-thread blocks, unpipelined one-wave forms, other tile counts) live
 // in csrc/lab/scan_count_lab.hip and are built only into libpcq_lab.so for the sweeps in tools/.
 #include <vector>
 
 #include "pcq_internal.h"
+#include "scan_batch_host.h"
 #include "scan_tiles.h"
 
 namespace {
@@ -59,18 +64,18 @@ __global__ __launch_bounds__(64) void k_bounds_count_w1_pipe(const v4i *__restri
         for (;;) {
             const uint64_t g1 = g + stride;
             pipe_load<TILES, COL>(B, base, g1 < steps ? g1 : g, lane, c2);  // clamped at the tail: a re-read that hits L2
-            pipe_wait<TILES, LOADS, COL>(A);                                 // A has landed, B's loads stay in flight
+            pipe_wait<LOADS>(A);                                 // A has landed, B's loads stay in flight
             total += pipe_eval<TILES, COL>(A, lb, c2);
             if (g1 >= steps) break;
             const uint64_t g2 = g1 + stride;
             pipe_load<TILES, COL>(A, base, g2 < steps ? g2 : g1, lane, c2);
-            pipe_wait<TILES, LOADS, COL>(B);
+            pipe_wait<LOADS>(B);
             total += pipe_eval<TILES, COL>(B, lb, c2);
             if (g2 >= steps) break;
             g = g2;
         }
-        pipe_wait<TILES, 0, COL>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<TILES, 0, COL>(B);
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
     }
     if (blockIdx.x == 0) {
         for (uint64_t t = steps * TILES; t < tiles; t++) {
@@ -104,27 +109,9 @@ __device__ __forceinline__ const DevClassSegment &cseg(const DevSegment *raw, in
     return *reinterpret_cast<const DevClassSegment *>(raw + i);
 }
 
-// Batched K2, one wave per workgroup, LOADS 1 KiB loads per step, software-pipelined like k_bounds_count_batch_pipe.
+// Batched K2, one wave per workgroup, LOADS 1 KiB loads per step (VecRegs), software-pipelined like k_bounds_count_batch_pipe.
 template <int LOADS>
-struct ClassRegs {
-    v4i r[LOADS];
-};
-template <int LOADS>
-__device__ __forceinline__ void class_load(ClassRegs<LOADS> &R, const v4i *tile, int lane) {
-#pragma unroll
-    for (int k = 0; k < LOADS; k++) {
-        const v4i *q = tile + 64 * k + lane;
-        asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(R.r[k]) : "v"(q) : "memory");
-    }
-}
-template <int LOADS, int PENDING>
-__device__ __forceinline__ void class_wait(ClassRegs<LOADS> &R) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
-#pragma unroll
-    for (int k = 0; k < LOADS; k++) asm volatile("" : "+v"(R.r[k])::"memory");
-}
-template <int LOADS>
-__device__ __forceinline__ uint32_t class_eval(const ClassRegs<LOADS> &R, uint32_t pat) {
+__device__ __forceinline__ uint32_t class_eval(const VecRegs<LOADS> &R, uint32_t pat) {
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < LOADS; k++)
@@ -156,30 +143,30 @@ __global__ __launch_bounds__(64) void k_class_count_batch_pipe(const DevSegment 
     const uint64_t stride = gridDim.x;
     uint32_t cnt = 0;
     if (blockIdx.x < total_steps) {
-        ClassRegs<LOADS> A, B;
+        VecRegs<LOADS> A, B;
         ClassCursor ca = {0, 0, 0, nullptr, 0}, cb;
         uint64_t u = blockIdx.x;
         class_seek<LOADS>(ca, raw, nseg, u);
-        class_load<LOADS>(A, ca.body + (u - ca.begin) * STEP_VEC, lane);
+        vec_load(A, ca.body + (u - ca.begin) * STEP_VEC, lane);
         for (;;) {
             const uint64_t u1 = u + stride;
             cb = ca;
             if (u1 < total_steps) class_seek<LOADS>(cb, raw, nseg, u1);
-            class_load<LOADS>(B, cb.body + ((u1 < total_steps ? u1 : u) - cb.begin) * STEP_VEC, lane);
-            class_wait<LOADS, LOADS>(A);
+            vec_load(B, cb.body + ((u1 < total_steps ? u1 : u) - cb.begin) * STEP_VEC, lane);
+            pipe_wait<LOADS>(A);
             cnt += class_eval<LOADS>(A, ca.pat);
             if (u1 >= total_steps) break;
             const uint64_t u2 = u1 + stride;
             ca = cb;
             if (u2 < total_steps) class_seek<LOADS>(ca, raw, nseg, u2);
-            class_load<LOADS>(A, ca.body + ((u2 < total_steps ? u2 : u1) - ca.begin) * STEP_VEC, lane);
-            class_wait<LOADS, LOADS>(B);
+            vec_load(A, ca.body + ((u2 < total_steps ? u2 : u1) - ca.begin) * STEP_VEC, lane);
+            pipe_wait<LOADS>(B);
             cnt += class_eval<LOADS>(B, cb.pat);
             if (u2 >= total_steps) break;
             u = u2;
         }
-        class_wait<LOADS, 0>(A);
-        class_wait<LOADS, 0>(B);
+        pipe_wait<0>(A);
+        pipe_wait<0>(B);
     }
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {
         const DevClassSegment g = cseg(raw, i);
@@ -214,24 +201,24 @@ __global__ __launch_bounds__(64) void k_class_count_pipe(const uint8_t *__restri
     const uint64_t steps = nvec / STEP_VEC, stride = gridDim.x;
     uint32_t cnt = 0;
     if (blockIdx.x < steps) {
-        ClassRegs<LOADS> A, B;
+        VecRegs<LOADS> A, B;
         uint64_t u = blockIdx.x;
-        class_load<LOADS>(A, body + u * STEP_VEC, lane);
+        vec_load(A, body + u * STEP_VEC, lane);
         for (;;) {
             const uint64_t u1 = u + stride;
-            class_load<LOADS>(B, body + (u1 < steps ? u1 : u) * STEP_VEC, lane);
-            class_wait<LOADS, LOADS>(A);
+            vec_load(B, body + (u1 < steps ? u1 : u) * STEP_VEC, lane);
+            pipe_wait<LOADS>(A);
             cnt += class_eval<LOADS>(A, pat);
             if (u1 >= steps) break;
             const uint64_t u2 = u1 + stride;
-            class_load<LOADS>(A, body + (u2 < steps ? u2 : u1) * STEP_VEC, lane);
-            class_wait<LOADS, LOADS>(B);
+            vec_load(A, body + (u2 < steps ? u2 : u1) * STEP_VEC, lane);
+            pipe_wait<LOADS>(B);
             cnt += class_eval<LOADS>(B, pat);
             if (u2 >= steps) break;
             u = u2;
         }
-        class_wait<LOADS, 0>(A);
-        class_wait<LOADS, 0>(B);
+        pipe_wait<0>(A);
+        pipe_wait<0>(B);
     }
     if (blockIdx.x == 0) {
         const uint8_t c8 = (uint8_t)(pat & 0xff);
@@ -267,9 +254,7 @@ static int launch_k1(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred 
     if (rc) return rc;
     hipLaunchKernelGGL((k_bounds_count_w1_pipe<K1_TILES, Col...>), dim3((unsigned)g), dim3(64), 0, s, reinterpret_cast<const v4i *>(d_xyz), n, pred,
                        ctx->d_partials, col...);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, d_count);
-    PCQ_HIP(hipGetLastError());
-    return PCQ_OK;
+    return pcq_launch_finish_counts(ctx, 1, (int)g, d_count, s);
 }
 
 int pcq_launch_bounds_count_xyz12(pcq_ctx *ctx, const void *d_xyz, uint64_t n, const DevPred &pred,
@@ -299,9 +284,41 @@ int pcq_launch_class_count_u8(pcq_ctx *ctx, const void *d_cls, uint64_t n, uint8
     if (rc) return rc;
     hipLaunchKernelGGL(k_class_count_pipe<K2_LOADS>, dim3((unsigned)g), dim3(64), 0, s, reinterpret_cast<const uint8_t *>(d_cls), n, pat, head,
                        nvec, ctx->d_partials);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, d_count);
-    PCQ_HIP(hipGetLastError());
-    return PCQ_OK;
+    return pcq_launch_finish_counts(ctx, 1, (int)g, d_count, s);
+}
+
+// The batched K2: one DevClassSegment per classification block (at DevSegment pitch), steps numbered across them.
+static int class_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments, uint64_t *device_total,
+                             hipStream_t s) {
+    static_assert(sizeof(DevClassSegment) <= sizeof(DevSegment), "the two segment tables share one buffer");
+    std::vector<DevSegment> table(nsegments);
+    memset(table.data(), 0, nsegments * sizeof(DevSegment));
+    uint64_t steps = 0;
+    for (size_t i = 0; i < nsegments; i++) {
+        if (preds[i].kind != PCQ_PRED_CLASS) return pcq_fail(PCQ_ERR_ARG, "count_batch: mixed predicate kinds");
+        if (cols[i].cls_stride != 1 || (!cols[i].cls && cols[i].n))
+            return pcq_fail(PCQ_ERR_ARG, "count_batch: LAST classification blocks only (stride 1)");
+        DevClassSegment g;
+        memset(&g, 0, sizeof g);
+        g.cls = (const uint8_t *)cols[i].cls;
+        g.n = cols[i].n;
+        g.head = (uint64_t)((16 - ((uintptr_t)g.cls & 15)) & 15);
+        if (g.head > g.n) g.head = g.n;
+        g.nvec = (g.n - g.head) / 16;
+        g.tile_begin = steps;
+        g.pat = 0x01010101u * (uint32_t)preds[i].cls;
+        memcpy(&table[i], &g, sizeof g);
+        steps += g.nvec / (64 * (uint64_t)K2_LOADS);
+    }
+    // (pcq_upload_segment_table: the table travels only when it differs from the one already in HBM)
+    int rc = pcq_upload_segment_table(ctx, PCQ_PRED_CLASS, nsegments, table.data(), nsegments * sizeof(DevSegment), s);
+    if (rc) return rc;
+    uint64_t g = (uint64_t)ctx->num_cus * K2_WAVES_PER_CU;
+    if (g > steps + nsegments) g = steps + nsegments;
+    rc = pcq_ensure_partials(ctx, (size_t)g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_class_count_batch_pipe<K2_LOADS>, dim3((unsigned)g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps, ctx->d_partials);
+    return pcq_launch_finish_counts(ctx, 1, (int)g, device_total, s);
 }
 
 extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
@@ -311,61 +328,25 @@ extern "C" int pcq_scan_dev_count_batch(pcq_ctx *ctx, const pcq_columns *cols, c
         return pcq_fail(PCQ_ERR_ARG, "pcq_scan_dev_count_batch: null argument");
     if (nsegments == 0) return PCQ_OK;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    {
+    {  // (this entry has always taken the scratch stream before it builds its table: k1_batch_launch's own call then finds it taken)
         const int src = pcq_scratch_stream(ctx, s);
         if (src) return src;
     }
-    static_assert(sizeof(DevClassSegment) <= sizeof(DevSegment), "the two segment tables share one buffer");
     const int kind = preds[0].kind;
-    // Build the segment table (pcq_upload_segment_table: it travels only when it differs from the one already in HBM)
-    std::vector<DevSegment> table(nsegments);
-    memset(table.data(), 0, nsegments * sizeof(DevSegment));
-    uint64_t steps = 0;
-    for (size_t i = 0; i < nsegments; i++) {
-        if (preds[i].kind != kind) return pcq_fail(PCQ_ERR_ARG, "count_batch: mixed predicate kinds");
-        if (kind == PCQ_PRED_CLASS) {
-            if (cols[i].cls_stride != 1 || (!cols[i].cls && cols[i].n))
-                return pcq_fail(PCQ_ERR_ARG, "count_batch: LAST classification blocks only (stride 1)");
-            DevClassSegment g;
-            memset(&g, 0, sizeof g);
-            g.cls = (const uint8_t *)cols[i].cls;
-            g.n = cols[i].n;
-            g.head = (uint64_t)((16 - ((uintptr_t)g.cls & 15)) & 15);
-            if (g.head > g.n) g.head = g.n;
-            g.nvec = (g.n - g.head) / 16;
-            g.tile_begin = steps;
-            g.pat = 0x01010101u * (uint32_t)preds[i].cls;
-            memcpy(&table[i], &g, sizeof g);
-            steps += g.nvec / (64 * (uint64_t)K2_LOADS);
-            continue;
-        }
-        if (kind != PCQ_PRED_BOUNDS) return pcq_fail(PCQ_ERR_ARG, "count_batch: bad predicate kind %d", kind);
-        if (cols[i].xyz_stride != 12) return pcq_fail(PCQ_ERR_ARG, "count_batch: LAST positions blocks only (stride 12)");
-        if (((uintptr_t)cols[i].xyz & 15) != 0) return pcq_fail(PCQ_ERR_ARG, "count_batch: positions block %zu not 16-byte aligned", i);
-        DevPred dp;
-        int rc = pcq_make_dev_pred(&preds[i], &dp);
-        if (rc) return rc;
-        DevSegment &g = table[i];
-        g.xyz = reinterpret_cast<const int4 *>(cols[i].xyz);
-        g.n = cols[i].n;
-        g.tile_begin = steps;
-        for (int a = 0; a < 3; a++) g.lo[a] = dp.lo[a], g.width[a] = dp.width[a];
-        g.empty = dp.empty;
-        steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
-    }
-    {
-        const int urc = pcq_upload_segment_table(ctx, kind, nsegments, table.data(), nsegments * sizeof(DevSegment), s);
-        if (urc) return urc;
-    }
-    uint64_t g = (uint64_t)ctx->num_cus * (kind == PCQ_PRED_CLASS ? K2_WAVES_PER_CU : K1_WAVES_PER_CU);
-    if (g > steps + nsegments) g = steps + nsegments;
-    int rc = pcq_ensure_partials(ctx, (size_t)g);
-    if (rc) return rc;
-    if (kind == PCQ_PRED_CLASS)
-        hipLaunchKernelGGL(k_class_count_batch_pipe<K2_LOADS>, dim3((unsigned)g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps, ctx->d_partials);
-    else
-        hipLaunchKernelGGL(k_bounds_count_batch_pipe<K1_TILES>, dim3((unsigned)g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps, ctx->d_partials);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, device_total);
-    PCQ_HIP(hipGetLastError());
-    return PCQ_OK;
+    if (kind == PCQ_PRED_CLASS) return class_count_batch(ctx, cols, preds, nsegments, device_total, s);
+    if (kind != PCQ_PRED_BOUNDS) return pcq_fail(PCQ_ERR_ARG, "count_batch: bad predicate kind %d", kind);
+    const K1Batch b = {"count_batch", PCQ_PRED_BOUNDS, K1_WAVES_PER_CU, 1, 1, /*null_refused=*/false};
+    return k1_batch_launch<DevSegment>(
+        ctx, b, cols, nsegments, device_total, s,
+        [&](size_t i) { return preds[i].kind != kind ? pcq_fail(PCQ_ERR_ARG, "count_batch: mixed predicate kinds") : (int)PCQ_OK; },
+        [&](DevSegment &g, size_t i) {
+            DevPred dp;
+            const int rc = pcq_make_dev_pred(&preds[i], &dp);
+            if (!rc) seg_box(g, dp);
+            return rc;
+        },
+        [&](unsigned g, uint64_t steps) {
+            hipLaunchKernelGGL(k_bounds_count_batch_pipe<K1_TILES>, dim3(g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps, ctx->d_partials);
+            return (int)PCQ_OK;
+        });
 }

@@ -3,11 +3,10 @@
 //
 // The kernel is k_bounds_count_batch_pipe<K1_TILES, ClassBytes / GpsTimes> (scan_tiles.h), the batched K1 with a compile-time
 // second column; the plain box kind is the same template without one, launched by pcq_scan_dev_count_batch (scan_count.hip).
-// One host routine serves both kinds here; per kind only the checks of the second column and the column's fields of a segment
-// differ (DevCombinedSegment / DevBoundsTimeSegment, each at its own pitch in the context's segment table).
-#include <vector>
-
+// k1_batch_launch (scan_batch_host.h) is the host side; per kind only the checks of the second column and the column's fields of a
+// segment differ (DevCombinedSegment / DevBoundsTimeSegment, each at its own pitch in the context's segment table).
 #include "pcq_internal.h"
+#include "scan_batch_host.h"
 #include "scan_tiles.h"
 
 namespace {
@@ -47,43 +46,29 @@ int count_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *pred
     if (!ctx || (!cols && nsegments) || (!preds && nsegments) || !device_total) return pcq_fail(PCQ_ERR_ARG, "%s: null argument", K::entry);
     if (nsegments == 0) return PCQ_OK;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the table first: nothing is touched when a segment is refused
-    std::vector<Seg> table(nsegments);
-    memset(table.data(), 0, nsegments * sizeof(Seg));
-    uint64_t steps = 0;
-    for (size_t i = 0; i < nsegments; i++) {
-        if (preds[i].kind != K::pred)
-            return pcq_fail(PCQ_ERR_ARG, "%s: predicate kind %d of segment %zu (%s only)", K::prefix, preds[i].kind, i, K::pred_name);
-        if (cols[i].xyz_stride != 12) return pcq_fail(PCQ_ERR_ARG, "%s: LAST positions blocks only (stride 12)", K::prefix);
-        if (((uintptr_t)cols[i].xyz & 15) != 0 || (!cols[i].xyz && cols[i].n))
-            return pcq_fail(PCQ_ERR_ARG, "%s: positions block %zu not 16-byte aligned", K::prefix, i);
-        Seg &g = table[i];
-        int rc = seg_column(g, cols[i], i);
-        if (rc) return rc;
-        DevPred dp;
-        rc = pcq_make_dev_pred(&preds[i], &dp);
-        if (rc) return rc;
-        g.xyz = reinterpret_cast<const int4 *>(cols[i].xyz);
-        g.n = cols[i].n;
-        g.tile_begin = steps;
-        for (int a = 0; a < 3; a++) g.lo[a] = dp.lo[a], g.width[a] = dp.width[a];
-        g.empty = dp.empty;
-        seg_pred(g, dp);
-        steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
-    }
-    int rc = pcq_scratch_stream(ctx, s);
-    if (rc) return rc;
-    rc = pcq_upload_segment_table(ctx, K::pred, nsegments, table.data(), nsegments * sizeof(Seg), s);
-    if (rc) return rc;
-    uint64_t g = (uint64_t)ctx->num_cus * K1_WAVES_PER_CU;
-    if (g > steps + nsegments) g = steps + nsegments;
-    rc = pcq_ensure_partials(ctx, (size_t)g);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_bounds_count_batch_pipe<K1_TILES, Col>), dim3((unsigned)g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps,
-                       ctx->d_partials);
-    hipLaunchKernelGGL(k_finish_count, dim3(1), dim3(BLOCK), 0, s, ctx->d_partials, (int)g, device_total);
-    PCQ_HIP(hipGetLastError());
-    return PCQ_OK;
+    const K1Batch b = {K::prefix, K::pred, K1_WAVES_PER_CU, 1, 1, /*null_refused=*/true};
+    return k1_batch_launch<Seg>(
+        ctx, b, cols, nsegments, device_total, s,
+        [&](size_t i) {
+            return preds[i].kind != K::pred
+                       ? pcq_fail(PCQ_ERR_ARG, "%s: predicate kind %d of segment %zu (%s only)", K::prefix, preds[i].kind, i, K::pred_name)
+                       : (int)PCQ_OK;
+        },
+        [&](Seg &g, size_t i) {
+            int rc = seg_column(g, cols[i], i);
+            if (rc) return rc;
+            DevPred dp;
+            rc = pcq_make_dev_pred(&preds[i], &dp);
+            if (rc) return rc;
+            seg_box(g, dp);
+            seg_pred(g, dp);
+            return (int)PCQ_OK;
+        },
+        [&](unsigned g, uint64_t steps) {
+            hipLaunchKernelGGL((k_bounds_count_batch_pipe<K1_TILES, Col>), dim3(g), dim3(64), 0, s, ctx->d_segments, (int)nsegments, steps,
+                               ctx->d_partials);
+            return (int)PCQ_OK;
+        });
 }
 
 }  // namespace

@@ -11,14 +11,9 @@
 // passes through SGPRs at a seek (seg_seek in scan_tiles.h has the reason).  A box whose live bit is clear — not asked of the
 // segment, or empty — is skipped by a wave-uniform branch.  The wave's NQ totals go to partials[q * gridDim.x + blockIdx.x];
 // k_finish_counts folds slice q into device_totals[q].
-#include <vector>
-
 #include "pcq_internal.h"
-// (the one-box kinds' finish reduction k_finish_count of scan_tiles.h is not launched here: k_finish_counts is)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
+#include "scan_batch_host.h"
 #include "scan_tiles.h"
-#pragma clang diagnostic pop
 
 namespace {
 
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(64) void k_bounds_count_multi_pipe(const DevMultiSe
                                                                uint64_t *__restrict__ partials) {
     static_assert(NQ >= 2 && NQ <= PCQ_MULTI_BOX_MAX, "boxes per pass");
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = TILES * 3;  // per register set
+    constexpr int LOADS = PipeRegs<TILES>::LOADS;  // per register set
     const int lane = threadIdx.x;
     const uint64_t stride = gridDim.x;
     uint64_t total[NQ];
@@ -99,20 +94,20 @@ __global__ __launch_bounds__(64) void k_bounds_count_multi_pipe(const DevMultiSe
             cb = ca;
             if (u1 < total_steps) multi_seek<TILES, NQ>(cb, segs, nseg, u1, lane);
             pipe_load<TILES>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane);  // clamped at the tail: an L2 hit
-            pipe_wait<TILES, LOADS, COL_NONE>(A);
+            pipe_wait<LOADS>(A);
             multi_eval<TILES, NQ>(A, ca, total);
             if (u1 >= total_steps) break;
             const uint64_t u2 = u1 + stride;
             ca = cb;
             if (u2 < total_steps) multi_seek<TILES, NQ>(ca, segs, nseg, u2, lane);
             pipe_load<TILES>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane);
-            pipe_wait<TILES, LOADS, COL_NONE>(B);
+            pipe_wait<LOADS>(B);
             multi_eval<TILES, NQ>(B, cb, total);
             if (u2 >= total_steps) break;
             u = u2;
         }
-        pipe_wait<TILES, 0, COL_NONE>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<TILES, 0, COL_NONE>(B);
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
     }
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point, every live box
         const DevMultiSegment &g = segs[i];
@@ -141,8 +136,9 @@ __global__ __launch_bounds__(64) void k_bounds_count_multi_pipe(const DevMultiSe
     }
 }
 
-// Folds the partial counts of the multi-box kernel and of the class histogram (scan_class_hist.hip, through
-// pcq_launch_finish_counts): block q folds slice q (nblocks words), += into d_counts[q].
+// THE finish reduction of every count kernel (pcq_launch_finish_counts): block q folds slice q of the per-workgroup partial
+// counts (nblocks words), += into d_counts[q].  One slice for the one-count kernels, a slice per box or class here and in
+// scan_class_hist.hip.
 __global__ __launch_bounds__(BLOCK) void k_finish_counts(const uint64_t *__restrict__ partials, int nblocks, uint64_t *__restrict__ d_counts) {
     __shared__ uint64_t s[BLOCK];
     const uint64_t *slice = partials + (uint64_t)blockIdx.x * (uint64_t)nblocks;
@@ -183,46 +179,31 @@ extern "C" int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *c
         return pcq_scan_dev_count_batch(ctx, cols, preds, nsegments, device_totals, stream);
     }
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    // the table first: nothing is touched when a segment is refused
-    std::vector<DevMultiSegment> table(nsegments);
-    memset(table.data(), 0, nsegments * sizeof(DevMultiSegment));
-    uint64_t steps = 0;
-    for (size_t i = 0; i < nsegments; i++) {
-        if (cols[i].xyz_stride != 12) return pcq_fail(PCQ_ERR_ARG, "count_batch_multi: LAST positions blocks only (stride 12)");
-        if (((uintptr_t)cols[i].xyz & 15) != 0 || (!cols[i].xyz && cols[i].n))
-            return pcq_fail(PCQ_ERR_ARG, "count_batch_multi: positions block %zu not 16-byte aligned", i);
-        DevMultiSegment &g = table[i];
-        g.xyz = reinterpret_cast<const int4 *>(cols[i].xyz);
-        g.n = cols[i].n;
-        g.tile_begin = steps;
-        for (size_t q = 0; q < nqueries; q++) {
-            const pcq_predicate &p = preds[i * nqueries + q];
-            DevPred dp;
-            const int rc = pcq_make_dev_pred(&p, &dp);
-            if (rc) return rc;
-            if (dp.empty) continue;  // the slot stays zero and its live bit clear
-            g.live |= 1u << q;
-            for (int a = 0; a < 3; a++) g.lo[q][a] = dp.lo[a], g.width[q][a] = dp.width[a];
-        }
-        steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
-    }
     const int nq = nqueries <= 2 ? 2 : (nqueries <= 4 ? 4 : 8);  // the instantiation: slots from nqueries on are dead
-    int rc = pcq_scratch_stream(ctx, s);
-    if (rc) return rc;
-    rc = pcq_upload_segment_table(ctx, PCQ_SEGMENTS_MULTI, nsegments, table.data(), nsegments * sizeof(DevMultiSegment), s);
-    if (rc) return rc;
-#ifdef PCQ_LAB
-    uint64_t g = (uint64_t)ctx->num_cus * (ctx->multi_waves_per_cu ? ctx->multi_waves_per_cu : MULTI_WAVES_PER_CU);  // (tools/resident_multi_rate.py sweeps it)
-#else
-    uint64_t g = (uint64_t)ctx->num_cus * MULTI_WAVES_PER_CU;
+    int waves = MULTI_WAVES_PER_CU;
+#ifdef PCQ_LAB  // (tools/resident_multi_rate.py sweeps it)
+    if (ctx->multi_waves_per_cu) waves = ctx->multi_waves_per_cu;
 #endif
-    if (g > steps + nsegments) g = steps + nsegments;
-    rc = pcq_ensure_partials(ctx, (size_t)g * (size_t)nq);
-    if (rc) return rc;
-    if (nq == 2) launch_multi<2>(ctx, (unsigned)g, (int)nsegments, steps, s);
-    else if (nq == 4) launch_multi<4>(ctx, (unsigned)g, (int)nsegments, steps, s);
-    else launch_multi<8>(ctx, (unsigned)g, (int)nsegments, steps, s);
-    return pcq_launch_finish_counts(ctx, (int)nqueries, (int)g, device_totals, s);
+    const K1Batch b = {"count_batch_multi", PCQ_SEGMENTS_MULTI, waves, nq, (int)nqueries, /*null_refused=*/true};
+    return k1_batch_launch<DevMultiSegment>(
+        ctx, b, cols, nsegments, device_totals, s, [](size_t) { return (int)PCQ_OK; },
+        [&](DevMultiSegment &g, size_t i) {
+            for (size_t q = 0; q < nqueries; q++) {
+                DevPred dp;
+                const int rc = pcq_make_dev_pred(&preds[i * nqueries + q], &dp);
+                if (rc) return rc;
+                if (dp.empty) continue;  // the slot stays zero and its live bit clear
+                g.live |= 1u << q;
+                for (int a = 0; a < 3; a++) g.lo[q][a] = dp.lo[a], g.width[q][a] = dp.width[a];
+            }
+            return (int)PCQ_OK;
+        },
+        [&](unsigned g, uint64_t steps) {
+            if (nq == 2) launch_multi<2>(ctx, g, (int)nsegments, steps, s);
+            else if (nq == 4) launch_multi<4>(ctx, g, (int)nsegments, steps, s);
+            else launch_multi<8>(ctx, g, (int)nsegments, steps, s);
+            return (int)PCQ_OK;
+        });
 }
 
 int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d_counts, hipStream_t s) {

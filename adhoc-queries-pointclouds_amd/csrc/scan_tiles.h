@@ -1,8 +1,10 @@
-// scan_tiles.h — the wave-tile count of packed LAST positions, shared by the count kernels (scan_count.hip,
-// scan_count_batch.hip) and the chunk index (chunk_index.hip): the mask algebra of a 768-dword tile, K1's second column
-// (class bytes or GPS times), the software-pipeline helpers, the batched K1 itself (k_bounds_count_batch_pipe: one template for
-// the box, box AND class and box AND time kinds) and the finish reduction of every count (k_finish_count).  See scan_count.hip
-// for the design.
+// scan_tiles.h — what the count kernels (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip, scan_class_hist.hip,
+// scan_time.hip) and the chunk index (chunk_index.hip) share: the mask algebra of a 768-dword tile of packed LAST positions,
+// K1's second column (class bytes or GPS times), the register sets of the software pipeline with their loads and counted waits
+// (PipeRegs for the K1 family, VecRegs for the one-column kernels K2 and K3; the loop itself is written in each kernel: see
+// scan_count.hip) and the batched K1 (k_bounds_count_batch_pipe: one template for the box, box AND class and box AND time
+// kinds).  The host side of a K1-family batched launch is k1_batch_launch (scan_batch_host.h); the finish reduction of every
+// count is pcq_launch_finish_counts (scan_count_multi.hip).  See scan_count.hip for the design.
 #pragma once
 
 #include "pcq_internal.h"
@@ -218,16 +220,18 @@ __device__ __forceinline__ uint32_t tile_count_masks(const v4i *tile, int lane, 
 
 // Software pipeline: asm volatile statements keep their order; the empty asm behind each s_waitcnt re-defines the
 // registers it guards, so no use can be hoisted above the wait.
+constexpr int col2_loads(int col) { return col == COL_NONE ? 0 : 2; }  // per tile
 template <int TILES, int COL = COL_NONE>
 struct PipeRegs {
+    static constexpr int LOADS = TILES * (3 + col2_loads(COL));  // what a counted wait leaves in flight
     v4i r[TILES][3];
     Col2Regs<COL> c[TILES];
 };
 template <int TILES>
 struct PipeRegs<TILES, COL_NONE> {
+    static constexpr int LOADS = TILES * 3;
     v4i r[TILES][3];
 };
-constexpr int col2_loads(int col) { return col == COL_NONE ? 0 : 2; }  // per tile
 // the second column of tile `tile` (two loads per lane, issued behind the positions: the waits count them)
 __device__ __forceinline__ void col2_load(Col2Regs<COL_U8> &r, const Col2<COL_U8> &c, uint64_t tile) {
     const uint8_t *tb = c.base + tile * 256;
@@ -283,7 +287,7 @@ __device__ __forceinline__ void pipe_load(PipeRegs<TILES> &R, const v4i *base, u
     pipe_load<TILES, COL_NONE>(R, base, step, lane, Col2<COL_NONE>{});
 }
 // PENDING: the loads of the other register set, which stay in flight
-template <int TILES, int PENDING, int COL>
+template <int PENDING, int TILES, int COL>
 __device__ __forceinline__ void pipe_wait(PipeRegs<TILES, COL> &R) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
 #pragma unroll
@@ -306,6 +310,27 @@ __device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES, COL> &R, con
 template <int TILES>
 __device__ __forceinline__ uint64_t pipe_eval(const PipeRegs<TILES> &R, const LaneBox &lb) {
     return pipe_eval<TILES, COL_NONE>(R, lb, Col2<COL_NONE>{});
+}
+
+// The register set of the one-column kernels (K2's class bytes, K3's times): LOADS x 1 KiB of a packed column per step.
+template <int N>
+struct VecRegs {
+    static constexpr int LOADS = N;
+    v4i r[N];
+};
+template <int N>
+__device__ __forceinline__ void vec_load(VecRegs<N> &R, const v4i *step, int lane) {
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const v4i *q = step + 64 * k + lane;
+        asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(R.r[k]) : "v"(q) : "memory");
+    }
+}
+template <int PENDING, int N>
+__device__ __forceinline__ void pipe_wait(VecRegs<N> &R) {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
+#pragma unroll
+    for (int k = 0; k < N; k++) asm volatile("" : "+v"(R.r[k])::"memory");
 }
 
 // The second column as a kernel's last template argument: none (the plain K1), ClassBytes (PCQ_PRED_BOUNDS_CLASS) or GpsTimes
@@ -464,7 +489,7 @@ __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment
     static_assert(sizeof...(Col) <= 1, "one second column at most");
     typedef typename BatchSeg<COL>::type Seg;
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = TILES * (3 + col2_loads(COL));  // per register set
+    constexpr int LOADS = PipeRegs<TILES, COL>::LOADS;  // per register set
     const Seg *__restrict__ segs = reinterpret_cast<const Seg *>(raw);
     const int lane = threadIdx.x;
     const uint64_t stride = gridDim.x;
@@ -483,20 +508,20 @@ __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment
             cb = ca;
             if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
             pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<TILES, LOADS, COL>(A);
+            pipe_wait<LOADS>(A);
             if (!ca.empty) total += pipe_eval<TILES, COL>(A, ca.lb, col2_of(lanes, ca.col));
             if (u1 >= total_steps) break;
             const uint64_t u2 = u1 + stride;
             ca = cb;
             if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
             pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<TILES, LOADS, COL>(B);
+            pipe_wait<LOADS>(B);
             if (!cb.empty) total += pipe_eval<TILES, COL>(B, cb.lb, col2_of(lanes, cb.col));
             if (u2 >= total_steps) break;
             u = u2;
         }
-        pipe_wait<TILES, 0, COL>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<TILES, 0, COL>(B);
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
     }
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const Seg &g = segs[i];
@@ -515,21 +540,6 @@ __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment
         }
     }
     if (lane == 0) partials[blockIdx.x] = total;
-}
-
-// Folds the per-workgroup partial counts of any of the count kernels: one block, += into *d_count.
-__global__ __launch_bounds__(BLOCK) void k_finish_count(const uint64_t *__restrict__ partials, int nblocks,
-                                                        uint64_t *__restrict__ d_count) {
-    __shared__ uint64_t s[BLOCK];
-    uint64_t t = 0;
-    for (int i = threadIdx.x; i < nblocks; i += BLOCK) t += partials[i];
-    s[threadIdx.x] = t;
-    __syncthreads();
-    for (int off = BLOCK / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd((unsigned long long *)d_count, (unsigned long long)s[0]);
 }
 
 }  // namespace

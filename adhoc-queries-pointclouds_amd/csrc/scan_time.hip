@@ -9,6 +9,7 @@
 // and every workgroup adds its count with one atomic.  A column that is not 8-byte aligned (or strided: LAS records) is
 // counted by k_generic_count<PCQ_PRED_TIME> (scan_generic.hip).
 #include "dev_common.h"
+#include "scan_tiles.h"
 
 using namespace pcqdev;
 
@@ -17,33 +18,12 @@ namespace {
 constexpr int K3_LOADS = 4;         // 1 KiB loads per step: 512 times per wave and step
 constexpr int K3_WAVES_PER_CU = 4;  // K2's measured shape (profiles/r01_k2_sweep.log)
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-template <int LOADS>
-struct TimeRegs {
-    v4i r[LOADS];
-};
-template <int LOADS>
-__device__ __forceinline__ void time_load(TimeRegs<LOADS> &R, const v4i *tile, int lane) {
-#pragma unroll
-    for (int k = 0; k < LOADS; k++) {
-        const v4i *q = tile + 64 * k + lane;
-        asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(R.r[k]) : "v"(q) : "memory");
-    }
-}
-// the empty asm behind the wait re-defines the registers it guards: no use can be hoisted above it
-template <int LOADS, int PENDING>
-__device__ __forceinline__ void time_wait(TimeRegs<LOADS> &R) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PENDING) : "memory");
-#pragma unroll
-    for (int k = 0; k < LOADS; k++) asm volatile("" : "+v"(R.r[k])::"memory");
-}
 __device__ __forceinline__ double f64_of(int lo, int hi) {
     return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
 }
 __device__ __forceinline__ bool in_range(double t, double t0, double t1) { return (t >= t0) & (t < t1); }
 template <int LOADS>
-__device__ __forceinline__ uint32_t time_eval(const TimeRegs<LOADS> &R, double t0, double t1) {
+__device__ __forceinline__ uint32_t time_eval(const VecRegs<LOADS> &R, double t0, double t1) {
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < LOADS; k++) {
@@ -63,24 +43,24 @@ __global__ __launch_bounds__(64) void k_time_count_pipe(const double *__restrict
     const uint64_t steps = nvec / STEP_VEC, stride = gridDim.x;
     uint32_t cnt = 0;  // (wave-uniform)
     if (blockIdx.x < steps) {
-        TimeRegs<LOADS> A, B;
+        VecRegs<LOADS> A, B;
         uint64_t u = blockIdx.x;
-        time_load<LOADS>(A, body + u * STEP_VEC, lane);
+        vec_load(A, body + u * STEP_VEC, lane);
         for (;;) {
             const uint64_t u1 = u + stride;
-            time_load<LOADS>(B, body + (u1 < steps ? u1 : u) * STEP_VEC, lane);  // clamped at the tail: a re-read that hits L2
-            time_wait<LOADS, LOADS>(A);
+            vec_load(B, body + (u1 < steps ? u1 : u) * STEP_VEC, lane);  // clamped at the tail: a re-read that hits L2
+            pipe_wait<LOADS>(A);
             cnt += time_eval<LOADS>(A, t0, t1);
             if (u1 >= steps) break;
             const uint64_t u2 = u1 + stride;
-            time_load<LOADS>(A, body + (u2 < steps ? u2 : u1) * STEP_VEC, lane);
-            time_wait<LOADS, LOADS>(B);
+            vec_load(A, body + (u2 < steps ? u2 : u1) * STEP_VEC, lane);
+            pipe_wait<LOADS>(B);
             cnt += time_eval<LOADS>(B, t0, t1);
             if (u2 >= steps) break;
             u = u2;
         }
-        time_wait<LOADS, 0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        time_wait<LOADS, 0>(B);
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
     }
     if (blockIdx.x == 0) {
         for (uint64_t v0 = steps * STEP_VEC; v0 < nvec; v0 += 64) {  // fewer than a step of leftover vectors

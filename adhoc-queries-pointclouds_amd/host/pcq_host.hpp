@@ -412,15 +412,22 @@ public:
 
 private:
     ResidentDataset() = default;
-    Status run(int kind, const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches);
-    Status count_box(const AABB &bounds, pcq_predicate pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
+    struct Segments;
+    typedef int (*BatchEntry)(pcq_ctx *, const pcq_columns *, const pcq_predicate *, size_t, uint64_t *, void *);  // pcq_scan_dev_count_batch*, _class_hist_batch
+    int ensure_counter(size_t words);
+    template <typename Launch>
+    Status read_counts(size_t words, Launch launch, uint64_t *out);  // (resident.cpp only)
+    Status box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg);
+    Status run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out);
+    Status count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
+    Status search_files(const AABB *bounds, pcq_predicate pred, ResultCollector &rc);  // search_*
     pcq_ctx *ctx_ = nullptr;
     bool with_points_ = false, with_times_ = false;
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (count_bounds_many grows it to a word per box, count_bounds_by_class to a word per class)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class)
     uint64_t points_ = 0;
 };
 

@@ -99,47 +99,116 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
     return Status::Ok();
 }
 
-// One batched launch of the kind's entry over the segments, the total into the dataset's counter and back.
-Status ResidentDataset::run(int kind, const std::vector<pcq_columns> &cols, const std::vector<pcq_predicate> &preds, uint64_t *matches) {
-    const auto entry = kind == PCQ_PRED_BOUNDS_CLASS  ? pcq_scan_dev_count_batch_combined
-                       : kind == PCQ_PRED_BOUNDS_TIME ? pcq_scan_dev_count_batch_bounds_time
-                                                      : pcq_scan_dev_count_batch;
-    int rc = pcq_device_memset(ctx_, counter_, 0, 8, nullptr);
-    if (!rc && !cols.empty()) rc = entry(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
-    if (!rc) rc = pcq_copy_to_host(ctx_, matches, counter_, 8);  // waits for the context's stream
-    return Status::FromLib(rc);
+static const char *const NO_COLOURS = "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)";
+static const char *const NO_TIMES = "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)";
+
+// A query's predicate but for its box: the class is the whole byte (last.rs:259-262), the times Range { start, end }: start <= t && t < end
+// (las.rs:336).
+static pcq_predicate predicate(int kind, uint8_t cls = 0, double start = 0.0, double end = 0.0) {
+    pcq_predicate pred{};
+    pred.kind = kind, pred.cls = cls, pred.wmin[0] = start, pred.wmax[0] = end;
+    return pred;
 }
 
-// The three box counts: per file the prologue the reference runs before its loop, then one batched launch over the surviving
-// files.  `pred` brings the kind and what it tests besides the box (cls; [wmin[0], wmax[0])); the kind picks the second column
-// (PCQ_PRED_BOUNDS_CLASS: the classification block, PCQ_PRED_BOUNDS_TIME: the time block).
-Status ResidentDataset::count_box(const AABB &bounds, pcq_predicate pred, uint64_t *matches, uint64_t *points_scanned) {
+// The prologue the reference runs per file before its loop, in its order: the header early-out (last.rs:92-94), the f64 -> local
+// integer box (:98-109) with its error, then the skip of a file without points.  *scan: the file is to be scanned with pred's box.
+static int box_prologue(const ResidentFile &f, const AABB &bounds, pcq_predicate *pred, bool *scan) {
+    *scan = false;
+    if (!f.header.bounds.intersects(bounds)) return PCQ_OK;
+    const int rc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred->lmin, pred->lmax);
+    *scan = !rc && f.header.number_of_points != 0;
+    return rc;
+}
+
+// The resident blocks of a file as a scan's columns: the positions, and the second column a predicate of `kind` tests (the class
+// block; the time block for the kinds that test GPS times; none for a plain box).
+static pcq_columns file_columns(const ResidentFile &f, int kind) {
+    pcq_columns c{};
+    c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;  // last.rs:114-121
+    if (kind == PCQ_PRED_CLASS || kind == PCQ_PRED_BOUNDS_CLASS) c.cls = f.cls, c.cls_stride = 1;  // :138-142
+    if (kind == PCQ_PRED_TIME || kind == PCQ_PRED_BOUNDS_TIME) c.cls = f.time, c.cls_stride = 8;
+    for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];  // :156-160
+    return c;
+}
+
+// The dataset's device counter, `words` words at least.  A call that failed has left launches on the context's stream that add
+// into the old counter, so the stream is drained before that one is freed.
+int ResidentDataset::ensure_counter(size_t words) {
+    if (words <= counter_words_) return PCQ_OK;
+    void *p = nullptr;
+    int rc = pcq_device_alloc(ctx_, words * 8, &p);
+    if (!rc) rc = pcq_ctx_synchronize(ctx_);
+    if (rc) {
+        if (p) pcq_device_free(ctx_, p);
+        return rc;
+    }
+    pcq_device_free(ctx_, counter_);
+    counter_ = (uint64_t *)p;
+    counter_words_ = words;
+    return PCQ_OK;
+}
+
+// `words` words of the counter zeroed, `launch` adding into them on the context's stream, then copied back (which waits for the
+// stream).  `out` is written only when everything has succeeded.
+template <typename Launch>
+Status ResidentDataset::read_counts(size_t words, Launch launch, uint64_t *out) {
+    uint64_t few[PCQ_CLASS_BINS];
+    std::vector<uint64_t> many(words > PCQ_CLASS_BINS ? words : 0);  // (more boxes than classes: count_bounds_many)
+    uint64_t *got = many.empty() ? few : many.data();
+    int rc = ensure_counter(words);
+    if (!rc) rc = pcq_device_memset(ctx_, counter_, 0, words * 8, nullptr);
+    if (!rc) rc = launch();
+    if (!rc) rc = pcq_copy_to_host(ctx_, got, counter_, words * 8);
+    if (rc) return Status::FromLib(rc);
+    memcpy(out, got, words * 8);
+    return Status::Ok();
+}
+
+// The segments of one batched launch: the surviving files' columns, each with its predicate, and their points.
+struct ResidentDataset::Segments {
     std::vector<pcq_columns> cols;
     std::vector<pcq_predicate> preds;
     uint64_t scanned = 0;
+};
+
+// The prologue for every file: a segment per surviving file, `pred` with the box in that file's integers, `col_kind` picking
+// the second column.
+Status ResidentDataset::box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg) {
     for (const auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        bool go;
+        const int brc = box_prologue(f, bounds, &pred, &go);
         if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        pcq_columns c{};
-        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
-        if (pred.kind == PCQ_PRED_BOUNDS_CLASS) c.cls = f.cls, c.cls_stride = 1;
-        if (pred.kind == PCQ_PRED_BOUNDS_TIME) c.cls = f.time, c.cls_stride = 8;
-        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
-        cols.push_back(c);
-        preds.push_back(pred);
-        scanned += c.n;
+        if (!go) continue;
+        seg->cols.push_back(file_columns(f, col_kind));
+        seg->preds.push_back(pred);
+        seg->scanned += f.header.number_of_points;
     }
-    if (points_scanned) *points_scanned = scanned;
-    return run(pred.kind, cols, preds, matches);
+    return Status::Ok();
+}
+
+// ONE batched launch of `entry` over the segments, `words` words of counts into the dataset's counter and back.
+Status ResidentDataset::run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out) {
+    return read_counts(
+        words, [&] { return seg.cols.empty() ? (int)PCQ_OK : entry(ctx_, seg.cols.data(), seg.preds.data(), seg.cols.size(), counter_, nullptr); }, out);
+}
+
+// The three box counts: per file the prologue the reference runs before its loop, then one batched launch over the surviving
+// files.  `pred` brings the kind and what it tests besides the box (cls; [wmin[0], wmax[0])); the kind picks the entry and the
+// second column (PCQ_PRED_BOUNDS_CLASS: the classification block, PCQ_PRED_BOUNDS_TIME: the time block).
+Status ResidentDataset::count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned) {
+    Segments seg;
+    Status st = box_segments(bounds, pred, pred.kind, &seg);
+    if (!st.ok()) return st;
+    if (points_scanned) *points_scanned = seg.scanned;
+    return run(pred.kind == PCQ_PRED_BOUNDS_CLASS  ? pcq_scan_dev_count_batch_combined
+               : pred.kind == PCQ_PRED_BOUNDS_TIME ? pcq_scan_dev_count_batch_bounds_time
+                                                   : pcq_scan_dev_count_batch,
+               1, seg, matches);
 }
 
 // `--bounds` over the dataset, count only: BoundsSearcher + CountCollector + the sum of main.rs:164-180.
 Status ResidentDataset::count_bounds(const AABB &bounds, uint64_t *matches, uint64_t *points_scanned) {
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS;
-    return count_box(bounds, pred, matches, points_scanned);
+    return count_box(bounds, predicate(PCQ_PRED_BOUNDS), matches, points_scanned);
 }
 
 // Many boxes, one pass per group of PCQ_MULTI_BOX_MAX (pcq_scan_dev_count_batch_multi).  First the prologue of count_box for every
@@ -157,61 +226,46 @@ Status ResidentDataset::count_bounds_many(size_t nboxes, const double *bmin, con
     for (int a = 0; a < 3; a++) none.lmin[a] = 1, none.lmax[a] = 0;
     std::vector<pcq_predicate> local(nboxes * nfiles, none);  // [box][file]
     std::vector<uint8_t> asked(nboxes * nfiles, 0);
-    std::vector<uint64_t> scanned(nboxes, 0), counts(nboxes, 0);
+    std::vector<uint64_t> scanned(nboxes, 0);
+    Status st = Status::Ok();
     for (size_t q = 0; q < nboxes; q++) {
         AABB bounds;
-        Status st = AABB::from_min_max(bmin + 3 * q, bmax + 3 * q, &bounds);
+        st = AABB::from_min_max(bmin + 3 * q, bmax + 3 * q, &bounds);
         if (!st.ok()) return st;
         for (size_t i = 0; i < nfiles; i++) {
-            const ResidentFile &f = files_[i];
-            if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-            pcq_predicate pred{};
-            pred.kind = PCQ_PRED_BOUNDS;
-            const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+            pcq_predicate pred = predicate(PCQ_PRED_BOUNDS);
+            bool go;
+            const int brc = box_prologue(files_[i], bounds, &pred, &go);
             if (brc) return Status::FromLib(brc);
-            if (f.header.number_of_points == 0) continue;
+            if (!go) continue;
             local[q * nfiles + i] = pred;
             asked[q * nfiles + i] = 1;
-            scanned[q] += f.header.number_of_points;
+            scanned[q] += files_[i].header.number_of_points;
         }
     }
-    if (nboxes > counter_words_) {
-        void *p = nullptr;
-        int rc = pcq_device_alloc(ctx_, nboxes * 8, &p);
-        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed between two groups has left launches that add into the old counter)
-        if (rc) {
-            if (p) pcq_device_free(ctx_, p);
-            return Status::FromLib(rc);
-        }
-        pcq_device_free(ctx_, counter_);
-        counter_ = (uint64_t *)p;
-        counter_words_ = nboxes;
-    }
-    int rc = pcq_device_memset(ctx_, counter_, 0, nboxes * 8, nullptr);
     uint64_t read = 0;
-    std::vector<pcq_columns> cols;
-    std::vector<pcq_predicate> preds;
-    for (size_t q0 = 0; q0 < nboxes && !rc; q0 += PCQ_MULTI_BOX_MAX) {
-        const size_t nq = nboxes - q0 < PCQ_MULTI_BOX_MAX ? nboxes - q0 : (size_t)PCQ_MULTI_BOX_MAX;
-        cols.clear();
-        preds.clear();
-        for (size_t i = 0; i < nfiles; i++) {
-            const ResidentFile &f = files_[i];
-            bool met = false;
-            for (size_t q = q0; q < q0 + nq; q++) met |= asked[q * nfiles + i] != 0;
-            if (!met) continue;
-            pcq_columns c{};
-            c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
-            for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
-            cols.push_back(c);
-            for (size_t q = q0; q < q0 + nq; q++) preds.push_back(local[q * nfiles + i]);
-            read += c.n;
+    // (the copy back waits for the context's stream; a group whose table differs from the one in HBM has waited once before its upload)
+    st = read_counts(nboxes, [&] {
+        std::vector<pcq_columns> cols;
+        std::vector<pcq_predicate> preds;
+        int rc = PCQ_OK;
+        for (size_t q0 = 0; q0 < nboxes && !rc; q0 += PCQ_MULTI_BOX_MAX) {
+            const size_t nq = nboxes - q0 < PCQ_MULTI_BOX_MAX ? nboxes - q0 : (size_t)PCQ_MULTI_BOX_MAX;
+            cols.clear();
+            preds.clear();
+            for (size_t i = 0; i < nfiles; i++) {
+                bool met = false;
+                for (size_t q = q0; q < q0 + nq; q++) met |= asked[q * nfiles + i] != 0;
+                if (!met) continue;
+                cols.push_back(file_columns(files_[i], PCQ_PRED_BOUNDS));
+                for (size_t q = q0; q < q0 + nq; q++) preds.push_back(local[q * nfiles + i]);
+                read += files_[i].header.number_of_points;
+            }
+            if (!cols.empty()) rc = pcq_scan_dev_count_batch_multi(ctx_, cols.data(), preds.data(), cols.size(), nq, counter_ + q0, nullptr);
         }
-        if (!cols.empty()) rc = pcq_scan_dev_count_batch_multi(ctx_, cols.data(), preds.data(), cols.size(), nq, counter_ + q0, nullptr);
-    }
-    if (!rc) rc = pcq_copy_to_host(ctx_, counts.data(), counter_, nboxes * 8);  // waits for the context's stream (a group whose table differs from the one in HBM has waited once before its upload)
-    if (rc) return Status::FromLib(rc);
-    for (size_t q = 0; q < nboxes; q++) matches[q] = counts[q];
+        return rc;
+    }, matches);
+    if (!st.ok()) return st;
     if (points_scanned)
         for (size_t q = 0; q < nboxes; q++) points_scanned[q] = scanned[q];
     if (points_read) *points_read = read;
@@ -222,99 +276,49 @@ Status ResidentDataset::count_bounds_many(size_t nboxes, const double *bmin, con
 // the positions and class blocks of the surviving files into PCQ_CLASS_BINS words of the dataset's counter.  `hist` is written
 // only when everything has succeeded.
 Status ResidentDataset::count_bounds_by_class(const AABB &bounds, uint64_t *hist, uint64_t *points_scanned) {
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS;
-    std::vector<pcq_columns> cols;
-    std::vector<pcq_predicate> preds;
-    uint64_t scanned = 0;
-    for (const auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // last.rs:92-94
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
-        if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        pcq_columns c{};
-        c.xyz = f.xyz, c.xyz_stride = 12, c.n = f.header.number_of_points;
-        c.cls = f.cls, c.cls_stride = 1;
-        for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];
-        cols.push_back(c);
-        preds.push_back(pred);
-        scanned += c.n;
-    }
-    if (counter_words_ < PCQ_CLASS_BINS) {
-        void *p = nullptr;
-        int rc = pcq_device_alloc(ctx_, PCQ_CLASS_BINS * 8, &p);
-        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed may have left launches that add into the old counter)
-        if (rc) {
-            if (p) pcq_device_free(ctx_, p);
-            return Status::FromLib(rc);
-        }
-        pcq_device_free(ctx_, counter_);
-        counter_ = (uint64_t *)p;
-        counter_words_ = PCQ_CLASS_BINS;
-    }
-    uint64_t bins[PCQ_CLASS_BINS];
-    int rc = pcq_device_memset(ctx_, counter_, 0, PCQ_CLASS_BINS * 8, nullptr);
-    if (!rc && !cols.empty()) rc = pcq_scan_dev_class_hist_batch(ctx_, cols.data(), preds.data(), cols.size(), counter_, nullptr);
-    if (!rc) rc = pcq_copy_to_host(ctx_, bins, counter_, PCQ_CLASS_BINS * 8);  // waits for the context's stream
-    if (rc) return Status::FromLib(rc);
-    memcpy(hist, bins, sizeof bins);
-    if (points_scanned) *points_scanned = scanned;
-    return Status::Ok();
+    Segments seg;
+    Status st = box_segments(bounds, predicate(PCQ_PRED_BOUNDS), PCQ_PRED_BOUNDS_CLASS, &seg);
+    if (st.ok()) st = run(pcq_scan_dev_class_hist_batch, PCQ_CLASS_BINS, seg, hist);
+    if (st.ok() && points_scanned) *points_scanned = seg.scanned;
+    return st;
 }
 
 // `--class` over the dataset, count only (last.rs:253-262: whole byte, no file-level early-out).
 Status ResidentDataset::count_class(uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
-    std::vector<pcq_columns> cols;
-    std::vector<pcq_predicate> preds;
-    uint64_t scanned = 0;
+    const pcq_predicate pred = predicate(PCQ_PRED_CLASS, cls);
+    Segments seg;
     for (const auto &f : files_) {
         if (f.header.number_of_points == 0) continue;
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_CLASS;
-        pred.cls = cls;
         pcq_columns c{};
         c.cls = f.cls, c.cls_stride = 1, c.n = f.header.number_of_points;
-        cols.push_back(c);
-        preds.push_back(pred);
-        scanned += c.n;
+        seg.cols.push_back(c);
+        seg.preds.push_back(pred);
+        seg.scanned += c.n;
     }
-    if (points_scanned) *points_scanned = scanned;
-    return run(PCQ_PRED_CLASS, cols, preds, matches);
+    if (points_scanned) *points_scanned = seg.scanned;
+    return run(pcq_scan_dev_count_batch, 1, seg, matches);
 }
 
 // `--combine --bounds --class` over the dataset, count only (pcq_scan_dev_count_batch_combined over the positions and
 // classification blocks).
 Status ResidentDataset::count_bounds_class(const AABB &bounds, uint8_t cls, uint64_t *matches, uint64_t *points_scanned) {
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS_CLASS;
-    pred.cls = cls;
-    return count_box(bounds, pred, matches, points_scanned);
+    return count_box(bounds, predicate(PCQ_PRED_BOUNDS_CLASS, cls), matches, points_scanned);
 }
 
 // `--combine --bounds --time` over the dataset, count only (pcq_scan_dev_count_batch_bounds_time over the positions and time
 // blocks).
 Status ResidentDataset::count_bounds_time(const AABB &bounds, double start, double end, uint64_t *matches, uint64_t *points_scanned) {
-    if (!with_times_)
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS_TIME;
-    pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
-    pred.wmax[0] = end;
-    return count_box(bounds, pred, matches, points_scanned);
+    if (!with_times_) return Status::Err(PCQ_ERR_ARG, NO_TIMES);
+    return count_box(bounds, predicate(PCQ_PRED_BOUNDS_TIME, 0, start, end), matches, points_scanned);
 }
 
 // One file of the search_* : execute_plan (search.cpp) with the resident blocks in place of the file.
 Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc) {
     const uint64_t n = f.header.number_of_points;
     const bool time = pred.kind == PCQ_PRED_TIME || pred.kind == PCQ_PRED_BOUNDS_TIME;
-    pcq_columns c{};
-    c.xyz = f.xyz, c.xyz_stride = 12;  // last.rs:114-121
-    c.cls = f.cls, c.cls_stride = 1;   // :138-142
-    c.rgb = f.rgb, c.rgb_stride = 6;   // :145-153
-    if (time) c.cls = f.time, c.cls_stride = 8, c.rgb = nullptr;  // the predicate's column; a time record has no class and no colour
-    c.n = n;
+    pcq_columns c = file_columns(f, time ? PCQ_PRED_TIME : PCQ_PRED_CLASS);  // the predicate's column, or the class of the records
+    c.rgb = time ? nullptr : f.rgb, c.rgb_stride = 6;  // last.rs:145-153; a time record has no class and no colour
     c.first_index = rc.next_index;
-    for (int a = 0; a < 3; a++) c.scale[a] = f.header.scale[a], c.offset[a] = f.header.offset[a];  // :156-160
     int r;
     if (dynamic_cast<GridSampledCollector *>(&rc)) {
         r = pcq_scan_dev(ctx_, &c, &pred, rc.handle(), nullptr);
@@ -333,99 +337,54 @@ Status ResidentDataset::scan(ResidentFile &f, const pcq_predicate &pred, ResultC
     return Status::FromLib(r);
 }
 
-// search_last_file_by_bounds_optimized (last.rs:46-166) for every file: the header early-out (:92-94) skips a file without
-// moving the collector's file-order index, as the per-file search does.
-Status ResidentDataset::search_bounds(const AABB &bounds, ResultCollector &rc) {
-    if (!with_points_ && rc.has_points())
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
+// Every file in load order through scan().  With `bounds`: the prologue of the box searches first, whose header early-out
+// (last.rs:92-94) skips a file without moving the collector's file-order index, as the per-file search does.  Without: no
+// file-level early-out (a header has no class and no time bounds).
+Status ResidentDataset::search_files(const AABB *bounds, pcq_predicate pred, ResultCollector &rc) {
     last_indices_.clear();
     for (auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS;
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
+        bool go = f.header.number_of_points != 0;
+        const int brc = bounds ? box_prologue(f, *bounds, &pred, &go) : (int)PCQ_OK;
         if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
+        if (!go) continue;
         Status st = scan(f, pred, rc);
         if (!st.ok()) return st;
     }
     return Status::Ok();
 }
 
-// search_last_file_by_classification_optimized (last.rs:213-293) for every file: no file-level early-out.
+// search_last_file_by_bounds_optimized (last.rs:46-166) for every file.
+Status ResidentDataset::search_bounds(const AABB &bounds, ResultCollector &rc) {
+    if (!with_points_ && rc.has_points()) return Status::Err(PCQ_ERR_ARG, NO_COLOURS);
+    return search_files(&bounds, predicate(PCQ_PRED_BOUNDS), rc);
+}
+
+// search_last_file_by_classification_optimized (last.rs:213-293) for every file.
 Status ResidentDataset::search_class(uint8_t cls, ResultCollector &rc) {
-    if (!with_points_ && rc.has_points())
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
-    last_indices_.clear();
-    for (auto &f : files_) {
-        if (f.header.number_of_points == 0) continue;
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_CLASS;
-        pred.cls = cls;  // :259-262 whole byte
-        Status st = scan(f, pred, rc);
-        if (!st.ok()) return st;
-    }
-    return Status::Ok();
+    if (!with_points_ && rc.has_points()) return Status::Err(PCQ_ERR_ARG, NO_COLOURS);
+    return search_files(nullptr, predicate(PCQ_PRED_CLASS, cls), rc);
 }
 
 // The combined search of search.cpp (DESIGN §8 "Combined searches") for every file: the prologue of search_bounds, then box
 // AND class in one scan — through both parts of the file's chunk index for count and buffer collectors.
 Status ResidentDataset::search_bounds_class(const AABB &bounds, uint8_t cls, ResultCollector &rc) {
-    if (!with_points_ && rc.has_points())
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its colour blocks: count collectors only (pcq_query_resident_load_points)");
-    last_indices_.clear();
-    for (auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS_CLASS;
-        pred.cls = cls;
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
-        if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        Status st = scan(f, pred, rc);
-        if (!st.ok()) return st;
-    }
-    return Status::Ok();
+    if (!with_points_ && rc.has_points()) return Status::Err(PCQ_ERR_ARG, NO_COLOURS);
+    return search_files(&bounds, predicate(PCQ_PRED_BOUNDS_CLASS, cls), rc);
 }
 
-// search_last_file_by_time_range_optimized (search.cpp) for every file: no file-level early-out (a header has no time bounds).
-// Any collector: a time record's colour is (0,0,0), so no colour block is needed.
+// search_last_file_by_time_range_optimized (search.cpp) for every file.  Any collector: a time record's colour is (0,0,0), so
+// no colour block is needed.
 Status ResidentDataset::search_time(double start, double end, ResultCollector &rc) {
-    if (!with_times_)
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
-    last_indices_.clear();
-    for (auto &f : files_) {
-        if (f.header.number_of_points == 0) continue;
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_TIME;
-        pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (las.rs:336)
-        pred.wmax[0] = end;
-        Status st = scan(f, pred, rc);
-        if (!st.ok()) return st;
-    }
-    return Status::Ok();
+    if (!with_times_) return Status::Err(PCQ_ERR_ARG, NO_TIMES);
+    return search_files(nullptr, predicate(PCQ_PRED_TIME, 0, start, end), rc);
 }
 
-// The combined time search of search.cpp for every file: the prologue of search_bounds (the header early-out leaves the
-// collector's file-order index where it was), then box AND time in one scan — through the bounds and time parts of the file's
-// chunk index for count and buffer collectors.  Any collector: the records carry class 0 and colour (0,0,0).
+// The combined time search of search.cpp for every file: the prologue of search_bounds, then box AND time in one scan — through
+// the bounds and time parts of the file's chunk index for count and buffer collectors.  Any collector: the records carry class 0
+// and colour (0,0,0).
 Status ResidentDataset::search_bounds_time(const AABB &bounds, double start, double end, ResultCollector &rc) {
-    if (!with_times_)
-        return Status::Err(PCQ_ERR_ARG, "resident dataset loaded without its GPS time blocks (pcq_query_resident_load_with, PCQ_RESIDENT_TIME)");
-    last_indices_.clear();
-    for (auto &f : files_) {
-        if (!f.header.bounds.intersects(bounds)) continue;  // :92-94
-        pcq_predicate pred{};
-        pred.kind = PCQ_PRED_BOUNDS_TIME;
-        pred.wmin[0] = start;
-        pred.wmax[0] = end;
-        const int brc = pcq_box_to_local(bounds.min, bounds.max, f.header.scale, f.header.offset, pred.lmin, pred.lmax);  // :98-109
-        if (brc) return Status::FromLib(brc);
-        if (f.header.number_of_points == 0) continue;
-        Status st = scan(f, pred, rc);
-        if (!st.ok()) return st;
-    }
-    return Status::Ok();
+    if (!with_times_) return Status::Err(PCQ_ERR_ARG, NO_TIMES);
+    return search_files(&bounds, predicate(PCQ_PRED_BOUNDS_TIME, 0, start, end), rc);
 }
 
 Status ResidentDataset::last_stats(pcq_index_stats *out) {

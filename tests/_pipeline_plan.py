@@ -18,13 +18,13 @@ m(s) matches of query value s mod 3, m pairwise distinct over the steps of any o
 mis-addressed step moves a count by an amount no other single error cancels.  Expected values always come from numpy
 compares on the finished arrays (class_count, time_count, box_count below), never from m(s).
 
-Restated from (adhoc-queries-pointclouds_amd/csrc):
-  K1 family  scan_tiles.h:13-15 (256-point tiles, 2 per step, 3 waves per CU); scan_count.hip:50 (steps), :263-265 (grid);
+Restated from (adhoc-queries-pointclouds_amd/csrc; the loop itself is written out in every kernel, e.g. scan_count.hip:64-78):
+  K1 family  scan_tiles.h:15-17 (256-point tiles, 2 per step, 3 waves per CU); scan_count.hip:55 (steps), :250-252 (grid);
              collectors.hip:267 (the points peeled in front of the first 16-byte aligned one)
-  K2         scan_tiles.h:16-17 (4 loads of 1 KiB per step, 4 waves per CU); scan_count.hip:291-297 (head, nvec, grid), :214
-  K3         scan_time.hip:17-18 (4 loads per step, 4 waves per CU), :110-114 (head, nvec, grid), :63
-  batches    scan_count.hip:333-339 (class segments), :351-354 (bounds segments), :360-361 (grid), :144 (K2's seek);
-             scan_count_batch.hip:68-72 (segments with a second column), :78-79 (grid); scan_tiles.h:370 (K1's seek)
+  K2         scan_tiles.h:18-19 (4 loads of 1 KiB per step, 4 waves per CU); scan_count.hip:276-282 (head, nvec, grid), :201
+  K3         scan_time.hip:18-19 (4 loads per step, 4 waves per CU), :90-94 (head, nvec, grid), :43
+  batches    scan_count.hip:305-311 (class segments), :316-317 (their grid), :129 (K2's seek); scan_batch_host.h:47-48 (bounds
+             segments, with or without a second column: k1_batch_launch), :54-55 (grid); scan_tiles.h:421 (K1's seek)
 """
 from collections import Counter, namedtuple
 

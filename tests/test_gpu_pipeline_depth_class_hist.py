@@ -2,7 +2,7 @@
 numpy's full 256-bin histogram.
 
 The plan, the schedule report and the step-coded data are those of tests/_pipeline_plan.py.  The kernel has K1's step of 512
-points but its own number of workgroups per CU (scan_class_hist.hip:42, CLASS_HIST_WAVES_PER_CU = 4; the grid is capped at steps +
+points but its own number of workgroups per CU (scan_class_hist.hip:37, CLASS_HIST_WAVES_PER_CU = 4; the grid is capped at steps +
 segments as K1's), so the Family is declared here.  The deep run is the batch of seventeen segments sized from the device's
 compute units: at least 5g + g // 3 steps (depth 5 at least, both exits out of the steady state), in which workgroups change
 segment when either cursor seeks and jump over segments with steps, without a whole step and without points.  The shallow run
@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
-FAM = pp.Family("K1 class hist", 4, pp.K1.step)  # adhoc-queries-pointclouds_amd/csrc/scan_class_hist.hip:42
+FAM = pp.Family("K1 class hist", 4, pp.K1.step)  # adhoc-queries-pointclouds_amd/csrc/scan_class_hist.hip:37
 EMPTY = ([5, 5, 5], [4, 4, 4])
 BINS = 256
 PRESET = np.asarray([3 + 11 * c for c in range(BINS)], dtype=np.uint64)

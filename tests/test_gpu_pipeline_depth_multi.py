@@ -2,7 +2,7 @@
 against numpy.
 
 The plan, the schedule report and the step-coded data are those of tests/_pipeline_plan.py.  The kernel has K1's step of 512
-points but launches 12 workgroups per CU where K1 launches 3 (scan_count_multi.hip:29, MULTI_WAVES_PER_CU; the grid is capped at
+points but launches 12 workgroups per CU where K1 launches 3 (scan_count_multi.hip:24, MULTI_WAVES_PER_CU; the grid is capped at
 steps + segments as K1's), so the Family is declared here.  The deep run
 is the batch of seventeen segments sized from the device's compute units: at least 5g + g // 3 steps (depth 5 at least, both
 exits out of the steady state), in which workgroups change segment when either cursor seeks.  The shallow run has 4g - 1 steps
@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
-FAM = pp.Family("K1 multi", 12, pp.K1.step)  # adhoc-queries-pointclouds_amd/csrc/scan_count_multi.hip:29
+FAM = pp.Family("K1 multi", 12, pp.K1.step)  # adhoc-queries-pointclouds_amd/csrc/scan_count_multi.hip:24
 EMPTY = ([5, 5, 5], [4, 4, 4])
 FULL = ([-2**40] * 3, [2**40] * 3)
 PRESET = [3 + 11 * q for q in range(8)]
