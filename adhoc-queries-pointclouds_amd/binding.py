@@ -210,6 +210,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_count_batch_bounds_time": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_count_batch_multi": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_scan_dev_class_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
+        "pcq_scan_dev_time_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, P(C.c_double), C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -462,6 +463,22 @@ class Context:
         ca = (Columns * n)(*cols)
         pa = (Predicate * n)(*preds)
         _check(self.lib.pcq_scan_dev_class_hist_batch(self.handle, ca, pa, n, C.c_void_p(device_hist), C.c_void_p(stream)))
+
+    def scan_dev_time_hist_batch(self, cols: Sequence[Columns], preds: Sequence[Predicate], edges, device_hist: int,
+                                 stream: Optional[int] = None) -> None:
+        """The time histogram of a box (Predicate kind PCQ_PRED_BOUNDS; segments laid out as for
+        scan_dev_count_batch_bounds_time) over many resident LAST files in ONE pass.  edges: nbins + 1 non-decreasing f64 values
+        in host memory (a C-contiguous float64 numpy array is read in place, anything else is copied); for every point inside its
+        segment's box whose time lies in [edges[b], edges[b + 1]), += 1 into word b of the nbins words of device_hist."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        if isinstance(edges, np.ndarray) and edges.dtype == np.float64 and edges.flags["C_CONTIGUOUS"]:
+            ea = edges.ctypes.data_as(C.POINTER(C.c_double))
+        else:
+            ea = (C.c_double * len(edges))(*edges)
+        _check(self.lib.pcq_scan_dev_time_hist_batch(self.handle, ca, pa, n, ea, max(len(edges), 1) - 1, C.c_void_p(device_hist),
+                                                     C.c_void_p(stream)))
 
     def scan_dev_count_batch_bounds_time(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_total: int,
                                          stream: Optional[int] = None) -> None:

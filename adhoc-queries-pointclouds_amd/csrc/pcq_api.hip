@@ -224,8 +224,8 @@ int pcq_ensure_partials(pcq_ctx *ctx, size_t n) {
 }
 
 // The segment tables of the batched count kernels (DevSegment: box, DevClassSegment: class at DevSegment pitch,
-// DevCombinedSegment: box AND class, DevBoundsTimeSegment: box AND time) share one pinned buffer and its device twin, sized
-// in bytes.
+// DevCombinedSegment: box AND class, DevBoundsTimeSegment: box AND time, or the time histogram's with its edges behind the
+// table) share one pinned buffer and its device twin, sized in bytes.
 int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->segments_cap) return PCQ_OK;
     if (ctx->d_segments) (void)hipFree(ctx->d_segments);
@@ -343,6 +343,7 @@ static const Option k_options[] = {
     {"class_batch_waves_per_cu", &pcq_ctx::class_batch_waves_per_cu, 1, 32, OPT_SET},
     {"multi_waves_per_cu", &pcq_ctx::multi_waves_per_cu, 0, 32, OPT_SET},
     {"class_hist_waves_per_cu", &pcq_ctx::class_hist_waves_per_cu, 0, 32, OPT_SET},
+    {"time_hist_waves_per_cu", &pcq_ctx::time_hist_waves_per_cu, 0, 32, OPT_SET},
     {"class_hist_copies", &pcq_ctx::class_hist_copies, 0, 16, OPT_SET},  // (only 0, 1, 2, 4, 8 and 16: scan_class_hist.hip)
 #endif
 };

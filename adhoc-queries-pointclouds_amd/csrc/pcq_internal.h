@@ -144,6 +144,9 @@ constexpr int PCQ_SEGMENTS_MULTI = 0x4d42;  // ("MB") no pcq_predicate_kind: the
 // The class histogram of a box (scan_class_hist.hip) reads tables of DevCombinedSegment (`pat` unused) under a kind of its own:
 // the same bytes under PCQ_PRED_BOUNDS_CLASS are another batch entry's table.
 constexpr int PCQ_SEGMENTS_CLASS_HIST = 0x4348;  // ("CH") no pcq_predicate_kind
+// The time histogram of a box (scan_time_hist.hip) reads tables of DevBoundsTimeSegment (t0, t1 unused) with the launch's bin
+// count and edges behind them, under a kind of its own: the same segments under PCQ_PRED_BOUNDS_TIME are another entry's table.
+constexpr int PCQ_SEGMENTS_TIME_HIST = 0x5448;  // ("TH") no pcq_predicate_kind
 
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
@@ -325,6 +328,7 @@ struct pcq_ctx {
     int class_batch_pipe = 1;
     int multi_waves_per_cu = 0;   // multi-box K1 (scan_count_multi.hip): workgroups per CU (0 = the product's: MULTI_WAVES_PER_CU)
     int class_hist_waves_per_cu = 0;  // class histogram (scan_class_hist.hip): workgroups per CU (0 = the product's: CLASS_HIST_WAVES_PER_CU)
+    int time_hist_waves_per_cu = 0;  // time histogram (scan_time_hist.hip): workgroups per CU (0 = the product's: TIME_HIST_WAVES_PER_CU)
     int class_hist_copies = 0;    // ... and copies of the LDS histogram per wave, 1 / 2 / 4 / 8 / 16 (0 = the product's: CLASS_HIST_COPIES)
 #endif
     int numa_node = -1;               // NUMA node the GPU hangs off (sysfs), -1 if unknown

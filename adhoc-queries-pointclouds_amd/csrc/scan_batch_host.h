@@ -1,5 +1,5 @@
 // scan_batch_host.h — the host side of the K1-family batched launches (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip,
-// scan_class_hist.hip): host code only; the kernels and their constants are in scan_tiles.h.
+// scan_class_hist.hip, scan_time_hist.hip): host code only; the kernels and their constants are in scan_tiles.h.
 #pragma once
 
 #include <vector>
@@ -14,6 +14,7 @@ namespace {
 // the finish.  The table first: nothing is touched when a segment is refused.  Per segment, in this order: admit(i) (the
 // entry's refusals that come before those of the positions), the positions' refusals, fill(seg, i) (the entry's columns and
 // predicates, or their refusal); xyz, n and tile_begin are filled here.  launch(workgroups, steps) enqueues the kernel, or refuses.
+// A trailer (the time histogram's edges) travels behind the table in the same upload, under the same compare of all bytes.
 struct K1Batch {
     const char *prefix;  // of a refusal's text
     int table_kind;      // the key of the table in HBM (pcq_upload_segment_table)
@@ -21,6 +22,8 @@ struct K1Batch {
     int slices;          // words of the partials per workgroup
     int folded;          // the first `folded` slices are added into d_out[0 .. folded)
     bool null_refused;   // positions that are null with n > 0 are refused (the plain box kind never has)
+    const void *trailer = nullptr;  // launch-level data behind the table in HBM (8-byte aligned there: every Seg is)
+    size_t trailer_bytes = 0;
 };
 template <typename Seg, typename DP>
 void seg_box(Seg &g, const DP &dp) {
@@ -49,7 +52,14 @@ int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, siz
     }
     int rc = pcq_scratch_stream(ctx, s);
     if (rc) return rc;
-    rc = pcq_upload_segment_table(ctx, b.table_kind, nsegments, table.data(), nsegments * sizeof(Seg), s);
+    if (b.trailer_bytes) {
+        std::vector<uint8_t> both(nsegments * sizeof(Seg) + b.trailer_bytes);
+        memcpy(both.data(), table.data(), nsegments * sizeof(Seg));
+        memcpy(both.data() + nsegments * sizeof(Seg), b.trailer, b.trailer_bytes);
+        rc = pcq_upload_segment_table(ctx, b.table_kind, nsegments, both.data(), both.size(), s);
+    } else {
+        rc = pcq_upload_segment_table(ctx, b.table_kind, nsegments, table.data(), nsegments * sizeof(Seg), s);
+    }
     if (rc) return rc;
     uint64_t g = (uint64_t)ctx->num_cus * (uint64_t)b.waves_per_cu;
     if (g > steps + nsegments) g = steps + nsegments;

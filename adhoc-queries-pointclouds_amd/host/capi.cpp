@@ -379,6 +379,17 @@ extern "C" int pcq_query_resident_count_bounds_time(pcq_host_resident *r, const 
     if (!st.ok()) return done(st);
     return done(r->ds->count_bounds_time(b, start, end, matches, points_scanned));
 }
+extern "C" int pcq_query_resident_count_bounds_by_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], const double *edges,
+                                                       size_t nbins, uint64_t *hist, uint64_t *points_scanned) {
+    if (!r || !bmin || !bmax || !edges || !hist) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nbins == 0) return PCQ_OK;
+    for (size_t i = 0; i <= nbins; i++) {  // (neither r nor a device is touched before the edges are known to be good)
+        if (edges[i] != edges[i]) return done(Status::Err(PCQ_ERR_ARG, "time histogram: edge " + std::to_string(i) + " is NaN"));
+        if (i && edges[i - 1] > edges[i])
+            return done(Status::Err(PCQ_ERR_ARG, "time histogram: edge " + std::to_string(i) + " is below edge " + std::to_string(i - 1)));
+    }
+    return done(r->ds->count_bounds_by_time(bmin, bmax, edges, nbins, hist, points_scanned));  // no times: PCQ_ERR_ARG; then min > max: PCQ_ERR_PANIC
+}
 extern "C" int pcq_query_resident_search_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
                                                      pcq_host_collector *c) {
     if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

@@ -399,6 +399,11 @@ public:
                              uint64_t *points_read = nullptr);
     // the class histogram of a box: hist[c] (PCQ_CLASS_BINS words) is what count_bounds_class gives for class c, from ONE pass
     Status count_bounds_by_class(const AABB &bounds, uint64_t *hist, uint64_t *points_scanned = nullptr);
+    // the time histogram of a box: hist[b] (nbins words) is what count_bounds_time gives for [edges[b], edges[b + 1]), from ONE pass
+    // per group of PCQ_TIME_BINS_MAX bins.  edges: nbins + 1 values the caller has checked (non-decreasing, none NaN).  The errors
+    // in this order: a dataset without times, then the box's own (min > max).  (with_times)
+    Status count_bounds_by_time(const double bmin[3], const double bmax[3], const double *edges, size_t nbins, uint64_t *hist,
+                                uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
@@ -427,7 +432,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time)
     uint64_t points_ = 0;
 };
 

@@ -24,6 +24,9 @@
 //
 // The class histogram of a box (count_bounds_by_class): the per-class breakdown of count_bounds_class for all 256 classes from
 // one pcq_scan_dev_class_hist_batch, instead of one combined count per class.
+//
+// The time histogram of a box (count_bounds_by_time): the per-slice breakdown of count_bounds_time for the bins between the
+// caller's edges, one pcq_scan_dev_time_hist_batch per group of PCQ_TIME_BINS_MAX bins, instead of one box AND time count per bin.
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -153,7 +156,7 @@ int ResidentDataset::ensure_counter(size_t words) {
 template <typename Launch>
 Status ResidentDataset::read_counts(size_t words, Launch launch, uint64_t *out) {
     uint64_t few[PCQ_CLASS_BINS];
-    std::vector<uint64_t> many(words > PCQ_CLASS_BINS ? words : 0);  // (more boxes than classes: count_bounds_many)
+    std::vector<uint64_t> many(words > PCQ_CLASS_BINS ? words : 0);  // (more boxes than classes: count_bounds_many; time bins)
     uint64_t *got = many.empty() ? few : many.data();
     int rc = ensure_counter(words);
     if (!rc) rc = pcq_device_memset(ctx_, counter_, 0, words * 8, nullptr);
@@ -279,6 +282,32 @@ Status ResidentDataset::count_bounds_by_class(const AABB &bounds, uint64_t *hist
     Segments seg;
     Status st = box_segments(bounds, predicate(PCQ_PRED_BOUNDS), PCQ_PRED_BOUNDS_CLASS, &seg);
     if (st.ok()) st = run(pcq_scan_dev_class_hist_batch, PCQ_CLASS_BINS, seg, hist);
+    if (st.ok() && points_scanned) *points_scanned = seg.scanned;
+    return st;
+}
+
+// When was this box scanned: the prologue of count_box with a plain box predicate, then the bins in their order in groups of
+// PCQ_TIME_BINS_MAX, ONE pcq_scan_dev_time_hist_batch per group over the positions and time blocks of the surviving files: edges
+// q0 .. q0 + nq, counter words from q0.  All launches go to the context's stream; the host waits for the copy of the counts at the
+// end (and once per group for the upload of its edges: pcq_upload_segment_table).  The caller has checked the edges.  `hist` and
+// `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::count_bounds_by_time(const double bmin[3], const double bmax[3], const double *edges, size_t nbins, uint64_t *hist,
+                                             uint64_t *points_scanned) {
+    if (!with_times_) return Status::Err(PCQ_ERR_ARG, NO_TIMES);
+    AABB bounds;
+    Status st = AABB::from_min_max(bmin, bmax, &bounds);
+    if (!st.ok()) return st;
+    Segments seg;
+    st = box_segments(bounds, predicate(PCQ_PRED_BOUNDS), PCQ_PRED_BOUNDS_TIME, &seg);
+    if (!st.ok()) return st;
+    st = read_counts(nbins, [&] {
+        int rc = PCQ_OK;
+        for (size_t q0 = 0; q0 < nbins && !rc && !seg.cols.empty(); q0 += PCQ_TIME_BINS_MAX) {
+            const size_t nq = nbins - q0 < PCQ_TIME_BINS_MAX ? nbins - q0 : (size_t)PCQ_TIME_BINS_MAX;
+            rc = pcq_scan_dev_time_hist_batch(ctx_, seg.cols.data(), seg.preds.data(), seg.cols.size(), edges + q0, nq, counter_ + q0, nullptr);
+        }
+        return rc;
+    }, hist);
     if (st.ok() && points_scanned) *points_scanned = seg.scanned;
     return st;
 }

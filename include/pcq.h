@@ -277,6 +277,23 @@ int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *cols, const 
 #define PCQ_CLASS_BINS 256
 int pcq_scan_dev_class_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
                                   uint64_t *device_hist, void *stream);
+/* The time histogram of a box in ONE pass: "when was this box scanned?".  Every predicate is PCQ_PRED_BOUNDS, and segment i has
+ * the layout of pcq_scan_dev_count_batch_bounds_time — packed positions (xyz_stride 12, 16-byte aligned) beside the packed f64
+ * GPS times of the same points in cols[i].cls (cls_stride 8, 8-byte aligned), both non-null when n > 0.  `edges` is a HOST
+ * pointer to nbins + 1 doubles e[0] <= e[1] <= ... <= e[nbins]: non-decreasing, none NaN; infinities, -0.0 and equal neighbours
+ * are allowed.  Bin b is the half-open range [e[b], e[b+1]) under IEEE compares, the range test of PCQ_PRED_BOUNDS_TIME.  A
+ * point of segment i inside the box of preds[i] with time t adds 1 to bin b = #{i : e[i] <= t} - 1 when 0 <= b < nbins and to
+ * nothing otherwise, so that device_hist[b] grows by what pcq_scan_dev_count_batch_bounds_time counts for [e[b], e[b+1]) on the
+ * same segments and boxes, for every b at once and from one read of the data: a NaN time lands in no bin, a time equal to an
+ * edge belongs to the bin that starts there, a bin with equal edges stays empty, -0.0 and 0.0 are one value, and +inf is in no
+ * bin.  Only compares decide a bin, no arithmetic.  The counts are ADDED to device_hist[0 .. nbins); no word beyond is touched.
+ * A predicate that is empty matches nothing and its segment is not evaluated.  nsegments == 0 is PCQ_OK after the argument
+ * checks.  A null argument, nbins == 0 or above PCQ_TIME_BINS_MAX, a NaN edge, e[i] > e[i+1], any other predicate kind
+ * (PCQ_PRED_BOUNDS_TIME included) and any other layout are refused (PCQ_ERR_ARG) before anything is uploaded or launched:
+ * device_hist is untouched. */
+#define PCQ_TIME_BINS_MAX 1024
+int pcq_scan_dev_time_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
+                                 const double *edges, size_t nbins, uint64_t *device_hist, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

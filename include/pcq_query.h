@@ -157,6 +157,17 @@ int pcq_query_resident_search_time(pcq_host_resident *r, double start, double en
  * box.  Needs a dataset loaded with PCQ_RESIDENT_TIME (else PCQ_ERR_ARG). */
 int pcq_query_resident_count_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
                                          uint64_t *matches, uint64_t *points_scanned);
+/* When was this box scanned (`--combine --bounds ... --time e[b] e[b+1]`, count only, for every b at once): edges is nbins + 1
+ * f64 values e[0] <= e[1] <= ... <= e[nbins], none NaN (infinities, -0.0 and equal neighbours are allowed); hist[b] is what
+ * pcq_query_resident_count_bounds_time(r, bmin, bmax, edges[b], edges[b+1], ...) returns as matches, for every b in 0 .. nbins-1,
+ * and points_scanned (NULL: not wanted) is what that entry reports.  The per-file prologue of that entry + one launch over the
+ * positions and time blocks of the surviving files per group of PCQ_TIME_BINS_MAX bins (pcq.h, pcq_scan_dev_time_hist_batch):
+ * the data is read once per group, not once per bin.  The checks in their order: a null r, bmin, bmax, edges or hist is
+ * PCQ_ERR_ARG; nbins == 0 is PCQ_OK with nothing written; a NaN or decreasing edge is PCQ_ERR_ARG — these three touch neither
+ * r nor a device; a dataset loaded without PCQ_RESIDENT_TIME is PCQ_ERR_ARG; last the box's own error (PCQ_ERR_PANIC for
+ * min > max).  On any failure hist and points_scanned are left as they were. */
+int pcq_query_resident_count_bounds_by_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], const double *edges,
+                                            size_t nbins, uint64_t *hist, uint64_t *points_scanned);
 /* == pcq_query_search_file_bounds_time(path, bmin, bmax, start, end, optimized=1, c) for every loaded file, in load order, into
  * ONE collector: the same count, the same records byte for byte and in order (class 0, colour (0,0,0), whether or not colour
  * blocks are loaded), the same grid cells and winners; the header early-out leaves the collector's file-order index where it

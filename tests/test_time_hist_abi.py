@@ -1,0 +1,110 @@
+"""The time histogram of a box: the libpcq entry (include/pcq.h: pcq_scan_dev_time_hist_batch) and the host entry
+(include/pcq_query.h: pcq_query_resident_count_bounds_by_time) are declared and exported beside the old batch and resident entries,
+PCQ_TIME_BINS_MAX is defined, the binding has the method, the ABI number is what it was, and the host entry's first three checks —
+null arguments, nbins == 0, bad edges — run before any dataset or device is touched: from python, and from a stand-alone driver
+built with ASan and UBSan (tests/native/time_hist_asan_driver.cpp).  No GPU call."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+PCQ_OK, PCQ_ERR_ARG = 0, -8
+LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
+           "pcq_scan_dev_count_batch_multi", "pcq_scan_dev_class_hist_batch"]
+QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
+             "pcq_query_resident_count_bounds_many", "pcq_query_resident_count_bounds_by_class"]
+
+
+def bins_max():
+    with open(os.path.join(ROOT, "include", "pcq.h")) as f:
+        m = re.search(r"^#define PCQ_TIME_BINS_MAX (\d+)$", f.read(), re.M)
+    assert m, "#define PCQ_TIME_BINS_MAX is not in pcq.h"
+    return int(m.group(1))
+
+
+def test_both_entries_are_declared_and_exported_beside_the_old_ones():
+    declared = pkg.declared_symbols(["pcq.h"])
+    exported = pkg.exported_symbols(pkg.lib_path())
+    for name in ["pcq_scan_dev_time_hist_batch"] + LIB_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    declared = pkg.declared_symbols(["pcq_query.h"])
+    exported = pkg.exported_symbols(os.path.join(PKG, "libpcq_query.so"))
+    for name in ["pcq_query_resident_count_bounds_by_time"] + QUERY_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    assert bins_max() in (512, 1024)
+
+
+def test_abi_number_is_unchanged_and_the_binding_has_the_method():
+    assert pkg.load_library().pcq_abi_version() == 6
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    assert callable(binding.Context.scan_dev_time_hist_batch)
+    assert callable(binding.Context.scan_dev_count_batch_bounds_time)
+
+
+def test_host_entry_checks_arguments_and_edges_without_a_device():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    lib.pcq_query_resident_count_bounds_by_time.argtypes = [C.c_void_p, dd, dd, dd, C.c_size_t, u64p, u64p]
+    entry = lib.pcq_query_resident_count_bounds_by_time
+    dummy = C.c_void_p(1)  # never dereferenced: the call ends before it
+    lo, hi = (C.c_double * 3)(0, 0, 0), (C.c_double * 3)(1, 1, 1)
+    words = bins_max() + 8
+    sentinel = [1000 + 7 * c for c in range(words)]
+    hist = (C.c_uint64 * words)(*sentinel)
+    s = C.c_uint64(15)
+    good = (C.c_double * 4)(1.0, 2.0, 3.0, 4.0)
+
+    def untouched():
+        return list(hist) == sentinel and s.value == 15
+
+    # 1. a null argument, also with nbins == 0
+    for nbins in (3, 0):
+        for args in ((None, lo, hi, good, nbins, hist, C.byref(s)), (dummy, None, hi, good, nbins, hist, C.byref(s)),
+                     (dummy, lo, None, good, nbins, hist, C.byref(s)), (dummy, lo, hi, None, nbins, hist, C.byref(s)),
+                     (dummy, lo, hi, good, nbins, None, C.byref(s)), (None, lo, hi, good, nbins, hist, None)):
+            assert entry(*args) == PCQ_ERR_ARG
+            assert b"null argument" in lib.pcq_query_last_error()
+            assert untouched()
+    # 2. nbins == 0: PCQ_OK with nothing written, whatever the edge
+    for e0 in (1.0, float("nan")):
+        assert entry(dummy, lo, hi, (C.c_double * 1)(e0), 0, hist, C.byref(s)) == PCQ_OK
+        assert untouched()
+    # 3. a NaN edge and e[1] > e[2], each refused
+    nan, inf = float("nan"), float("inf")
+    for bad in ([1.0, nan, 3.0, 4.0], [nan, 2.0, 3.0, 4.0], [1.0, 2.0, 3.0, nan], [1.0, 3.0, 2.0, 4.0], [2.0, 1.0, 3.0, 4.0],
+                [1.0, 2.0, 4.0, 3.0], [-inf, inf, 0.0, inf]):
+        assert entry(dummy, lo, hi, (C.c_double * 4)(*bad), 3, hist, C.byref(s)) == PCQ_ERR_ARG, bad
+        assert b"edge" in lib.pcq_query_last_error()
+        assert untouched()
+    # a decrease behind the first group of bins is found before anything runs too
+    many = [float(i) for i in range(bins_max() + 4)]
+    many[-1] = 5.0
+    assert entry(dummy, lo, hi, (C.c_double * len(many))(*many), len(many) - 1, hist, None) == PCQ_ERR_ARG
+    assert untouched()
+
+
+def test_host_entry_under_address_sanitizer(tmp_path):
+    """The same paths under ASan + UBSan, through a stand-alone program (nothing sanitized is loaded into python; no device is
+    touched).  The two translation units the entry lives in — capi.cpp and resident.cpp — are built sanitized into the program,
+    where their definitions come first; the rest of the host layer is the libpcq_query.so beside them, which keeps the build to
+    a few seconds."""
+    host = os.path.join(PKG, "host")
+    exe = str(tmp_path / "time_hist_asan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
+           "-I" + os.path.join(ROOT, "include"), "-I" + host, os.path.join(ROOT, "tests", "native", "time_hist_asan_driver.cpp"),
+           os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG,
+           "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
+    assert r.stdout.split() == ["ok", "33", "1"]
