@@ -211,6 +211,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_count_batch_multi": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_scan_dev_class_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, vp, vp]),
         "pcq_scan_dev_time_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, P(C.c_double), C.c_size_t, vp, vp]),
+        "pcq_scan_dev_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -479,6 +480,20 @@ class Context:
             ea = (C.c_double * len(edges))(*edges)
         _check(self.lib.pcq_scan_dev_time_hist_batch(self.handle, ca, pa, n, ea, max(len(edges), 1) - 1, C.c_void_p(device_hist),
                                                      C.c_void_p(stream)))
+
+    def scan_dev_raster_batch(self, cols: Sequence[Columns], preds: Sequence[Predicate], cells, nx: int, ny: int, d_raster: int,
+                              stream: Optional[int] = None) -> None:
+        """The density raster of a box (Predicate kind PCQ_PRED_BOUNDS; segments laid out as for scan_dev_count_batch) over many
+        resident LAST files in ONE pass.  cells: per segment its (x, y) cell widths in lattice units; for every point (X, Y, Z)
+        inside its segment's box, += 1 into word ((Y - lmin[1]) // cell_y) * nx + (X - lmin[0]) // cell_x of the nx * ny words of
+        d_raster."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        flat = [int(w) for c in cells for w in c]
+        assert len(flat) == 2 * n, "one (x, y) pair of cell widths per segment"
+        wa = (C.c_uint32 * max(len(flat), 1))(*flat)
+        _check(self.lib.pcq_scan_dev_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_raster), C.c_void_p(stream)))
 
     def scan_dev_count_batch_bounds_time(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_total: int,
                                          stream: Optional[int] = None) -> None:

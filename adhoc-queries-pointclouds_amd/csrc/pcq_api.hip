@@ -225,7 +225,7 @@ int pcq_ensure_partials(pcq_ctx *ctx, size_t n) {
 
 // The segment tables of the batched count kernels (DevSegment: box, DevClassSegment: class at DevSegment pitch,
 // DevCombinedSegment: box AND class, DevBoundsTimeSegment: box AND time, or the time histogram's with its edges behind the
-// table) share one pinned buffer and its device twin, sized in bytes.
+// table, DevRasterSegment: the density raster) share one pinned buffer and its device twin, sized in bytes.
 int pcq_ensure_segment_table(pcq_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->segments_cap) return PCQ_OK;
     if (ctx->d_segments) (void)hipFree(ctx->d_segments);
@@ -344,6 +344,8 @@ static const Option k_options[] = {
     {"multi_waves_per_cu", &pcq_ctx::multi_waves_per_cu, 0, 32, OPT_SET},
     {"class_hist_waves_per_cu", &pcq_ctx::class_hist_waves_per_cu, 0, 32, OPT_SET},
     {"time_hist_waves_per_cu", &pcq_ctx::time_hist_waves_per_cu, 0, 32, OPT_SET},
+    {"raster_waves_per_cu", &pcq_ctx::raster_waves_per_cu, 0, 32, OPT_SET},
+    {"raster_add", &pcq_ctx::raster_add, 0, 2, OPT_SET},  // 0 the product's, 1 per lane, 2 wave-level (scan_raster.hip)
     {"class_hist_copies", &pcq_ctx::class_hist_copies, 0, 16, OPT_SET},  // (only 0, 1, 2, 4, 8 and 16: scan_class_hist.hip)
 #endif
 };

@@ -148,6 +148,23 @@ constexpr int PCQ_SEGMENTS_CLASS_HIST = 0x4348;  // ("CH") no pcq_predicate_kind
 // count and edges behind them, under a kind of its own: the same segments under PCQ_PRED_BOUNDS_TIME are another entry's table.
 constexpr int PCQ_SEGMENTS_TIME_HIST = 0x5448;  // ("TH") no pcq_predicate_kind
 
+// One segment of a density raster launch (scan_raster.hip): DevSegment with the segment's cell widths in lattice units and the
+// magics of the division by them (raster_div.h).  At its own pitch in the same buffers, under a kind of its own: the widths are
+// part of the bytes the upload compares.
+struct DevRasterSegment {
+    const int4 *xyz;       // 16-byte aligned positions block
+    uint64_t n;            // points
+    uint64_t tile_begin;   // first global step of this segment
+    int32_t lo[3];         // (lo[0], lo[1]: the raster's origin)
+    uint32_t width[3];
+    int32_t empty;
+    int32_t _pad;
+    uint32_t cw[2];        // cell widths along x and y
+    uint32_t magic[2];     // raster_div_magic of them
+};
+static_assert(sizeof(DevRasterSegment) == 72, "DevRasterSegment: DevSegment and four words");
+constexpr int PCQ_SEGMENTS_RASTER = 0x5253;  // ("RS") no pcq_predicate_kind
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -330,6 +347,8 @@ struct pcq_ctx {
     int class_hist_waves_per_cu = 0;  // class histogram (scan_class_hist.hip): workgroups per CU (0 = the product's: CLASS_HIST_WAVES_PER_CU)
     int time_hist_waves_per_cu = 0;  // time histogram (scan_time_hist.hip): workgroups per CU (0 = the product's: TIME_HIST_WAVES_PER_CU)
     int class_hist_copies = 0;    // ... and copies of the LDS histogram per wave, 1 / 2 / 4 / 8 / 16 (0 = the product's: CLASS_HIST_COPIES)
+    int raster_waves_per_cu = 0;  // density raster (scan_raster.hip): workgroups per CU before the LDS limit (0 = the product's: RASTER_WAVES_PER_CU)
+    int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif
     int numa_node = -1;               // NUMA node the GPU hangs off (sysfs), -1 if unknown
     cpu_set_t node_cpus;              // its CPUs (empty if unknown)

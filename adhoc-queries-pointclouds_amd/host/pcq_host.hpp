@@ -404,6 +404,11 @@ public:
     // in this order: a dataset without times, then the box's own (min > max).  (with_times)
     Status count_bounds_by_time(const double bmin[3], const double bmax[3], const double *edges, size_t nbins, uint64_t *hist,
                                 uint64_t *points_scanned = nullptr);
+    // the density raster of a box: raster[cy * nx + cx] counts the points of cell (cx, cy) of nx x ny cells of cell_size from
+    // (bmin[0], bmin[1]) with z in [bmin[2], zmax], from ONE pass per block of PCQ_RASTER_CELLS_MAX cells.  The caller has checked nx,
+    // ny and cell_size.  A cell that is no whole number of a scanned file's lattice steps: PCQ_ERR_UNSUPPORTED.
+    Status count_bounds_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *raster,
+                               uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
@@ -432,7 +437,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster)
     uint64_t points_ = 0;
 };
 

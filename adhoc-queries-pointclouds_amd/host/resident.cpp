@@ -27,6 +27,10 @@
 //
 // The time histogram of a box (count_bounds_by_time): the per-slice breakdown of count_bounds_time for the bins between the
 // caller's edges, one pcq_scan_dev_time_hist_batch per group of PCQ_TIME_BINS_MAX bins, instead of one box AND time count per bin.
+//
+// The density raster of a box (count_bounds_raster): the per-cell breakdown of count_bounds over a 2-D lattice of cells, one
+// pcq_scan_dev_raster_batch per block of PCQ_RASTER_CELLS_MAX cells, instead of one box count per cell.
+#include <cmath>
 #include <cstring>
 
 #include "pcq_host.hpp"
@@ -310,6 +314,81 @@ Status ResidentDataset::count_bounds_by_time(const double bmin[3], const double 
     }, hist);
     if (st.ok() && points_scanned) *points_scanned = seg.scanned;
     return st;
+}
+
+// Where in this box are the points: the prologue of count_box with the world box of the whole raster, then per surviving file the
+// cell as a whole number of that file's lattice steps (else PCQ_ERR_UNSUPPORTED) and the file's box cut to full cells: lmin ..
+// lmin + n k - 1 on x and y.  A raster of at most PCQ_RASTER_CELLS_MAX cells is ONE pcq_scan_dev_raster_batch; a larger one is cut
+// into blocks of whole rows (of row pieces, where a row alone is too long), each block the integer sub-box of every file — empty
+// where it starts beyond the i32 range — and one launch into its own counter words.  All launches go to the context's stream; the
+// counts are copied back once and scattered.  `raster` and `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::count_bounds_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *raster,
+                                            uint64_t *points_scanned) {
+    const double bmax[3] = {bmin[0] + (double)nx * cell_size, bmin[1] + (double)ny * cell_size, zmax};
+    AABB bounds;
+    Status st = AABB::from_min_max(bmin, bmax, &bounds);
+    if (!st.ok()) return st;
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    const uint64_t dim[2] = {nx, ny};
+    pcq_predicate pred = predicate(PCQ_PRED_BOUNDS);
+    for (const auto &f : files_) {
+        bool go;
+        const int brc = box_prologue(f, bounds, &pred, &go);
+        if (brc) return Status::FromLib(brc);
+        if (!go) continue;
+        for (int a = 0; a < 2; a++) {
+            const double cw = cell_size / f.header.scale[a], k = std::nearbyint(cw);
+            if (!(k >= 1.0 && k <= 4294967295.0) || !(std::fabs(cw - k) <= 1e-9 * k))
+                return Status::Err(PCQ_ERR_UNSUPPORTED, "raster: the cell size is not a whole number of lattice steps of " + f.path);
+            if (pred.lmin[a] < INT32_MIN || pred.lmin[a] > INT32_MAX)
+                return Status::Err(PCQ_ERR_UNSUPPORTED, "raster: the origin lies outside the lattice of " + f.path);
+            cells.push_back((uint32_t)k);
+            pred.lmax[a] = pred.lmin[a] + (int64_t)dim[a] * (int64_t)k - 1;
+        }
+        seg.cols.push_back(file_columns(f, PCQ_PRED_BOUNDS));
+        seg.preds.push_back(pred);
+        seg.scanned += f.header.number_of_points;
+    }
+    // blocks of bw x bh cells, row-major over the raster; block b's words follow block b - 1's in the counter
+    const uint64_t bw = nx < PCQ_RASTER_CELLS_MAX ? nx : (uint64_t)PCQ_RASTER_CELLS_MAX;
+    const uint64_t bh = PCQ_RASTER_CELLS_MAX / bw < ny ? PCQ_RASTER_CELLS_MAX / bw : ny;
+    const size_t words = (size_t)(nx * ny);
+    std::vector<uint64_t> got(words);
+    st = read_counts(words, [&] {
+        int rc = PCQ_OK;
+        size_t at = 0;
+        std::vector<pcq_predicate> preds(seg.preds.size());
+        for (uint64_t y0 = 0; y0 < ny && !rc && !seg.cols.empty(); y0 += bh) {
+            for (uint64_t x0 = 0; x0 < nx && !rc; x0 += bw) {
+                const uint64_t off[2] = {x0, y0}, ext[2] = {nx - x0 < bw ? nx - x0 : bw, ny - y0 < bh ? ny - y0 : bh};
+                for (size_t i = 0; i < preds.size(); i++) {
+                    pcq_predicate p = seg.preds[i];
+                    for (int a = 0; a < 2; a++) {
+                        const int64_t k = cells[2 * i + a];
+                        p.lmin[a] += (int64_t)off[a] * k;
+                        p.lmax[a] = p.lmin[a] + (int64_t)ext[a] * k - 1;
+                        if (p.lmin[a] > INT32_MAX) p.lmin[0] = 1, p.lmax[0] = 0;  // no stored point can lie in this block: an empty predicate
+                    }
+                    if (p.lmin[0] > p.lmax[0]) p.lmin[1] = 1, p.lmax[1] = 0;
+                    preds[i] = p;
+                }
+                rc = pcq_scan_dev_raster_batch(ctx_, seg.cols.data(), preds.data(), cells.data(), preds.size(), (uint32_t)ext[0], (uint32_t)ext[1],
+                                               counter_ + at, nullptr);
+                at += (size_t)(ext[0] * ext[1]);
+            }
+        }
+        return rc;
+    }, got.data());
+    if (!st.ok()) return st;
+    size_t at = 0;
+    for (uint64_t y0 = 0; y0 < ny; y0 += bh)
+        for (uint64_t x0 = 0; x0 < nx; x0 += bw) {
+            const uint64_t w = nx - x0 < bw ? nx - x0 : bw, h = ny - y0 < bh ? ny - y0 : bh;
+            for (uint64_t y = 0; y < h; y++, at += (size_t)w) memcpy(raster + (y0 + y) * nx + x0, got.data() + at, (size_t)w * 8);
+        }
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
 }
 
 // `--class` over the dataset, count only (last.rs:253-262: whole byte, no file-level early-out).

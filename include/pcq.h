@@ -294,6 +294,22 @@ int pcq_scan_dev_class_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const p
 #define PCQ_TIME_BINS_MAX 1024
 int pcq_scan_dev_time_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, size_t nsegments,
                                  const double *edges, size_t nbins, uint64_t *device_hist, void *stream);
+/* The density raster of a box in ONE pass: "where in this box are the points?".  Every predicate is PCQ_PRED_BOUNDS and the layout
+ * is that of pcq_scan_dev_count_batch: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.  `cell_xy` is a HOST
+ * pointer to [nsegments][2] cell widths in the segment's lattice units (x, y), 1 .. 2^32 - 1.  All in the segment's integer
+ * lattice: a point (X, Y, Z) of segment i inside the box of preds[i] adds 1 to device_raster[cy * nx + cx] with cx = (X - lmin[0])
+ * / cell_xy[2i] and cy = (Y - lmin[1]) / cell_xy[2i + 1], exact integer floor divisions, so that word (cx, cy) grows by what
+ * pcq_scan_dev_count_batch counts for the box intersected with that cell's integer sub-box, for every cell at once and from one
+ * read of the data.  Only integer arithmetic decides a cell.  The counts are ADDED to device_raster[0 .. nx * ny), row-major with
+ * y the slow axis; no word beyond is touched.  A predicate that is empty (lmin > lmax on an axis, or a box outside the i32 value
+ * range) matches nothing and its segment is not evaluated.  nsegments == 0 is PCQ_OK after the argument checks.  A null argument,
+ * nx == 0, ny == 0 or nx * ny above PCQ_RASTER_CELLS_MAX, any other predicate kind, any other layout, a cell width of 0 in a
+ * segment with points, a non-empty predicate whose lmin[0] or lmin[1] lies outside the i32 range, and a non-empty predicate whose
+ * box reaches beyond the raster — (min(lmax[a], INT32_MAX) - lmin[a]) / cell >= n for a = 0 or 1 — are refused (PCQ_ERR_ARG)
+ * before anything is uploaded or launched: device_raster is untouched.  lmax and lmin[2] may be anywhere. */
+#define PCQ_RASTER_CELLS_MAX 8192
+int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                              size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_raster, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

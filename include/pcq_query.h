@@ -168,6 +168,24 @@ int pcq_query_resident_count_bounds_time(pcq_host_resident *r, const double bmin
  * min > max).  On any failure hist and points_scanned are left as they were. */
 int pcq_query_resident_count_bounds_by_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], const double *edges,
                                             size_t nbins, uint64_t *hist, uint64_t *points_scanned);
+/* Where in this box are the points (`--bounds`, count only, for every cell of a 2-D raster at once): the raster is nx x ny cells
+ * of cell_size world units from the origin (bmin[0], bmin[1]), row-major with y upward (raster[cy * nx + cx]), and counts the
+ * points with z in [bmin[2], zmax].  The checks in their order, before the dataset or a device is touched: a null r, bmin or
+ * raster is PCQ_ERR_ARG; nx * ny == 0 is PCQ_OK with nothing written; nx * ny above PCQ_QUERY_RASTER_CELLS_MAX is PCQ_ERR_ARG; a
+ * cell_size that is not finite or not above 0 is PCQ_ERR_ARG.  Then per file the prologue of pcq_query_resident_count_bounds with
+ * the world box bmin .. (bmin[0] + nx cell_size, bmin[1] + ny cell_size, zmax): the header early-out, pcq_box_to_local bug for
+ * bug, PCQ_ERR_PANIC for bmin[2] > zmax.  A cell is a whole number of a file's lattice steps: k = nearbyint(cell_size / scale[a])
+ * must lie in 1 .. 2^32 - 1 with |cell_size / scale[a] - k| <= 1e-9 k, and the file's lmin[0] and lmin[1] inside the i32 range,
+ * else PCQ_ERR_UNSUPPORTED naming the file.  The file's box becomes lmin[a] .. lmin[a] + n_a k - 1 on x and y (the cells are full
+ * and half-open in the lattice; z stays as converted), so raster[cy * nx + cx] is the number of stored points (X, Y, Z), over the
+ * surviving files, with (X - lmin[0]) / k_x == cx, (Y - lmin[1]) / k_y == cy and Z inside.  ONE launch over the positions of the
+ * surviving files while nx * ny <= PCQ_RASTER_CELLS_MAX (pcq.h, pcq_scan_dev_raster_batch); a larger raster is cut into blocks of
+ * at most that many cells, one launch per block into its own counter words, each reading every surviving file.  points_scanned
+ * (NULL: not wanted): what pcq_query_resident_count_bounds reports for the world box.  On any failure raster and points_scanned
+ * are left as they were. */
+#define PCQ_QUERY_RASTER_CELLS_MAX (1u << 20)
+int pcq_query_resident_count_bounds_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
+                                           uint64_t ny, uint64_t *raster, uint64_t *points_scanned);
 /* == pcq_query_search_file_bounds_time(path, bmin, bmax, start, end, optimized=1, c) for every loaded file, in load order, into
  * ONE collector: the same count, the same records byte for byte and in order (class 0, colour (0,0,0), whether or not colour
  * blocks are loaded), the same grid cells and winners; the header early-out leaves the collector's file-order index where it
