@@ -532,6 +532,7 @@ static int grid_fold(pcq_ctx *ctx, pcq_collector *c) {
 #endif
         if (f2 > 1) ctx->grid_level2++;
         if (big && stream) ctx->grid_deferred += (int64_t)st[3];
+        if (dense) ctx->grid_dense_deferred += (int64_t)st[3];
         if (st[1]) {  // a partition held more cells than the LDS table: more partitions
             if (f2 >= F2_MAX || attempt > 8) return pcq_fail(PCQ_ERR_UNSUPPORTED, "grid collector: a partition does not fit the LDS table at the largest fan-out");
             ctx->grid_refolds++;

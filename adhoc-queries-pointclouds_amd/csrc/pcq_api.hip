@@ -331,7 +331,7 @@ static const Option k_options[] = {
     {"emit_sparse_max", &pcq_ctx::emit_sparse_max, 0, 2048, OPT_SET},
     {"scratch_cap_words", &pcq_ctx::scratch_cap_words, 0, INT64_MAX, OPT_SET},
     DIAG(numa_node), DIAG(grid_folds), DIAG(grid_level2), DIAG(grid_refolds), DIAG(grid_level2_exact), DIAG(grid_last_f2),
-    DIAG(grid_compactions), DIAG(grid_deferred), DIAG(grid_last_tuples), DIAG(grid_last_tuple_bytes), DIAG(emit_park_fallbacks),
+    DIAG(grid_compactions), DIAG(grid_deferred), DIAG(grid_dense_deferred), DIAG(grid_last_tuples), DIAG(grid_last_tuple_bytes), DIAG(emit_park_fallbacks),
 #ifdef PCQ_LAB
     {"k1_variant", &pcq_ctx::k1_variant, 0, 14, OPT_SET | OPT_ENV},
     {"k1_waves_per_cu", &pcq_ctx::k1_waves_per_cu, 1, 32, OPT_SET | OPT_ENV},

@@ -319,6 +319,7 @@ struct pcq_ctx {
                                         // 1 = every tile, 2 = never; the results are the same, the tuples moved are not
     int grid_stream = 1;                // option (tests): 0 = a coarse grid's bins are folded by k_fold<BIG> (the fallback of the streaming fold) only
     int64_t grid_deferred = 0;          // diagnostics: bins the streaming fold left to k_fold<BIG> (survivor list outgrown)
+    int64_t grid_dense_deferred = 0;    // diagnostics: partitions k_fold_dense left to k_fold<SMALL> (more tuples than its chunk of 1536)
     int host_in_place = 2;              // option: count and grid scans of host / file data read the pinned staging ring IN PLACE (over PCIe) instead of
                                         // copying it to a device twin first: 0 never, 1 always, 2 while the process's copy path is being set up
                                         // (host_stream.hip scan_host_impl)

@@ -426,14 +426,18 @@ int pcq_bind_thread_near_device(pcq_ctx *ctx);
  * most that many matches leaves them as 16-byte words in the count pass — default 256, bounds queries —
  * or is written by one wave from the count pass's match bits — default 64; 0 = never), "grid_tuple16" / "grid_stream" (tests: force
  * the grid collector's tuple size — 1 = 16 bytes with the selector, 2 = without, 0 = 24 bytes — and the coarse fold's form —
- * 1 = k_fold_stream, 0 = k_fold<BIG>; same results in every combination), "scratch_cap_words" (tests: while > 0, growing the
+ * 1 = k_fold_stream, 0 = k_fold<BIG>; same results in every combination), "grid_block_pad" (tests: 0 .. 65536 units of 16
+ * bytes left between a tile's block of tuples and the next one — moves every block's address and phase; same results for
+ * every value; default 0), "scratch_cap_words" (tests: while > 0, growing the
  * context's device scratch beyond that many 8-byte words fails with PCQ_ERR_NOMEM without an allocation — a buffer scan then
  * emits without parking its matches; 0 = no cap, the default).  pcq_get_option also
  * reads "numa_node" and the grid diagnostics "grid_folds", "grid_level2" (folds that needed a second partition level),
  * "grid_refolds" (folds repeated with more partitions), "grid_level2_exact" (second levels repeated in the counting form),
- * "grid_compactions" (folds that copied short fragments together first), "grid_last_f2", "grid_last_tuples" (tuples the last
- * fold found pending: what is left of the matches after pass 0's own fold), "grid_last_tuple_bytes" (16 or 24: the tuple size
- * the last grid scan packed its matches in) and "emit_park_fallbacks" (buffer scans that found no room for the parked matches
+ * "grid_compactions" (folds that copied short fragments together first), "grid_deferred" (bins the streaming fold left to
+ * k_fold<BIG>: their survivors outgrew the list), "grid_dense_deferred" (second-level partitions k_fold_dense left to
+ * k_fold<SMALL>: more than its chunk of 1536 tuples; both also count in an attempt that is repeated with more partitions),
+ * "grid_last_f2", "grid_last_tuples" (tuples the last fold found pending: what is left of the matches after pass 0's own
+ * fold), "grid_last_tuple_bytes" (16 or 24: the tuple size the last grid scan packed its matches in) and "emit_park_fallbacks" (buffer scans that found no room for the parked matches
  * and read their thin tiles a second time instead).  (The kernel-shape experiments of round 1 —
  * "k1_variant", "batch_variant", ... — are options of libpcq_lab.so only: include/pcq_lab.h.) */
 int pcq_set_option(pcq_ctx *ctx, const char *key, int64_t value);

@@ -28,11 +28,12 @@ RANGED = [
     ("emit_sparse_max", "emit_sparse_max", 0, 2048),
     ("grid_tuple16", "grid_tuple16", 0, 2),
     ("grid_stream", "grid_stream", 0, 1),
+    ("grid_block_pad", "grid_block_pad", 0, 65536),
     ("scratch_cap_words", "scratch_cap_words", 0, None),
 ]
 BOOLEAN = [("numa_local", "numa_local"), ("allreduce_single_rank", "allreduce_single_rank")]
 DIAGNOSTICS = ["numa_node", "grid_folds", "grid_level2", "grid_refolds", "grid_level2_exact", "grid_compactions", "grid_last_f2",
-               "grid_last_tuples", "grid_last_tuple_bytes", "emit_park_fallbacks"]
+               "grid_last_tuples", "grid_last_tuple_bytes", "emit_park_fallbacks", "grid_deferred", "grid_dense_deferred"]
 
 
 def header_default(field):
