@@ -1,5 +1,5 @@
 // scan_batch_host.h — the host side of the K1-family batched launches (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip,
-// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip): host code only; the kernels and their constants are in scan_tiles.h.
+// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip): host code only; the kernels and their constants are in scan_tiles.h.
 #pragma once
 
 #include <vector>
@@ -15,6 +15,8 @@ namespace {
 // entry's refusals that come before those of the positions), the positions' refusals, fill(seg, i) (the entry's columns and
 // predicates, or their refusal); xyz, n and tile_begin are filled here.  launch(workgroups, steps) enqueues the kernel, or refuses.
 // A trailer (the time histogram's edges) travels behind the table in the same upload, under the same compare of all bytes.
+// finish(workgroups) enqueues the fold of the partials into the caller's words: pcq_launch_finish_counts (`folded` slices added into
+// d_out) for every count; the height raster brings its own (pcq_launch_finish_zrange).
 struct K1Batch {
     const char *prefix;  // of a refusal's text
     int table_kind;      // the key of the table in HBM (pcq_upload_segment_table)
@@ -30,9 +32,9 @@ void seg_box(Seg &g, const DP &dp) {
     for (int a = 0; a < 3; a++) g.lo[a] = dp.lo[a], g.width[a] = dp.width[a];
     g.empty = dp.empty;
 }
-template <typename Seg, typename Admit, typename Fill, typename Launch>
-int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, size_t nsegments, uint64_t *d_out, hipStream_t s, Admit admit,
-                    Fill fill, Launch launch) {
+template <typename Seg, typename Admit, typename Fill, typename Launch, typename Finish>
+int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, size_t nsegments, hipStream_t s, Admit admit, Fill fill, Launch launch,
+                    Finish finish) {
     std::vector<Seg> table(nsegments);
     memset(table.data(), 0, nsegments * sizeof(Seg));
     uint64_t steps = 0;
@@ -67,7 +69,13 @@ int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, siz
     if (rc) return rc;
     rc = launch((unsigned)g, steps);
     if (rc) return rc;
-    return pcq_launch_finish_counts(ctx, b.folded, (int)g, d_out, s);
+    return finish((int)g);
+}
+template <typename Seg, typename Admit, typename Fill, typename Launch>
+int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, size_t nsegments, uint64_t *d_out, hipStream_t s, Admit admit,
+                    Fill fill, Launch launch) {
+    return k1_batch_launch<Seg>(ctx, b, cols, nsegments, s, admit, fill, launch,
+                                [&](int g) { return pcq_launch_finish_counts(ctx, b.folded, g, d_out, s); });
 }
 
 }  // namespace

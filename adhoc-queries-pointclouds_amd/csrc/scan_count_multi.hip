@@ -153,6 +153,37 @@ __global__ __launch_bounds__(BLOCK) void k_finish_counts(const uint64_t *__restr
     if (threadIdx.x == 0) atomicAdd((unsigned long long *)(d_counts + blockIdx.x), (unsigned long long)s[0]);
 }
 
+// The finish of the height raster (scan_zrange.hip, pcq_launch_finish_zrange): block `cell` folds slice `cell` of the per-workgroup
+// partials — max z in the high word, min z in the low word, both signed; a workgroup that met no point of the cell wrote INT32_MIN
+// and INT32_MAX — and folds the two into d_zmin[cell] and d_zmax[cell] (vector atomics on global memory: callers on several streams
+// may fold into the same words).  A cell no workgroup reached touches neither word.
+__global__ __launch_bounds__(BLOCK) void k_finish_zrange(const uint64_t *__restrict__ partials, int nblocks, int32_t *__restrict__ d_zmin,
+                                                        int32_t *__restrict__ d_zmax) {
+    __shared__ int32_t smin[BLOCK], smax[BLOCK];
+    const uint64_t *slice = partials + (uint64_t)blockIdx.x * (uint64_t)nblocks;
+    int32_t mn = INT32_MAX, mx = INT32_MIN;
+    for (int i = threadIdx.x; i < nblocks; i += BLOCK) {
+        const uint64_t w = slice[i];
+        const int32_t lo = (int32_t)(uint32_t)w, hi = (int32_t)(uint32_t)(w >> 32);
+        mn = lo < mn ? lo : mn;
+        mx = hi > mx ? hi : mx;
+    }
+    smin[threadIdx.x] = mn, smax[threadIdx.x] = mx;
+    __syncthreads();
+    for (int off = BLOCK / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            const int32_t a = smin[threadIdx.x + off], b = smax[threadIdx.x + off];
+            if (a < smin[threadIdx.x]) smin[threadIdx.x] = a;
+            if (b > smax[threadIdx.x]) smax[threadIdx.x] = b;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && smin[0] <= smax[0]) {
+        atomicMin(d_zmin + blockIdx.x, smin[0]);
+        atomicMax(d_zmax + blockIdx.x, smax[0]);
+    }
+}
+
 template <int NQ>
 void launch_multi(pcq_ctx *ctx, unsigned g, int nsegments, uint64_t steps, hipStream_t s) {
     hipLaunchKernelGGL((k_bounds_count_multi_pipe<K1_TILES, NQ>), dim3(g), dim3(64), 0, s,
@@ -208,6 +239,12 @@ extern "C" int pcq_scan_dev_count_batch_multi(pcq_ctx *ctx, const pcq_columns *c
 
 int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d_counts, hipStream_t s) {
     hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)nslices), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_counts);
+    PCQ_HIP(hipGetLastError());
+    return PCQ_OK;
+}
+
+int pcq_launch_finish_zrange(pcq_ctx *ctx, int ncells, int nblocks, int32_t *d_zmin, int32_t *d_zmax, hipStream_t s) {
+    hipLaunchKernelGGL(k_finish_zrange, dim3((unsigned)ncells), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_zmin, d_zmax);
     PCQ_HIP(hipGetLastError());
     return PCQ_OK;
 }

@@ -34,6 +34,7 @@
 // segments x 512, in all, and HBM (288 GB) holds 2.4 x 10^10 points at 12 B/point; with the grid capped at steps + segments every
 // wave has one step and one segment's leftovers at most.
 #include "pcq_internal.h"
+#include "raster_cells.h"
 #include "raster_div.h"
 #include "scan_batch_host.h"
 #include "scan_tiles.h"
@@ -56,32 +57,6 @@ constexpr uint32_t RASTER_LDS_PER_CU = 160 * 1024;
 // profiles/raster_rate_sweep.log.
 constexpr bool RASTER_WAVE_ADD = false;
 
-// The raster's cursor kind for seg_seek (scan_tiles.h): no second column is loaded (PipeRegs<TILES>), the segment's constants
-// take the place of one.
-constexpr int COL_RASTER = 3;
-template <>
-struct BatchSeg<COL_RASTER> {
-    typedef DevRasterSegment type;
-};
-template <>
-struct SegCol<COL_RASTER> {
-    int32_t lox, loy;      // the raster's origin: the box's lower corner, unrotated (uniform)
-    uint32_t cwx, cwy;     // cell widths (uniform)
-    uint32_t mx, my;       // their magics (uniform)
-};
-typedef SegCol<COL_RASTER> RasterCol;
-// through SGPRs like the box (seg_seek says why)
-__device__ __forceinline__ void segcol_seek(RasterCol &c, const DevRasterSegment &g, int) {
-    int32_t lox = g.lo[0], loy = g.lo[1];
-    uint32_t cwx = g.cw[0], cwy = g.cw[1], mx = g.magic[0], my = g.magic[1];
-    asm volatile("" : "+s"(lox), "+s"(loy), "+s"(cwx), "+s"(cwy), "+s"(mx), "+s"(my));
-    c.lox = lox, c.loy = loy, c.cwx = cwx, c.cwy = cwy, c.mx = mx, c.my = my;
-}
-
-__device__ __forceinline__ uint32_t cell_of(int x, int y, const RasterCol &c, uint32_t nx) {
-    return raster_div((uint32_t)(y - c.loy), c.cwy, c.my) * nx + raster_div((uint32_t)(x - c.lox), c.cwx, c.mx);
-}
-
 // One slot: the points of the lanes in `pass` (uniform) into their cells, without a branch.  WAVE: when every passing lane has the
 // cell of the first one, that lane alone adds their number; a slot without a passing lane has no first lane and adds nothing.
 template <bool WAVE>
@@ -96,11 +71,6 @@ __device__ __forceinline__ void raster_add(uint32_t *ras, uint64_t pass, uint32_
         by = same ? (uint32_t)__popcll(pass) : 1u;
     }
     if (add) atomicAdd(&ras[cell], by);  // (result unused: ds_add_u32, exec-masked)
-}
-
-// v of lane + 1; lane 63 gets `last`
-__device__ __forceinline__ int next_lane(int v, int last) {
-    return __builtin_amdgcn_update_dpp(last, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
 }
 
 // One tile in registers: every passing point into the raster.  A tile none of whose points passes is skipped; otherwise the six
@@ -234,26 +204,9 @@ extern "C" int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, 
                        : (int)PCQ_OK;
         },
         [&](DevRasterSegment &g, size_t i) {
-            DevPred dp;
-            const int prc = pcq_make_dev_pred(&preds[i], &dp);
-            if (prc) return prc;
             const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
             const uint32_t dim[2] = {nx, ny};
-            for (int a = 0; a < 2; a++) {
-                if (cw[a] == 0) {
-                    if (cols[i].n) return pcq_fail(PCQ_ERR_ARG, "raster_batch: cell width 0 on axis %d of segment %zu", a, i);
-                    continue;
-                }
-                if (dp.empty) continue;  // (matches nothing: not evaluated)
-                const int64_t lmin = preds[i].lmin[a], lmax = preds[i].lmax[a] > INT32_MAX ? (int64_t)INT32_MAX : preds[i].lmax[a];
-                if (lmin < INT32_MIN || lmin > INT32_MAX)
-                    return pcq_fail(PCQ_ERR_ARG, "raster_batch: the raster's origin on axis %d of segment %zu is outside the i32 range", a, i);
-                if ((uint64_t)(lmax - lmin) / cw[a] >= dim[a])
-                    return pcq_fail(PCQ_ERR_ARG, "raster_batch: the box of segment %zu reaches beyond the raster's %u cells on axis %d", i, dim[a], a);
-            }
-            seg_box(g, dp);
-            for (int a = 0; a < 2; a++) g.cw[a] = cw[a], g.magic[a] = raster_div_magic(cw[a]);
-            return (int)PCQ_OK;
+            return raster_segment_fill("raster_batch", g, preds[i], cols[i], cw, dim, i);
         },
         [&](unsigned g, uint64_t steps) {
 #ifdef PCQ_LAB

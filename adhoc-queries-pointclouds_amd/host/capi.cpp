@@ -400,6 +400,17 @@ extern "C" int pcq_query_resident_count_bounds_raster(pcq_host_resident *r, cons
     if (!(cell_size > 0.0) || cell_size - cell_size != 0.0) return done(Status::Err(PCQ_ERR_ARG, "raster: cell_size must be finite and above 0"));
     return done(r->ds->count_bounds_raster(bmin, zmax, cell_size, nx, ny, raster, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
 }
+extern "C" int pcq_query_resident_bounds_zrange_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
+                                                       uint64_t ny, double *zlo, double *zhi, uint64_t *points_scanned) {
+    if (!r || !bmin || !zlo || !zhi) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nx == 0 || ny == 0) return PCQ_OK;
+    if (nx > PCQ_QUERY_RASTER_CELLS_MAX || ny > PCQ_QUERY_RASTER_CELLS_MAX || nx * ny > PCQ_QUERY_RASTER_CELLS_MAX)  // (neither r nor a device is touched before these)
+        return done(Status::Err(PCQ_ERR_ARG, "height raster: " + std::to_string(nx) + " x " + std::to_string(ny) + " cells (at most " +
+                                                 std::to_string(PCQ_QUERY_RASTER_CELLS_MAX) + ")"));
+    if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
+        return done(Status::Err(PCQ_ERR_ARG, "height raster: cell_size must be finite and above 0"));
+    return done(r->ds->bounds_zrange_raster(bmin, zmax, cell_size, nx, ny, zlo, zhi, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
+}
 extern "C" int pcq_query_resident_search_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
                                                      pcq_host_collector *c) {
     if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

@@ -409,6 +409,12 @@ public:
     // ny and cell_size.  A cell that is no whole number of a scanned file's lattice steps: PCQ_ERR_UNSUPPORTED.
     Status count_bounds_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *raster,
                                uint64_t *points_scanned = nullptr);
+    // the height raster of a box: zlo[cy * nx + cx] / zhi[...] are the lowest / highest world z of the points the density raster counts
+    // in cell (cx, cy), NaN where it counts none; ONE pass per group of files of one z lattice and block of PCQ_ZRANGE_CELLS_MAX cells.
+    // The caller has checked nx, ny and cell_size.  count_bounds_raster's errors, and PCQ_ERR_UNSUPPORTED for a scanned file whose z
+    // scale is not finite or not above 0.
+    Status bounds_zrange_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, double *zlo, double *zhi,
+                                uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);
@@ -429,6 +435,8 @@ private:
     Status read_counts(size_t words, Launch launch, uint64_t *out);  // (resident.cpp only)
     Status box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg);
     Status run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out);
+    Status raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, Segments *seg,
+                           std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster
     Status count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     Status search_files(const AABB *bounds, pcq_predicate pred, ResultCollector &rc);  // search_*
@@ -437,7 +445,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster and of bounds_zrange_raster: two i32)
     uint64_t points_ = 0;
 };
 

@@ -30,6 +30,11 @@
 //
 // The density raster of a box (count_bounds_raster): the per-cell breakdown of count_bounds over a 2-D lattice of cells, one
 // pcq_scan_dev_raster_batch per block of PCQ_RASTER_CELLS_MAX cells, instead of one box count per cell.
+//
+// The height raster of a box (bounds_zrange_raster): the lowest and the highest world z of the points of every cell of the same
+// lattice, one pcq_scan_dev_zrange_raster_batch per group of files of one z lattice and block of PCQ_ZRANGE_CELLS_MAX cells, instead of
+// a search into a buffer collector whose records the host would have to reduce.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -316,20 +321,17 @@ Status ResidentDataset::count_bounds_by_time(const double bmin[3], const double 
     return st;
 }
 
-// Where in this box are the points: the prologue of count_box with the world box of the whole raster, then per surviving file the
-// cell as a whole number of that file's lattice steps (else PCQ_ERR_UNSUPPORTED) and the file's box cut to full cells: lmin ..
-// lmin + n k - 1 on x and y.  A raster of at most PCQ_RASTER_CELLS_MAX cells is ONE pcq_scan_dev_raster_batch; a larger one is cut
-// into blocks of whole rows (of row pieces, where a row alone is too long), each block the integer sub-box of every file — empty
-// where it starts beyond the i32 range — and one launch into its own counter words.  All launches go to the context's stream; the
-// counts are copied back once and scattered.  `raster` and `points_scanned` are written only when everything has succeeded.
-Status ResidentDataset::count_bounds_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *raster,
-                                            uint64_t *points_scanned) {
+// The prologue of the two rasters of a box (count_bounds_raster, bounds_zrange_raster): the prologue of count_box with the world
+// box of the whole raster, then per surviving file the cell as a whole number of that file's lattice steps (else
+// PCQ_ERR_UNSUPPORTED) and the file's box cut to full cells: lmin .. lmin + n k - 1 on x and y.  cells: [segment][2], the cell in
+// each segment's lattice steps.  z_lattice: a surviving file whose z scale is not finite or not above 0 is PCQ_ERR_UNSUPPORTED as
+// well (the height raster's conversion to world z has to be monotone).
+Status ResidentDataset::raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, Segments *seg,
+                                        std::vector<uint32_t> *cells) {
     const double bmax[3] = {bmin[0] + (double)nx * cell_size, bmin[1] + (double)ny * cell_size, zmax};
     AABB bounds;
     Status st = AABB::from_min_max(bmin, bmax, &bounds);
     if (!st.ok()) return st;
-    Segments seg;
-    std::vector<uint32_t> cells;  // [segment][2]
     const uint64_t dim[2] = {nx, ny};
     pcq_predicate pred = predicate(PCQ_PRED_BOUNDS);
     for (const auto &f : files_) {
@@ -343,50 +345,145 @@ Status ResidentDataset::count_bounds_raster(const double bmin[3], double zmax, d
                 return Status::Err(PCQ_ERR_UNSUPPORTED, "raster: the cell size is not a whole number of lattice steps of " + f.path);
             if (pred.lmin[a] < INT32_MIN || pred.lmin[a] > INT32_MAX)
                 return Status::Err(PCQ_ERR_UNSUPPORTED, "raster: the origin lies outside the lattice of " + f.path);
-            cells.push_back((uint32_t)k);
+            cells->push_back((uint32_t)k);
             pred.lmax[a] = pred.lmin[a] + (int64_t)dim[a] * (int64_t)k - 1;
         }
-        seg.cols.push_back(file_columns(f, PCQ_PRED_BOUNDS));
-        seg.preds.push_back(pred);
-        seg.scanned += f.header.number_of_points;
+        const double sz = f.header.scale[2];
+        if (z_lattice && (!(sz > 0.0) || sz - sz != 0.0))
+            return Status::Err(PCQ_ERR_UNSUPPORTED, "height raster: the z scale is not finite and above 0 in " + f.path);
+        seg->cols.push_back(file_columns(f, PCQ_PRED_BOUNDS));
+        seg->preds.push_back(pred);
+        seg->scanned += f.header.number_of_points;
     }
-    // blocks of bw x bh cells, row-major over the raster; block b's words follow block b - 1's in the counter
-    const uint64_t bw = nx < PCQ_RASTER_CELLS_MAX ? nx : (uint64_t)PCQ_RASTER_CELLS_MAX;
-    const uint64_t bh = PCQ_RASTER_CELLS_MAX / bw < ny ? PCQ_RASTER_CELLS_MAX / bw : ny;
+    return Status::Ok();
+}
+
+// A raster of nx x ny cells cut into the blocks of one launch each, at most `limit` cells: whole rows, or row pieces where a row
+// alone is too long; row-major over the raster, block b's words following block b - 1's (`at`).
+namespace {
+struct RasterBlock {
+    uint64_t x0, y0, w, h;
+    size_t at;
+};
+std::vector<RasterBlock> raster_blocks(uint64_t nx, uint64_t ny, uint64_t limit) {
+    const uint64_t bw = nx < limit ? nx : limit;
+    const uint64_t bh = limit / bw < ny ? limit / bw : ny;
+    std::vector<RasterBlock> out;
+    size_t at = 0;
+    for (uint64_t y0 = 0; y0 < ny; y0 += bh)
+        for (uint64_t x0 = 0; x0 < nx; x0 += bw) {
+            const RasterBlock b = {x0, y0, nx - x0 < bw ? nx - x0 : bw, ny - y0 < bh ? ny - y0 : bh, at};
+            out.push_back(b);
+            at += (size_t)(b.w * b.h);
+        }
+    return out;
+}
+// Segment i's predicate for a block: the integer sub-box of its file — empty where it starts beyond the i32 range.
+pcq_predicate block_predicate(pcq_predicate p, const uint32_t *cell, const RasterBlock &b) {
+    const uint64_t off[2] = {b.x0, b.y0}, ext[2] = {b.w, b.h};
+    for (int a = 0; a < 2; a++) {
+        const int64_t k = cell[a];
+        p.lmin[a] += (int64_t)off[a] * k;
+        p.lmax[a] = p.lmin[a] + (int64_t)ext[a] * k - 1;
+        if (p.lmin[a] > INT32_MAX) p.lmin[0] = 1, p.lmax[0] = 0;  // no stored point can lie in this block: an empty predicate
+    }
+    if (p.lmin[0] > p.lmax[0]) p.lmin[1] = 1, p.lmax[1] = 0;
+    return p;
+}
+// the words of the blocks, one after the other in `got`, into the row-major raster
+template <typename T>
+void scatter_blocks(const std::vector<RasterBlock> &blocks, const T *got, uint64_t nx, T *raster) {
+    for (const RasterBlock &b : blocks)
+        for (uint64_t y = 0; y < b.h; y++) memcpy(raster + (b.y0 + y) * nx + b.x0, got + b.at + (size_t)(y * b.w), (size_t)b.w * sizeof(T));
+}
+}  // namespace
+
+// Where in this box are the points: raster_segments, then a raster of at most PCQ_RASTER_CELLS_MAX cells is ONE
+// pcq_scan_dev_raster_batch; a larger one is cut into blocks (raster_blocks), each block the integer sub-box of every file and one
+// launch into its own counter words.  All launches go to the context's stream; the counts are copied back once and scattered.
+// `raster` and `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::count_bounds_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *raster,
+                                            uint64_t *points_scanned) {
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/false, &seg, &cells);
+    if (!st.ok()) return st;
+    const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_RASTER_CELLS_MAX);
     const size_t words = (size_t)(nx * ny);
     std::vector<uint64_t> got(words);
     st = read_counts(words, [&] {
         int rc = PCQ_OK;
-        size_t at = 0;
         std::vector<pcq_predicate> preds(seg.preds.size());
-        for (uint64_t y0 = 0; y0 < ny && !rc && !seg.cols.empty(); y0 += bh) {
-            for (uint64_t x0 = 0; x0 < nx && !rc; x0 += bw) {
-                const uint64_t off[2] = {x0, y0}, ext[2] = {nx - x0 < bw ? nx - x0 : bw, ny - y0 < bh ? ny - y0 : bh};
-                for (size_t i = 0; i < preds.size(); i++) {
-                    pcq_predicate p = seg.preds[i];
-                    for (int a = 0; a < 2; a++) {
-                        const int64_t k = cells[2 * i + a];
-                        p.lmin[a] += (int64_t)off[a] * k;
-                        p.lmax[a] = p.lmin[a] + (int64_t)ext[a] * k - 1;
-                        if (p.lmin[a] > INT32_MAX) p.lmin[0] = 1, p.lmax[0] = 0;  // no stored point can lie in this block: an empty predicate
-                    }
-                    if (p.lmin[0] > p.lmax[0]) p.lmin[1] = 1, p.lmax[1] = 0;
-                    preds[i] = p;
-                }
-                rc = pcq_scan_dev_raster_batch(ctx_, seg.cols.data(), preds.data(), cells.data(), preds.size(), (uint32_t)ext[0], (uint32_t)ext[1],
-                                               counter_ + at, nullptr);
-                at += (size_t)(ext[0] * ext[1]);
-            }
+        for (size_t b = 0; b < blocks.size() && !rc && !seg.cols.empty(); b++) {
+            for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(seg.preds[i], &cells[2 * i], blocks[b]);
+            rc = pcq_scan_dev_raster_batch(ctx_, seg.cols.data(), preds.data(), cells.data(), preds.size(), (uint32_t)blocks[b].w, (uint32_t)blocks[b].h,
+                                           counter_ + blocks[b].at, nullptr);
         }
         return rc;
     }, got.data());
     if (!st.ok()) return st;
-    size_t at = 0;
-    for (uint64_t y0 = 0; y0 < ny; y0 += bh)
-        for (uint64_t x0 = 0; x0 < nx; x0 += bw) {
-            const uint64_t w = nx - x0 < bw ? nx - x0 : bw, h = ny - y0 < bh ? ny - y0 : bh;
-            for (uint64_t y = 0; y < h; y++, at += (size_t)w) memcpy(raster + (y0 + y) * nx + x0, got.data() + at, (size_t)w * 8);
+    scatter_blocks(blocks, got.data(), nx, raster);
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
+}
+
+// How high is this box, cell by cell: raster_segments (with the z lattice rule), then the surviving files in groups of one z
+// lattice — bitwise-equal (scale[2], offset[2]), in the order of their first file: the integers of two lattices are not comparable.
+// Per group the dataset's counter holds nx * ny i32 minima and behind them nx * ny i32 maxima, uploaded as INT32_MAX / INT32_MIN
+// (pcq_device_memset is bytewise); per block of at most PCQ_ZRANGE_CELLS_MAX cells ONE pcq_scan_dev_zrange_raster_batch over the
+// group's files on the context's stream; then one copy back.  The words become world values (Z as f64 * scale[2]) + offset[2], the
+// reference's two-rounding rebuild (last.rs:156-160); that map is non-decreasing in Z for a scale above 0, so a cell's world minimum
+// is the image of its integer minimum whatever the order of the points.  Groups are merged with < and > on f64; a cell no point
+// reached is NaN in both arrays.  `zlo`, `zhi` and `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::bounds_zrange_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, double *zlo, double *zhi,
+                                             uint64_t *points_scanned) {
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, &seg, &cells);
+    if (!st.ok()) return st;
+    const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZRANGE_CELLS_MAX);
+    const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
+    const double nan = std::nan("");
+    std::vector<double> lo(words, nan), hi(words, nan);
+    std::vector<int32_t> preset(2 * words), got(2 * words), zmin(words), zmax_i(words);
+    std::fill(preset.begin(), preset.begin() + words, INT32_MAX);
+    std::fill(preset.begin() + words, preset.end(), INT32_MIN);
+    std::vector<uint8_t> grouped(nseg, 0);
+    for (size_t first = 0; first < nseg; first++) {
+        if (grouped[first]) continue;
+        const double scale = seg.cols[first].scale[2], offset = seg.cols[first].offset[2];
+        Segments grp;
+        std::vector<uint32_t> gcells;
+        for (size_t i = first; i < nseg; i++) {
+            if (grouped[i] || memcmp(&seg.cols[i].scale[2], &scale, 8) || memcmp(&seg.cols[i].offset[2], &offset, 8)) continue;
+            grouped[i] = 1;
+            grp.cols.push_back(seg.cols[i]);
+            grp.preds.push_back(seg.preds[i]);
+            gcells.push_back(cells[2 * i]), gcells.push_back(cells[2 * i + 1]);
         }
+        int rc = ensure_counter(words);  // (2 x words i32)
+        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed may have left launches that write the counter)
+        if (!rc) rc = pcq_copy_to_device(ctx_, counter_, preset.data(), 2 * words * sizeof(int32_t));
+        int32_t *const d_zmin = reinterpret_cast<int32_t *>(counter_), *const d_zmax = d_zmin + words;
+        std::vector<pcq_predicate> preds(grp.preds.size());
+        for (size_t b = 0; b < blocks.size() && !rc; b++) {
+            for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(grp.preds[i], &gcells[2 * i], blocks[b]);
+            rc = pcq_scan_dev_zrange_raster_batch(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(), (uint32_t)blocks[b].w,
+                                                  (uint32_t)blocks[b].h, d_zmin + blocks[b].at, d_zmax + blocks[b].at, nullptr);
+        }
+        if (!rc) rc = pcq_copy_to_host(ctx_, got.data(), counter_, 2 * words * sizeof(int32_t));
+        if (rc) return Status::FromLib(rc);
+        scatter_blocks(blocks, got.data(), nx, zmin.data());
+        scatter_blocks(blocks, got.data() + words, nx, zmax_i.data());
+        for (size_t c = 0; c < words; c++) {
+            if (zmin[c] > zmax_i[c]) continue;  // (no point of this group)
+            const double a = ((double)zmin[c] * scale) + offset, b = ((double)zmax_i[c] * scale) + offset;
+            if (!(lo[c] <= a)) lo[c] = a;  // (NaN: nothing yet)
+            if (!(hi[c] >= b)) hi[c] = b;
+        }
+    }
+    memcpy(zlo, lo.data(), words * sizeof(double));
+    memcpy(zhi, hi.data(), words * sizeof(double));
     if (points_scanned) *points_scanned = seg.scanned;
     return Status::Ok();
 }

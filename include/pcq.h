@@ -310,6 +310,25 @@ int pcq_scan_dev_time_hist_batch(pcq_ctx *ctx, const pcq_columns *cols, const pc
 #define PCQ_RASTER_CELLS_MAX 8192
 int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                               size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_raster, void *stream);
+/* The height raster of a box in ONE pass: "how high is this box, cell by cell?".  Layout, predicate kind, `cell_xy`, the cell rule
+ * and the refusals are those of pcq_scan_dev_raster_batch, word for word; only the limit on nx * ny differs: PCQ_ZRANGE_CELLS_MAX.
+ * A point (X, Y, Z) of segment i inside the box of preds[i] lies in cell c = cy * nx + cx with cx = (X - lmin[0]) / cell_xy[2i] and
+ * cy = (Y - lmin[1]) / cell_xy[2i + 1], exact integer floor divisions.  The call is a FOLD, the counterpart of "the counts are
+ * ADDED": after it device_zmin[c] = min(device_zmin[c] before, the Z of every such point) and device_zmax[c] = max(device_zmax[c]
+ * before, the Z of every such point), signed compares of i32 words, for every cell at once and from one read of the data.  The
+ * caller presets the words: INT32_MAX in device_zmin and INT32_MIN in device_zmax say "nothing yet", and a cell no point reaches
+ * keeps both words.  Z is in the segment's OWN integer lattice: the values of segments whose z scale or z offset differ are NOT
+ * comparable, so a caller batches segments of one z lattice per call (pcq_query_resident_bounds_zrange_raster does).  No word at
+ * or beyond nx * ny of either array is touched.  A predicate that is empty matches nothing and its segment is not evaluated; a
+ * point that fails only the z test of its box contributes nothing.  nsegments == 0 is PCQ_OK after the argument checks.  A null
+ * argument (device_zmin and device_zmax among them), nx == 0, ny == 0 or nx * ny above PCQ_ZRANGE_CELLS_MAX, any other predicate
+ * kind, any other layout, a cell width of 0 in a segment with points, a non-empty predicate whose lmin[0] or lmin[1] lies outside
+ * the i32 range, and a non-empty predicate whose box reaches beyond the raster — (min(lmax[a], INT32_MAX) - lmin[a]) / cell >= n for
+ * a = 0 or 1 — are refused (PCQ_ERR_ARG) before anything is uploaded or launched: both arrays are untouched.  lmax and lmin[2] may
+ * be anywhere. */
+#define PCQ_ZRANGE_CELLS_MAX 4096
+int pcq_scan_dev_zrange_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                                     size_t nsegments, uint32_t nx, uint32_t ny, int32_t *device_zmin, int32_t *device_zmax, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

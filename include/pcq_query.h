@@ -186,6 +186,23 @@ int pcq_query_resident_count_bounds_by_time(pcq_host_resident *r, const double b
 #define PCQ_QUERY_RASTER_CELLS_MAX (1u << 20)
 int pcq_query_resident_count_bounds_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
                                            uint64_t ny, uint64_t *raster, uint64_t *points_scanned);
+/* How high is this box, cell by cell: over the raster of pcq_query_resident_count_bounds_raster — nx x ny cells of cell_size world
+ * units from (bmin[0], bmin[1]), row-major with y upward, the points with z in [bmin[2], zmax] — zlo[cy * nx + cx] is the lowest
+ * and zhi[cy * nx + cx] the highest world z of the points that entry counts in cell (cx, cy); a cell it counts no point in is NaN
+ * in both.  The highest z per cell is a surface model, the lowest a first ground model, their difference a height above ground.
+ * The checks are that entry's, in its order and before the dataset or a device is touched: a null r, bmin, zlo or zhi is
+ * PCQ_ERR_ARG; nx * ny == 0 is PCQ_OK with nothing written; nx * ny above PCQ_QUERY_RASTER_CELLS_MAX is PCQ_ERR_ARG; a cell_size
+ * that is not finite or not above 0 is PCQ_ERR_ARG.  The per-file prologue is that entry's too — the header early-out,
+ * pcq_box_to_local bug for bug, PCQ_ERR_PANIC for bmin[2] > zmax, PCQ_ERR_UNSUPPORTED naming the file for a cell that is no whole
+ * number of its lattice steps — and one rule more: a surviving file whose scale[2] is not finite or not above 0 is
+ * PCQ_ERR_UNSUPPORTED naming the file.  World z is (Z as f64 * scale[2]) + offset[2] of the stored integer Z, the value a record
+ * of pcq_query_resident_search_bounds carries; it does not decrease with Z, so the results are those of a min / max over these
+ * records' z, bit for bit.  The surviving files are scanned in groups of one z lattice (bitwise-equal scale[2] and offset[2]):
+ * per group and per block of at most PCQ_ZRANGE_CELLS_MAX cells (pcq.h) ONE pcq_scan_dev_zrange_raster_batch over the positions of
+ * the group's files; the groups are merged on the host.  points_scanned (NULL: not wanted): what
+ * pcq_query_resident_count_bounds_raster reports.  On any failure zlo, zhi and points_scanned are left as they were. */
+int pcq_query_resident_bounds_zrange_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
+                                            uint64_t ny, double *zlo, double *zhi, uint64_t *points_scanned);
 /* == pcq_query_search_file_bounds_time(path, bmin, bmax, start, end, optimized=1, c) for every loaded file, in load order, into
  * ONE collector: the same count, the same records byte for byte and in order (class 0, colour (0,0,0), whether or not colour
  * blocks are loaded), the same grid cells and winners; the header early-out leaves the collector's file-order index where it

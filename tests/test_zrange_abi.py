@@ -1,0 +1,93 @@
+"""The height raster of a box: the libpcq entry (include/pcq.h: pcq_scan_dev_zrange_raster_batch) and the host entry
+(include/pcq_query.h: pcq_query_resident_bounds_zrange_raster) are declared and exported beside the old batch entries with the launch
+limit, the binding has the method, the ABI number is what it was, and the host entry makes its argument checks, in the density
+raster's order, before any device is touched — from python, and from a stand-alone driver built with ASan and UBSan
+(tests/native/zrange_asan_driver.cpp).  No GPU call."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+PCQ_ERR_ARG = -8
+LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
+           "pcq_scan_dev_count_batch_multi", "pcq_scan_dev_class_hist_batch", "pcq_scan_dev_time_hist_batch", "pcq_scan_dev_raster_batch"]
+QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
+             "pcq_query_resident_count_bounds_many", "pcq_query_resident_count_bounds_by_class", "pcq_query_resident_count_bounds_by_time",
+             "pcq_query_resident_count_bounds_raster"]
+
+
+def test_both_entries_are_declared_and_exported_beside_the_old_ones():
+    declared = pkg.declared_symbols(["pcq.h"])
+    exported = pkg.exported_symbols(pkg.lib_path())
+    for name in ["pcq_scan_dev_zrange_raster_batch"] + LIB_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    declared = pkg.declared_symbols(["pcq_query.h"])
+    exported = pkg.exported_symbols(os.path.join(PKG, "libpcq_query.so"))
+    for name in ["pcq_query_resident_bounds_zrange_raster"] + QUERY_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    with open(os.path.join(ROOT, "include", "pcq.h")) as f:
+        text = f.read()
+    assert "#define PCQ_ZRANGE_CELLS_MAX 4096" in text and "#define PCQ_RASTER_CELLS_MAX 8192" in text
+
+
+def test_abi_number_is_unchanged_and_the_binding_has_the_method():
+    assert pkg.load_library().pcq_abi_version() == 6
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    assert callable(binding.Context.scan_dev_zrange_raster_batch)
+    assert callable(binding.Context.scan_dev_raster_batch) and callable(binding.Context.scan_dev_time_hist_batch)
+
+
+def test_host_entry_checks_its_arguments_without_a_device():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    f = lib.pcq_query_resident_bounds_zrange_raster
+    f.argtypes = [C.c_void_p, dd, C.c_double, C.c_double, C.c_uint64, C.c_uint64, dd, dd, u64p]
+    dummy = C.c_void_p(1)  # never dereferenced: a check refuses first
+    lo = (C.c_double * 3)(0, 0, 0)
+    s_lo, s_hi = [1000.5 + 7 * c for c in range(64)], [-3.25 - c for c in range(64)]
+    zlo, zhi = (C.c_double * 64)(*s_lo), (C.c_double * 64)(*s_hi)
+    s = C.c_uint64(15)
+    inf, nan = float("inf"), float("nan")
+    for args, text in (((None, lo, 10.0, 1.0, 8, 8, zlo, zhi), b"null argument"), ((dummy, None, 10.0, 1.0, 8, 8, zlo, zhi), b"null argument"),
+                       ((dummy, lo, 10.0, 1.0, 8, 8, None, zhi), b"null argument"), ((dummy, lo, 10.0, 1.0, 8, 8, zlo, None), b"null argument"),
+                       ((None, None, 10.0, 1.0, 0, 0, None, None), b"null argument"),
+                       ((dummy, lo, 10.0, 1.0, 1025, 1024, zlo, zhi), b"cells"), ((dummy, lo, 10.0, 1.0, 2**20 + 1, 1, zlo, zhi), b"cells"),
+                       ((dummy, lo, 10.0, 1.0, 2**32, 2**32, zlo, zhi), b"cells"), ((dummy, lo, 10.0, 1.0, 2**64 - 1, 2**64 - 1, zlo, zhi), b"cells"),
+                       ((dummy, lo, 10.0, 0.0, 8, 8, zlo, zhi), b"cell_size"), ((dummy, lo, 10.0, -0.5, 8, 8, zlo, zhi), b"cell_size"),
+                       ((dummy, lo, 10.0, inf, 8, 8, zlo, zhi), b"cell_size"), ((dummy, lo, 10.0, nan, 8, 8, zlo, zhi), b"cell_size")):
+        for scanned in (C.byref(s), None):
+            assert f(*args, scanned) == PCQ_ERR_ARG, args
+            assert text in lib.pcq_query_last_error(), (args, lib.pcq_query_last_error())
+            assert list(zlo) == s_lo and list(zhi) == s_hi and s.value == 15
+    # a null output comes before the number of cells, the number of cells before the cell size
+    assert f(dummy, lo, 10.0, nan, 2**32, 2**32, None, zhi, None) == PCQ_ERR_ARG and b"null argument" in lib.pcq_query_last_error()
+    assert f(dummy, lo, 10.0, nan, 2**32, 2**32, zlo, zhi, None) == PCQ_ERR_ARG and b"cells" in lib.pcq_query_last_error()
+    # nx * ny == 0 comes before the cell size and the number of cells: PCQ_OK, nothing written
+    for nx, ny in ((0, 8), (8, 0), (0, 0), (0, 2**64 - 1)):
+        assert f(dummy, lo, 10.0, nan, nx, ny, zlo, zhi, C.byref(s)) == 0
+        assert list(zlo) == s_lo and list(zhi) == s_hi and s.value == 15
+
+
+def test_host_entry_under_address_sanitizer(tmp_path):
+    """The argument checks of the new host entry under ASan + UBSan, through a stand-alone program (nothing sanitized is loaded
+    into python; no device is touched).  The two translation units the entry lives in — capi.cpp and resident.cpp — are built
+    sanitized into the program, where their definitions come first; the rest of the host layer is the libpcq_query.so beside
+    them, which keeps the build to a few seconds."""
+    host = os.path.join(PKG, "host")
+    exe = str(tmp_path / "zrange_asan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
+           "-I" + os.path.join(ROOT, "include"), "-I" + host, os.path.join(ROOT, "tests", "native", "zrange_asan_driver.cpp"),
+           os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG, "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
+    assert r.stdout.split() == ["ok", "30", "4"]

@@ -1,0 +1,235 @@
+"""Developer tool: the height raster of a box on resident data — one pass that folds the z of every point inside the box into the
+min and the max of its cell of an nx x ny raster over x and y.
+
+(i)   FILES resident synthetic files of N points each (the 4 x 4 tiles of synth_ca13), twice: (g) in the generator's order (random
+      inside a tile) and (s) in scan-strip order (strips 10 m wide in y and z, points sorted along x: the lanes of a wave mostly
+      share a cell).  The ca13_XL box with z unbounded, which keeps every point.  Rasters of 8 x 8, 64 x 64 and 128 x 32 cells (the
+      last two: PCQ_ZRANGE_CELLS_MAX) over the box's x and y.  Per order and raster two routes, timed with device events around
+      the whole of each, alternated in one process, REPS rounds after 3 warm-up rounds; median, minimum and maximum, TB/s on
+      12 B/point:
+        zrange    ONE pcq_scan_dev_zrange_raster_batch, its words preset by two fills;
+        raster    ONE pcq_scan_dev_raster_batch at the same cells: the floor — the same loads and divisions, one LDS add per
+                  point instead of a min and a max.
+      The cells the height raster reaches must be the cells the density raster counts in, and g and s must agree.
+(ii)  (not with PCQ_LAB=1) the same 16 tiles as LAST files of NB points each in a resident dataset of the host layer
+      (pcq_query_resident_load_points), and a box of one sixteenth of the set's x-y extent — tile (1, 1) — with z unbounded, 64 x 64
+      cells: pcq_query_resident_bounds_zrange_raster against the only other route to the answer, pcq_query_resident_search_bounds
+      into a buffer collector and pcq_query_collector_points to host memory (the host-side binning of the records is not timed).
+      Wall time of the whole of each (these entries wait for their answer themselves), alternated the same way.  The records'
+      z, binned here with numpy, must give the same min and max per cell, bit for bit.
+      Rule: the one pass's slowest round is below that route's fastest round.
+(iii) with PCQ_LAB=1 (libpcq_lab.so accepts the option "zrange_waves_per_cu"): the one pass of (i) at 2 .. 16 workgroups per CU
+      before the LDS limit (160 KiB / (8 nx ny): 5 at 4096 cells).
+The last line restates the checks.
+usage: resident_zrange_rate.py [N [FILES [REPS [NB]]]]"""
+import ctypes as C
+import importlib, json, os, shutil, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import torch
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+specs = importlib.import_module("adhoc-queries-pointclouds_amd.synth_specs")
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 163_000_000
+files = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+reps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+nb = int(sys.argv[4]) if len(sys.argv) > 4 else n
+dev = torch.device("cuda:0")
+ts = torch.cuda.Stream(); torch.cuda.set_stream(ts); stream = ts.cuda_stream
+lab = os.environ.get("PCQ_LAB") == "1"
+RASTERS = ((8, 8), (64, 64), (128, 32))
+I32_MIN, I32_MAX = -2**31, 2**31 - 1
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median_ms": v[len(v) // 2], "min_ms": v[0], "max_ms": v[-1], "reps": len(v)}
+
+
+def alternate(fns, reps, warm=3, events=True):
+    """fns: name -> callable; one of each per round, device events (or the wall clock) around each, the first `warm` rounds dropped"""
+    times = {k: [] for k in fns}
+    for it in range(reps + warm):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            if events:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record(); e1.synchronize()
+                ms = e0.elapsed_time(e1)
+            else:
+                t0 = time.perf_counter()
+                fn()
+                ms = (time.perf_counter() - t0) * 1e3
+            if it >= warm:
+                times[k].append(ms)
+    return {k: spread(v) for k, v in times.items()}
+
+
+def tbps(points, ms):
+    return points * 12 / (ms * 1e-3) / 1e12
+
+
+checks = {}
+with pkg.Context(0) as ctx:
+    # ---- (i) one pass against the density raster's pass, (iii) at other grids ------------------------------------------
+    tiles = specs.synth_ca13(points_per_file=n, files=files)
+    bmin, bmax = specs.box("ca13_XL")
+    keep, cols = [], {"g": [], "s": []}
+    for spec in tiles:
+        raw = torch.empty(n * 3, dtype=torch.int32, device=dev)
+        ctx.synth_fill(spec, 0, n, raw.data_ptr(), None, stream)
+        torch.cuda.synchronize()
+        t = raw.view(n, 3)
+        width, zwidth = int(10.0 / spec.scale[1]), int(10.0 / spec.scale[2])
+        key = ((t[:, 1].long() // width) * 4096 + (t[:, 2].long() // zwidth + 2048)) * (1 << 32) + (t[:, 0].long() + (1 << 31))
+        order = torch.argsort(key)
+        del key
+        strips = t[order].contiguous().view(-1)
+        del order
+        keep += [raw, strips]
+        for name, buf in (("g", raw), ("s", strips)):
+            assert buf.data_ptr() % 16 == 0
+            cols[name].append(binding.make_columns(xyz=buf.data_ptr(), n=n, scale=list(spec.scale), offset=list(spec.offset)))
+    torch.cuda.synchronize()
+    # every tile has the scale and offset of the first: one local box, one lattice (x, y and z)
+    lmin, lmax = pkg.box_to_local(bmin, bmax, list(tiles[0].scale), list(tiles[0].offset))
+    assert all(pkg.box_to_local(bmin, bmax, list(s.scale), list(s.offset)) == (lmin, lmax) for s in tiles)
+    zmin = torch.zeros(4096, dtype=torch.int32, device=dev)
+    zmax = torch.zeros(4096, dtype=torch.int32, device=dev)
+    out = torch.zeros(4096, dtype=torch.int64, device=dev)
+    points = files * n
+    for nx, ny in RASTERS:
+        cw = [-(-(lmax[a] - lmin[a] + 1) // d) for a, d in ((0, nx), (1, ny))]
+        lo, hi = [lmin[0], lmin[1], -2**40], [lmin[0] + nx * cw[0] - 1, lmin[1] + ny * cw[1] - 1, 2**40]
+        preds = [pkg.Predicate.bounds(lo, hi)] * files
+        cells = [cw] * files
+        seen = {}
+        for order in ("g", "s"):
+            c = cols[order]
+
+            def zrange():
+                zmin.fill_(I32_MAX); zmax.fill_(I32_MIN)
+                ctx.scan_dev_zrange_raster_batch(c, preds, cells, nx, ny, zmin.data_ptr(), zmax.data_ptr(), stream)
+
+            def raster():
+                out.zero_()
+                ctx.scan_dev_raster_batch(c, preds, cells, nx, ny, out.data_ptr(), stream)
+
+            zrange(); raster()
+            torch.cuda.synchronize()
+            got = (zmin[:nx * ny].clone(), zmax[:nx * ny].clone())
+            ras = out[:nx * ny].clone()
+            tag = f"{nx}x{ny}_{order}"
+            checks[f"{tag}_reaches_the_counted_cells"] = bool(((got[0] <= got[1]) == (ras > 0)).all()) and int(ras.sum()) == points
+            seen[order] = got
+            if not lab:
+                res = alternate({"zrange": zrange, "raster": raster}, reps)
+                for k in res:
+                    res[k]["TBps_12B_per_point"] = tbps(points, res[k]["median_ms"])
+                print("(i)", json.dumps({"nx_ny": [nx, ny], "order": order, "files": files, "points_per_file": n, "cells_hit": int((ras > 0).sum()),
+                                          "largest_cell": int(ras.max()), "z_lowest": int(got[0].min()), "z_highest": int(got[1].max()),
+                                          "zrange_over_raster": res["zrange"]["median_ms"] / res["raster"]["median_ms"], **res}), flush=True)
+            else:
+                sweep = {}
+                for w in (2, 3, 4, 5, 6, 8, 12, 16):
+                    ctx.set_option("zrange_waves_per_cu", w)
+                    r = alternate({"zrange": zrange}, max(3, reps // 2), warm=1)["zrange"]
+                    torch.cuda.synchronize()
+                    assert torch.equal(zmin[:nx * ny], got[0]) and torch.equal(zmax[:nx * ny], got[1]), w
+                    sweep[f"w{w}"] = [round(r["median_ms"], 3), round(r["min_ms"], 3), round(r["max_ms"], 3)]
+                ctx.set_option("zrange_waves_per_cu", 0)
+                r = alternate({"zrange": zrange}, max(3, reps // 2), warm=1)["zrange"]
+                sweep["shipped"] = [round(r["median_ms"], 3), round(r["min_ms"], 3), round(r["max_ms"], 3)]
+                print("(iii)", json.dumps({"nx_ny": [nx, ny], "order": order, "lds_limit_waves_per_cu": 160 * 1024 // (8 * nx * ny),
+                                            "median_min_max_ms": sweep}), flush=True)
+        checks[f"{nx}x{ny}_orders_agree"] = all(torch.equal(a, b) for a, b in zip(seen["g"], seen["s"]))
+    del keep, cols, zmin, zmax, out
+    torch.cuda.empty_cache()
+if lab:
+    print("checks", json.dumps(checks), flush=True)
+    sys.exit(0)
+
+# ---- (ii) the host entry against a search into a buffer collector and the copy of its records -----------------------------
+import _oracle  # only to WRITE the synthetic files (the generator lives in the oracle)
+d = tempfile.mkdtemp(prefix="pcq_zrange_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+try:
+    oracle = _oracle.Oracle()
+    tiles = specs.synth_ca13(points_per_file=nb, files=16)
+    paths = []
+    t0 = time.perf_counter()
+    for i, s in enumerate(tiles):
+        p = os.path.join(d, f"ca13_{i}.last")
+        oracle.synth_write(s, p, threads=16)
+        paths.append(p)
+    t1 = time.perf_counter()
+    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
+    vp, dd, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    lib.pcq_query_resident_load_points.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(vp)]
+    lib.pcq_query_resident_free.argtypes = [vp]
+    lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, C.c_double, C.c_double, C.c_uint64, C.c_uint64, dd, dd, u64p]
+    lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
+    lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.pcq_query_collector_free.argtypes = [vp]
+    lib.pcq_query_collector_points.argtypes = [vp, vp, C.c_uint64, u64p]
+    arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+    h = vp()
+    assert lib.pcq_query_resident_load_points(0, arr, len(paths), C.byref(h)) == 0, lib.pcq_query_last_error()
+    print(f"(ii) wrote 16 files x {nb} points in {t1 - t0:.1f} s, loaded in {time.perf_counter() - t1:.1f} s", flush=True)
+    # tile (1, 1): 64 x 64 cells of 36515 lattice steps of 0.01 m cover 23369.6 of its 23369.8 m; the origin half a step inside it, so
+    # that the truncating conversion to the lattice lands on the tile's first value
+    s = tiles[5]
+    k, nx, ny = 36515, 64, 64
+    cell = k * 0.01
+    assert nx * k <= s.span[0] and ny * k <= s.span[1] and s.scale[0] == s.scale[1] == s.scale[2] == 0.01 and s.offset[2] == 0.0
+    lo = (s.lo[0] * 0.01 + 0.005, s.lo[1] * 0.01 + 0.005, -1e9)
+    hi = (lo[0] + nx * cell, lo[1] + ny * cell, 1e9)
+    c_lo, c_hi = (C.c_double * 3)(*lo), (C.c_double * 3)(*hi)
+    zlo, zhi = np.zeros(nx * ny), np.zeros(nx * ny)
+    scanned = C.c_uint64()
+    cap = nb + 1024
+    records = np.zeros(cap, dtype=pkg.POINT_DTYPE)
+    got_n = C.c_uint64()
+
+    def one_pass():
+        assert lib.pcq_query_resident_bounds_zrange_raster(h, c_lo, 1e9, cell, nx, ny, zlo.ctypes.data_as(dd), zhi.ctypes.data_as(dd),
+                                                           C.byref(scanned)) == 0, lib.pcq_query_last_error()
+
+    def search_and_copy():
+        coll = vp()
+        assert lib.pcq_query_collector_new_buffer(0, C.byref(coll)) == 0, lib.pcq_query_last_error()
+        try:
+            assert lib.pcq_query_resident_search_bounds(h, c_lo, c_hi, coll) == 0, lib.pcq_query_last_error()
+            assert lib.pcq_query_collector_points(coll, records.ctypes.data_as(vp), cap, C.byref(got_n)) == 0, lib.pcq_query_last_error()
+        finally:
+            lib.pcq_query_collector_free(coll)
+
+    one_pass(); search_and_copy()
+    # the records binned on the host: the stored integers back from world x and y (scale 0.01, offset 0: exact below 2^31), the cell
+    # from the lattice origin the prologue gives, the records beyond the last full cell dropped
+    lmin, _ = pkg.box_to_local(list(lo), list(hi), list(s.scale), list(s.offset))
+    r = records[:got_n.value]
+    cx = (np.rint(r["x"] / 0.01).astype(np.int64) - lmin[0]) // k
+    cy = (np.rint(r["y"] / 0.01).astype(np.int64) - lmin[1]) // k
+    sel = (cx >= 0) & (cx < nx) & (cy >= 0) & (cy < ny)
+    rlo, rhi = np.full(nx * ny, np.nan), np.full(nx * ny, np.nan)
+    np.fmin.at(rlo, (cy * nx + cx)[sel], r["z"][sel])
+    np.fmax.at(rhi, (cy * nx + cx)[sel], r["z"][sel])
+    checks["host_routes_agree_bit_for_bit"] = bool(np.array_equal(rlo.view(np.uint64), zlo.view(np.uint64)) and
+                                                   np.array_equal(rhi.view(np.uint64), zhi.view(np.uint64)))
+    res = alternate({"one_pass": one_pass, "search_and_copy": search_and_copy}, reps, events=False)
+    checks["host_one_pass_faster_beyond_spread"] = res["one_pass"]["max_ms"] < res["search_and_copy"]["min_ms"]
+    checks["host_speedup"] = res["search_and_copy"]["median_ms"] / res["one_pass"]["median_ms"]
+    print("(ii)", json.dumps({"box": [list(lo), list(hi)], "nx_ny": [nx, ny], "cell_size": cell, "points_per_file": nb, "points_scanned": scanned.value,
+                              "records": got_n.value, "record_bytes": got_n.value * 31, "records_in_cells": int(sel.sum()),
+                              "cells_hit": int((~np.isnan(zlo)).sum()), "z_lowest": float(np.nanmin(zlo)), "z_highest": float(np.nanmax(zhi)),
+                              "speedup": checks["host_speedup"], **res}), flush=True)
+    lib.pcq_query_resident_free(h)
+finally:
+    shutil.rmtree(d, ignore_errors=True)
+print("checks", json.dumps(checks), flush=True)
