@@ -15,6 +15,7 @@
 
 #include "pcq.h"
 #include "stage_plan.h"  // the predicate-kind helpers (pred_has_box, ...), the collector kinds, what a scan reads
+#include "index_plan.h"  // the chunk sizes of the index (INDEX_BOUNDS_CHUNK, ...), what an indexed scan of each kind prunes with
 
 // ---------------------------------------------------------------------------------------------
 // error plumbing
@@ -194,7 +195,6 @@ struct EmitIndex {
     uint64_t covered_tiles;
 };
 enum { CHUNK_SCAN = 0, CHUNK_NONE = 1, CHUNK_ALL = 2 };  // straddling: read it · disjoint: no match · contained: every point matches
-constexpr uint64_t INDEX_BOUNDS_CHUNK = 4096, INDEX_CLASS_CHUNK = 65536, EMIT_TILE_POINTS = 2048;
 // A chunk's integer AABB against the predicate's inclusive i64 box [lo, lo + width] (pred.empty: nothing matches).
 __device__ __forceinline__ int index_box_state(const int32_t (&mn)[3], const int32_t (&mx)[3], const DevPred &pr) {
     bool disjoint = pr.empty != 0, inside = !pr.empty;

@@ -109,8 +109,11 @@ template <>
 struct Col2Regs<COL_F64> {
     v4i a, b;
 };
+__device__ __forceinline__ double time_of(int lo, int hi) {  // the f64 whose two dwords a load delivered
+    return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+}
 __device__ __forceinline__ bool t_in(int lo, int hi, double t0, double t1) {
-    const double t = __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+    const double t = time_of(lo, hi);
     return (t >= t0) & (t < t1);  // Range<f64>::contains: NaN is no match
 }
 __device__ __forceinline__ uint32_t verdict_word(const Col2Regs<COL_U8> &r, const Col2<COL_U8> &c) {

@@ -88,10 +88,6 @@ __device__ __forceinline__ TimeLanes time_lanes(int lane) {
     return h;
 }
 
-__device__ __forceinline__ double time_of(int lo, int hi) {
-    return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
 // The launch's edges as a wave sees them.
 struct EdgeTable {
     const double *tab;  // LDS: the interior edges, +inf behind them

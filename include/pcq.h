@@ -342,8 +342,9 @@ int pcq_scan_dev_zrange_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, cons
  * emit's count pass reads neither the positions nor the class bytes of a disjoint or contained
  * chunk (a disjoint one is then skipped by the emit as well; a contained one is read once, for its
  * records), and the ragged tail behind the last whole bounds chunk is always read.  Results are
- * identical to pcq_scan_dev; layouts the index does not cover fall through to it: strided / LAS
- * columns, positions not 16-byte aligned or fewer than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME,
+ * identical to pcq_scan_dev; layouts the index does not cover fall through to pcq_scan_dev with all-zero
+ * statistics and leave the index untouched: strided / LAS columns, positions not 16-byte aligned or fewer
+ * than 4096 points (bounds), cls_stride != 1 (class).  PCQ_PRED_TIME,
  * PCQ_PRED_BOUNDS_CLASS, PCQ_PRED_BOUNDS_TIME and PCQ_PRED_BOUNDS_F64 have no index: they are served by pcq_scan_dev, the
  * statistics of such a scan are all zero, and the index is neither built nor changed by it.
  * Statistics of the last scan, in index chunks: for a count scan what it read; for a buffer scan the

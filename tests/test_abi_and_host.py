@@ -384,6 +384,25 @@ def test_staging_plan_of_the_host_scans(tmp_path):
     assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-500:], r.stderr[-3000:])
 
 
+def test_plan_of_the_indexed_scans(tmp_path):
+    """csrc/index_plan.h decides what an indexed scan of each predicate kind prunes with: the parts, the layouts they cover, the
+    chunk counts, the tiles the buffer emit takes from the index, the columns of the ragged tail.  Pure host arithmetic,
+    compiled with g++ alone under AddressSanitizer and UBSan: every kind at the edges of its layouts, and the tails against
+    numbers worked out by hand (tests/native/index_plan_driver.cpp)."""
+    import shutil
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "index_plan")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "native", "index_plan_driver.cpp"), "-o", exe], capture_output=True, text=True)
+    if r.returncode != 0 and "sanitize" in r.stderr and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_every_entry_point_runs_on_the_context_device():
     """A driver thread that never chose a device sits on device 0; draining the collectors of GPU k from it must
     still allocate and launch on GPU k.  Every extern "C" function that takes a context, a collector or an index
