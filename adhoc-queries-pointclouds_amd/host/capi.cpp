@@ -198,7 +198,7 @@ extern "C" int pcq_query_test_plan_replace_execute(const char *path, const char 
     AABB b;
     Status st = AABB::from_min_max(bmin, bmax, &b);
     if (!st.ok()) return done(st);
-    FilePlan plan = plan_last_file_by_bounds_optimized(path, b);
+    FilePlan plan = plan_file(path, FileLayout::LAST, Query{PCQ_PRED_BOUNDS, b, 0, 0.0, 0.0});
     if (replacement && ::rename(replacement, path) != 0) return done(Status::Err(PCQ_ERR_IO, std::string("rename: ") + strerror(errno)));
     return done(execute_plan(plan, *c->c));
 }

@@ -173,27 +173,37 @@ struct FilePlan {
     pcq_columns cols{};          // the column "pointers" are byte offsets into the file (pcq_scan_fd)
     pcq_predicate pred{};
 };
-FilePlan plan_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds);
-// (header: when not NULL, the parsed header — valid when the plan's status is OK; the combined plans read its bounds)
-FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header = nullptr);
-FilePlan plan_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds);
-FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header = nullptr);
+// One query over a file: the predicate's kind (PCQ_PRED_BOUNDS, _CLASS, _TIME, _BOUNDS_CLASS, _BOUNDS_TIME) and the values that kind
+// reads — the box; the class byte; GPS time in [start, end) (Range<f64>::contains, las.rs:336).  The two combined kinds (--combine)
+// are not in the reference.
+struct Query {
+    int kind = PCQ_PRED_BOUNDS;
+    AABB box{};
+    uint8_t cls = 0;
+    double start = 0, end = 0;
+};
+enum class FileLayout { LAS, LAST };  // records (las.rs) or the record transposed by attribute (last.rs, last_reader.rs:83-144)
+// Where the columns the searches read lie in a file.  An attribute at `in_point` of a record is, in a LAS file, a column from
+// offset_to_point_data + in_point with the record length as stride; in a LAST file a packed block from offset_to_point_data +
+// n * in_point.  `size`: the bytes of one element (the stride of a LAST block).
+struct FileColumn {
+    bool present = false;
+    uint64_t offset = 0, stride = 0, size = 0;
+};
+struct ColumnLayout {
+    FileColumn xyz, cls, rgb, time;  // rgb: formats 2, 3, 5; time: every format but 0 and 2
+    uint64_t record_length = 0;      // LAS
+};
+ColumnLayout column_layout(const LasHeader &h, FileLayout layout);  // (h: a parsed header, its format 0..10)
+FilePlan plan_file(const std::string &path, FileLayout layout, const Query &query);  // the prologue of search_{las,last}_file_by_*_optimized
 Status execute_plan(FilePlan &plan, ResultCollector &rc);  // the per-point loop: pcq_scan_fd into the collector
-Status search_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc);
-Status search_last_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
-Status search_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc, SearchLog *log);
-Status search_las_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc);
-// GPS time in [start, end) (Range<f64>::contains): las.rs:297-358; the LAST form reads the transposed time block
-FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header = nullptr);
-FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header = nullptr);
-Status search_las_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
-Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc);
-// The box AND a class byte / a GPS time range (--combine; not in the reference): the attribute search's plan
-// and records, then the bounds search's header early-out and box
-FilePlan plan_las_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls);
-FilePlan plan_last_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls);
-FilePlan plan_las_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end);
-FilePlan plan_last_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end);
+// The host-only part of ResidentDataset::load for one file: the header and where the blocks to load lie (rgb, time: 0 when that
+// block is not loaded).  `file` is opened here and stays open for the reads.
+struct ResidentBlocks {
+    LasHeader header;
+    uint64_t xyz = 0, cls = 0, rgb = 0, time = 0;
+};
+Status resident_file_blocks(const std::string &path, bool with_points, bool with_times, MappedFile *file, ResidentBlocks *out);
 // search/lazer.rs:34-116 over readers/src/lazer_reader.rs (one implementation for both --optimized settings)
 Status search_lazer_file_by_bounds(const std::string &path, const AABB &bounds, ResultCollector &rc);
 Status search_lazer_file_by_classification(const std::string &path, uint8_t cls, ResultCollector &rc);
@@ -202,67 +212,35 @@ Status lazer_file_bounds(const std::string &path, AABB *out);  // LAZERSource::f
 // ---- search/searcher.rs ----------------------------------------------------------------------------
 enum class SearchImplementation { Regular, Optimized };
 
+// One searcher over the query value; the reference's two structs and the three that are not in its searcher.rs construct it.
 class Searcher {
 public:
     virtual ~Searcher() = default;
-    virtual Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                               SearchLog *log = nullptr) const = 0;
+    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *log = nullptr) const;
     // the host-only part of search_file where there is one (nullopt: search_file does everything)
-    virtual std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const = 0;
-};
-class BoundsSearcher : public Searcher {
-public:
-    explicit BoundsSearcher(const AABB &bounds) : bounds_(bounds) {}
-    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                       SearchLog *log = nullptr) const override;
-    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
+    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const;
+
+protected:
+    explicit Searcher(const Query &query) : query_(query) {}
 
 private:
-    AABB bounds_;
+    Query query_;
 };
-class ClassSearcher : public Searcher {
-public:
-    explicit ClassSearcher(uint8_t cls) : class_(cls) {}
-    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                       SearchLog *log = nullptr) const override;
-    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
-
-private:
-    uint8_t class_;
+struct BoundsSearcher : Searcher {
+    explicit BoundsSearcher(const AABB &bounds) : Searcher({PCQ_PRED_BOUNDS, bounds, 0, 0, 0}) {}
 };
-// Not wired into the reference's searcher.rs (its time searches are unused there): GPS time in [start, end)
-class TimeSearcher : public Searcher {
-public:
-    TimeSearcher(double start, double end) : start_(start), end_(end) {}
-    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                       SearchLog *log = nullptr) const override;
-    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
-
-private:
-    double start_, end_;
+struct ClassSearcher : Searcher {
+    explicit ClassSearcher(uint8_t cls) : Searcher({PCQ_PRED_CLASS, {}, cls, 0, 0}) {}
 };
-// --combine: a point matches when both single searches would match it (PCQ_PRED_BOUNDS_CLASS / PCQ_PRED_BOUNDS_TIME)
-class BoundsClassSearcher : public Searcher {
-public:
-    BoundsClassSearcher(const AABB &bounds, uint8_t cls) : bounds_(bounds), class_(cls) {}
-    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                       SearchLog *log = nullptr) const override;
-    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
-
-private:
-    AABB bounds_;
-    uint8_t class_;
+struct TimeSearcher : Searcher {  // GPS time in [start, end)
+    TimeSearcher(double start, double end) : Searcher({PCQ_PRED_TIME, {}, 0, start, end}) {}
 };
-class BoundsTimeSearcher : public Searcher {
-public:
-    BoundsTimeSearcher(const AABB &bounds, double start, double end) : bounds_(bounds), start_(start), end_(end) {}
-    Status search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                       SearchLog *log = nullptr) const override;
-    std::optional<FilePlan> plan_file(const std::string &path, SearchImplementation impl) const override;
-
-private:
-    AABB bounds_;
-    double start_, end_;
+// --combine: a point matches when both single searches would match it
+struct BoundsClassSearcher : Searcher {
+    BoundsClassSearcher(const AABB &bounds, uint8_t cls) : Searcher({PCQ_PRED_BOUNDS_CLASS, bounds, cls, 0, 0}) {}
+};
+struct BoundsTimeSearcher : Searcher {
+    BoundsTimeSearcher(const AABB &bounds, double start, double end) : Searcher({PCQ_PRED_BOUNDS_TIME, bounds, 0, start, end}) {}
 };
 
 // ---- dump_points.rs ----------------------------------------------------------------------------------

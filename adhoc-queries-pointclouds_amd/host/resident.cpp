@@ -53,10 +53,10 @@ ResidentDataset::~ResidentDataset() {
     if (counter_) pcq_device_free(ctx_, counter_);
 }
 
-// Loads the positions and classification blocks of every .last file (last.rs:68-90 for the offsets) into HBM.
+// Loads the positions and classification blocks of every .last file into HBM; where they lie, and what fails before a byte is
+// loaded, is resident_file_blocks (search.cpp).
 // with_points: the colour block as well (last.rs:83-90), for the records of buffer and grid collectors.
-// with_times: the GPS time block as well, where the LAST time search finds it — its plan (search.cpp) is made first, so a file
-// fails here as it fails there: no GPS times (formats 0, 2), a format above 10, a block that reaches past the file.
+// with_times: the GPS time block as well, where the LAST time search finds it.
 Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths, std::unique_ptr<ResidentDataset> *out, bool with_points,
                              bool with_times) {
     auto ds = std::unique_ptr<ResidentDataset>(new ResidentDataset());
@@ -68,30 +68,14 @@ Status ResidentDataset::load(pcq_ctx *ctx, const std::vector<std::string> &paths
     if (!st.ok()) return st;
     ds->counter_ = (uint64_t *)p;
     for (const auto &path : paths) {
-        if (path.size() < 5 || path.compare(path.size() - 5, 5, ".last") != 0)
-            return Status::Err(PCQ_ERR_EXTENSION, "resident datasets hold LAST files: " + path);
-        uint64_t time_block = 0;
-        if (with_times) {
-            FilePlan plan = plan_last_file_by_time_range_optimized(path, 0.0, 0.0);
-            if (!plan.status.ok()) return plan.status;
-            time_block = (uint64_t)(uintptr_t)plan.cols.cls;  // (a plan's column pointers are file offsets; a file of 0 points has none)
-        }
         MappedFile file;
-        st = file.open(path);
+        ResidentBlocks b;
+        st = resident_file_blocks(path, with_points, with_times, &file, &b);
         if (!st.ok()) return st;
         ResidentFile rf;
-        st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, &rf.header);  // last.rs:53-54
-        if (!st.ok()) return st;
-        const uint8_t fmt = rf.header.point_data_record_format & 0x0F;
-        if (fmt > 10) return Status::Err(PCQ_ERR_FORMAT, "Invalid LAS format " + std::to_string(fmt) + " in file " + path);
-        const uint64_t n = rf.header.number_of_points, otp = rf.header.offset_to_point_data;
-        const uint64_t cls_block = otp + n * (fmt <= 5 ? 15 : 16);  // last.rs:69-81
-        if (otp > file.size() || n * 12 > file.size() - otp || cls_block > file.size() || n > file.size() - cls_block)
-            return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer");
-        const uint64_t col_in_point = fmt == 2 ? 20 : (fmt == 3 || fmt == 5 ? 28 : 0);  // last.rs:83-88
-        const uint64_t col_block = otp + n * col_in_point;
-        const bool colours = with_points && col_in_point;
-        if (colours && (col_block > file.size() || n * 6 > file.size() - col_block)) return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer");
+        rf.header = b.header;
+        const uint64_t n = rf.header.number_of_points, otp = b.xyz, cls_block = b.cls, col_block = b.rgb, time_block = b.time;
+        const bool colours = b.rgb != 0;
         rf.path = path;
         if (n) {
             st = Status::FromLib(pcq_device_alloc(ctx, n * 12, &rf.xyz));

@@ -1,6 +1,6 @@
-// search.cpp — collectors, the four optimized per-file searches and the Searcher dispatch.
+// search.cpp — collectors, the plan of the optimized per-file searches and the Searcher dispatch.
 //
-// Each search function does on the host exactly what the reference does before its per-point loop
+// plan_file does on the host exactly what the reference does before its per-point loop
 // (open + mmap, header parse, block offsets, file-level early-out, query box -> local integer box)
 // and then hands the column blocks to libpcq.so, which replaces the loop and the collector pushes.
 #include "pcq_host.hpp"
@@ -9,8 +9,10 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <cstring>
+#include <initializer_list>
 
 namespace pcq {
 
@@ -78,31 +80,6 @@ std::optional<std::vector<Point>> GridSampledCollector::points() {  // :116-118
     return cache_;
 }
 
-// ---- shared pieces of the four searches -------------------------------------------------------------
-namespace {
-
-std::optional<uint64_t> las_offset_to_color(uint8_t fmt) {  // las.rs:38-45, last.rs:83-88
-    switch (fmt) {
-    case 2: return 20;
-    case 3: return 28;
-    case 5: return 28;
-    default: return std::nullopt;
-    }
-}
-
-Status invalid_format(uint8_t fmt, const std::string &path) {
-    return Status::Err(PCQ_ERR_FORMAT, "Invalid LAS format " + std::to_string(fmt) + " in file " + path);
-}
-
-Status eof() { return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer"); }
-
-// A block [off, off + bytes) must lie inside the mapped file.  The reference's Cursor reads fail
-// lazily with UnexpectedEof when a truncated byte is touched; here the blocks a scan may touch are
-// validated up front (DESIGN.md, "deviations").
-bool block_ok(const MappedFile &f, uint64_t off, uint64_t bytes) { return off <= f.size() && bytes <= f.size() - off; }
-
-}  // namespace
-
 // The column blocks were located in the mapped file (header parse, offsets: exactly as the reference does); the
 // bytes themselves are streamed by the library with pread, so a plan carries FILE OFFSETS instead of addresses inside a
 // mapping — and nothing else of the file: the mapping and the descriptor of the prologue are gone when the plan is
@@ -136,318 +113,144 @@ Status execute_plan(FilePlan &plan, ResultCollector &rc) {
     return Status::FromLib(r);
 }
 
-namespace {
-// plan helpers: `done` = resolved on the host (no GPU work), `gpu` = the scan is ready to be issued
-FilePlan done(Status st = Status::Ok()) {
-    FilePlan p;
-    p.status = std::move(st);
-    return p;
+// ---- where a file's columns lie: the one place that knows these numbers -----------------------------------------------
+ColumnLayout column_layout(const LasHeader &h, FileLayout layout) {
+    const uint8_t fmt = h.point_data_record_format;
+    const uint64_t otp = h.offset_to_point_data, n = h.number_of_points;
+    ColumnLayout l;
+    l.record_length = layout == FileLayout::LAS ? h.point_data_record_length : 0;
+    auto at = [&](uint64_t in_point, uint64_t size) {
+        return layout == FileLayout::LAS ? FileColumn{true, otp + in_point, l.record_length, size} : FileColumn{true, otp + n * in_point, size, size};
+    };
+    l.xyz = at(0, 12);                                      // last.rs:114-121, las.rs:102-104
+    l.cls = at(fmt <= 5 ? 15 : 16, 1);                      // last.rs:69-81
+    l.rgb.stride = at(0, 6).stride;                         // (a plan names the colours' stride even where the format has none)
+    if (fmt == 2) l.rgb = at(20, 6);                        // las.rs:38-45, last.rs:83-88: the reference knows the colours of
+    if (fmt == 3 || fmt == 5) l.rgb = at(28, 6);            // formats 2, 3 and 5 only
+    if (fmt != 0 && fmt != 2) l.time = at(fmt <= 5 ? 20 : 22, 8);  // las.rs:305-330
+    return l;
 }
-// `cols` points into the mapping of `file`: the plan keeps the offsets (a NULL column stays NULL; offset 0 never is a
-// column, the header lives there)
-FilePlan gpu(const std::string &path, const MappedFile &file, pcq_columns cols, const pcq_predicate &pred) {
-    auto to_offset = [&](const void *p) -> const void * { return p ? (const void *)(uintptr_t)((const uint8_t *)p - file.data()) : nullptr; };
-    cols.xyz = to_offset(cols.xyz);
-    cols.cls = to_offset(cols.cls);
-    cols.rgb = to_offset(cols.rgb);
-    FilePlan plan;
+
+namespace {
+Status invalid_format(uint8_t fmt, const std::string &path) {
+    return Status::Err(PCQ_ERR_FORMAT, "Invalid LAS format " + std::to_string(fmt) + " in file " + path);
+}
+Status eof() { return Status::Err(PCQ_ERR_EOF, "failed to fill whole buffer"); }
+
+// A block [off, off + bytes) must lie inside the mapped file.  The reference's Cursor reads fail
+// lazily with UnexpectedEof when a truncated byte is touched; here the blocks a scan may touch are
+// validated up front (DESIGN.md, "deviations").
+bool block_ok(const MappedFile &f, uint64_t off, uint64_t bytes) { return off <= f.size() && bytes <= f.size() - off; }
+
+// Every column of `read` lies inside the file.  LAST: each block, n elements.  LAS: every record up to the last byte any of the
+// columns needs, as one block from the first record.
+bool columns_ok(const MappedFile &f, const LasHeader &h, FileLayout layout, std::initializer_list<FileColumn> read) {
+    const uint64_t n = h.number_of_points, otp = h.offset_to_point_data;
+    uint64_t last_needed = 0;
+    for (const FileColumn &c : read) {
+        if (!c.present) continue;
+        if (layout == FileLayout::LAST && !block_ok(f, c.offset, n * c.size)) return false;
+        last_needed = std::max(last_needed, c.offset - otp + c.size);
+    }
+    return layout == FileLayout::LAST || block_ok(f, otp, (n - 1) * h.point_data_record_length + last_needed);
+}
+}  // namespace
+
+// What the host does for one file before the per-point loop: open + mmap, header, where the columns lie, the file-level early-out,
+// the query box -> local integer box.  One body for the five kinds and both layouts; what differs between them is named first.
+FilePlan plan_file(const std::string &path, FileLayout layout, const Query &q) {
+    const bool las = layout == FileLayout::LAS;
+    const bool plain_box = q.kind == PCQ_PRED_BOUNDS;
+    const bool by_class = q.kind == PCQ_PRED_CLASS || q.kind == PCQ_PRED_BOUNDS_CLASS;
+    const bool by_time = q.kind == PCQ_PRED_TIME || q.kind == PCQ_PRED_BOUNDS_TIME;
+    const bool boxed = !(q.kind == PCQ_PRED_CLASS || q.kind == PCQ_PRED_TIME);
+    const bool mask_format = !las && by_class;     // last.rs:220-223 `&= 0b1111`; no other search masks (last.rs:53-54, las.rs:59-60, :199-200, :302-303)
+    const bool format_rereported = by_time;        // las.rs:324-329: the time search's own match arm names a format above 10
+    const bool class_at_15 = las && plain_box;     // las.rs:121-124 seek(Current(3)): +15 whatever the format; las.rs:224-228 goes by format
+    const bool prints_record_size = las && plain_box;  // las.rs:73, before the early-out; the combined kinds print none
+    const bool box_first = plain_box;              // last.rs:92-109: early-out and box before a byte of a point is touched; the combined
+                                                   // kinds run the attribute search's prologue, then these two
+    const bool colours = !by_time;                 // las.rs:345-355 `..Default::default()`: a time record has no colour
+
+    FilePlan plan;  // resolved on the host (no GPU work) until the last lines
+    auto resolved = [&](Status st = Status::Ok()) {
+        FilePlan p;
+        p.status = std::move(st), p.las_record_size = plan.las_record_size;
+        return p;
+    };
+    MappedFile file;
+    Status st = file.open(path);  // last.rs:51
+    if (!st.ok()) return resolved(st);
+    LasHeader h;
+    st = parse_las_header(file.data(), file.size(), mask_format, &h);
+    if (!st.ok() && format_rereported && st.message.rfind("invalid point format number: ", 0) == 0) st = invalid_format(file.data()[104], path);  // (the format byte)
+    if (!st.ok()) return resolved(st);
+    if (prints_record_size) plan.las_record_size = h.point_data_record_length;
+    ColumnLayout l = column_layout(h, layout);
+    if (class_at_15) l.cls.offset = h.offset_to_point_data + 15;
+    if (by_time && !l.time.present) return resolved(Status::Err(PCQ_ERR_FORMAT, "File " + path + " does not contain GPS times!"));  // las.rs:306-318
+    const FileColumn attribute = by_time ? l.time : l.cls, rgb = colours ? l.rgb : FileColumn{};
+    const uint64_t n = h.number_of_points;
+
+    // the header-AABB early-out (last.rs:92-94: resolved from the header alone), then the box (:98-109) and its error
+    pcq_predicate pred{};
+    auto box = [&]() -> std::optional<FilePlan> {
+        if (!h.bounds.intersects(q.box)) return resolved();
+        const int rc = pcq_box_to_local(q.box.min, q.box.max, h.scale, h.offset, pred.lmin, pred.lmax);
+        if (rc) return resolved(Status::FromLib(rc));
+        return std::nullopt;
+    };
+    if (box_first)
+        if (auto out = box()) return *out;
+    if (n != 0 && !columns_ok(file, h, layout, {l.xyz, attribute, rgb})) return resolved(eof());
+    if (boxed && !box_first)
+        if (auto out = box()) return *out;
+    if (n == 0) {  // (no points; no file-level early-out for the attributes: the header has no class or time bounds, las.rs:332)
+        FilePlan p = resolved();
+        if (!box_first) p.pred = pred;  // (a combined plan keeps the box it converted; nothing reads the predicate of a resolved plan)
+        return p;
+    }
+
+    pred.kind = q.kind;
+    if (by_class) pred.cls = q.cls;                               // last.rs:259-262 whole byte
+    if (by_time) pred.wmin[0] = q.start, pred.wmax[0] = q.end;    // Range { start, end }: start <= t && t < end (las.rs:336)
+    // The bytes are streamed by the library with pread, so the plan carries FILE OFFSETS as column "pointers" (a NULL column stays
+    // NULL; offset 0 never is a column, the header lives there) and which file they hold for: execute_plan opens the path again.
+    auto pointer = [](const FileColumn &c) { return c.present ? (const void *)(uintptr_t)c.offset : nullptr; };
     plan.needs_gpu = true;
     plan.path = path;
     plan.file_size = file.size();
     plan.file_dev = file.dev(), plan.file_ino = file.ino(), plan.file_mtime_ns = file.mtime_ns();
-    plan.cols = cols;
+    plan.cols.xyz = pointer(l.xyz), plan.cols.xyz_stride = l.xyz.stride;
+    plan.cols.cls = pointer(attribute), plan.cols.cls_stride = attribute.stride;  // (the predicate's column: class bytes or GPS times)
+    plan.cols.rgb = pointer(rgb), plan.cols.rgb_stride = rgb.stride;
+    plan.cols.n = n;
+    for (int a = 0; a < 3; a++) plan.cols.scale[a] = h.scale[a], plan.cols.offset[a] = h.offset[a];  // last.rs:156-160
     plan.pred = pred;
     return plan;
 }
-}  // namespace
 
-// ---- last.rs:46-166 -------------------------------------------------------------------------------------
-FilePlan plan_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);  // :51
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, &h);  // :53-54
-    if (!st.ok()) return done(st);
-    const uint8_t fmt = h.point_data_record_format;  // :68
-    uint64_t cls_in_point;
-    if (fmt <= 5) cls_in_point = 15;  // :69-79
-    else if (fmt <= 10) cls_in_point = 16;
-    else return done(invalid_format(fmt, path));
-    const uint64_t n = h.number_of_points;
-    const uint64_t otp = h.offset_to_point_data;
-    const uint64_t cls_block = otp + n * cls_in_point;  // :80-81
-    const auto col_in_point = las_offset_to_color(fmt);  // :83-88
-    const std::optional<uint64_t> col_block = col_in_point ? std::optional<uint64_t>(otp + n * *col_in_point) : std::nullopt;  // :89-90
-
-    if (!h.bounds.intersects(bounds)) return done();  // :92-94: resolved from the header alone
-
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS;
-    const int brc = pcq_box_to_local(bounds.min, bounds.max, h.scale, h.offset, pred.lmin, pred.lmax);  // :98-109
-    if (brc) return done(Status::FromLib(brc));
-    if (n == 0) return done();
-
-    if (!block_ok(file, otp, n * 12) || !block_ok(file, cls_block, n) || (col_block && !block_ok(file, *col_block, n * 6)))
-        return done(eof());
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;  // :114-121
-    cols.xyz_stride = 12;
-    cols.cls = file.data() + cls_block;  // :138-142
-    cols.cls_stride = 1;
-    cols.rgb = col_block ? file.data() + *col_block : nullptr;  // :145-153
-    cols.rgb_stride = 6;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :156-160
-    return gpu(path, file, cols, pred);
-}
-Status search_last_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc) {
-    FilePlan plan = plan_last_file_by_bounds_optimized(path, bounds);
-    return execute_plan(plan, rc);
-}
-
-// ---- last.rs:213-293 -------------------------------------------------------------------------------------
-FilePlan plan_last_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);  // :218
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    st = parse_las_header(file.data(), file.size(), /*mask_format=*/true, &h);  // :220-223
-    if (!st.ok()) return done(st);
-    if (header) *header = h;
-    const uint8_t fmt = h.point_data_record_format;  // :225
-    uint64_t cls_in_point;
-    if (fmt <= 5) cls_in_point = 15;  // :226-236
-    else if (fmt <= 10) cls_in_point = 16;
-    else return done(invalid_format(fmt, path));
-    const auto col_in_point = las_offset_to_color(fmt);  // :238-243
-    const uint64_t n = h.number_of_points;
-    const uint64_t otp = h.offset_to_point_data;
-    const uint64_t cls_block = cls_in_point * n + otp;  // :245-246, :254-256
-    const std::optional<uint64_t> col_block = col_in_point ? std::optional<uint64_t>(otp + n * *col_in_point) : std::nullopt;  // :249-250
-    if (n == 0) return done();
-
-    if (!block_ok(file, cls_block, n) || !block_ok(file, otp, n * 12) || (col_block && !block_ok(file, *col_block, n * 6)))
-        return done(eof());
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_CLASS;
-    pred.cls = cls;  // :259-262 whole byte
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;  // :265
-    cols.xyz_stride = 12;
-    cols.cls = file.data() + cls_block;
-    cols.cls_stride = 1;
-    cols.rgb = col_block ? file.data() + *col_block : nullptr;  // :272-280
-    cols.rgb_stride = 6;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :283-287
-    return gpu(path, file, cols, pred);
-}
-Status search_last_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc) {
-    FilePlan plan = plan_last_file_by_classification_optimized(path, cls);
-    return execute_plan(plan, rc);
-}
-
-// ---- las.rs:52-148 ---------------------------------------------------------------------------------------
-FilePlan plan_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);  // :57
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, &h);  // :59-60
-    if (!st.ok()) return done(st);
-    const int rec = h.point_data_record_length;  // :73 — printed before the early-out below
-    auto with_rec = [rec](FilePlan p) {
-        p.las_record_size = rec;
-        return p;
-    };
-    const auto color_offset = las_offset_to_color(h.point_data_record_format);  // :74-80
-
-    if (!h.bounds.intersects(bounds)) return with_rec(done());  // :82-84: resolved from the header alone
-
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_BOUNDS;
-    const int brc = pcq_box_to_local(bounds.min, bounds.max, h.scale, h.offset, pred.lmin, pred.lmax);  // :88-99
-    if (brc) return with_rec(done(Status::FromLib(brc)));
-    const uint64_t n = h.number_of_points, rl = h.point_data_record_length, otp = h.offset_to_point_data;
-    if (n == 0) return with_rec(done());
-    // every record up to its last needed byte: XYZ +0..12, class +15, colour +off..off+6
-    const uint64_t last_needed = color_offset ? *color_offset + 6 : 16;
-    if (!block_ok(file, otp, (n - 1) * rl + last_needed)) return with_rec(done(eof()));
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;  // :102-104
-    cols.cls = file.data() + otp + 15;  // :121-124 — seek(Current(3)): always +15 on this path
-    cols.rgb = color_offset ? file.data() + otp + *color_offset : nullptr;  // :127-135
-    cols.xyz_stride = cols.cls_stride = cols.rgb_stride = rl;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :138-142
-    FilePlan plan = gpu(path, file, cols, pred);
-    plan.las_record_size = rec;
-    return plan;
-}
-Status search_las_file_by_bounds_optimized(const std::string &path, const AABB &bounds, ResultCollector &rc, SearchLog *log) {
-    FilePlan plan = plan_las_file_by_bounds_optimized(path, bounds);
-    if (log) log->las_record_size = plan.las_record_size;
-    return execute_plan(plan, rc);
-}
-
-// ---- las.rs:192-261 --------------------------------------------------------------------------------------
-FilePlan plan_las_file_by_classification_optimized(const std::string &path, uint8_t cls, LasHeader *header) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);  // :197
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, &h);  // :199-200
-    if (!st.ok()) return done(st);
-    if (header) *header = h;
-    const uint8_t fmt = h.point_data_record_format;  // raw, unmasked (:202)
-    uint64_t cls_in_point;
-    if (fmt <= 5) cls_in_point = 15;
-    else if (fmt <= 10) cls_in_point = 16;
-    else return done(invalid_format(fmt, path));
-    const auto color_offset = las_offset_to_color(fmt);  // :214-219
-    const uint64_t n = h.number_of_points, rl = h.point_data_record_length, otp = h.offset_to_point_data;
-    if (n == 0) return done();
-    const uint64_t last_needed = color_offset ? *color_offset + 6 : cls_in_point + 1;
-    if (!block_ok(file, otp, (n - 1) * rl + last_needed)) return done(eof());
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_CLASS;
-    pred.cls = cls;
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;  // :233-237
-    cols.cls = file.data() + otp + cls_in_point;  // :224-228
-    cols.rgb = color_offset ? file.data() + otp + *color_offset : nullptr;  // :240-248
-    cols.xyz_stride = cols.cls_stride = cols.rgb_stride = rl;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :251-255
-    return gpu(path, file, cols, pred);
-}
-Status search_las_file_by_classification_optimized(const std::string &path, uint8_t cls, ResultCollector &rc) {
-    FilePlan plan = plan_las_file_by_classification_optimized(path, cls);
-    return execute_plan(plan, rc);
-}
-
-// ---- las.rs:297-358 (and its LAST counterpart, a todo!() stub at last.rs:339-400) -------------------------------
-namespace {
-// The prologue of _search_las_file_by_time_range_optimized: header (raw format, las.rs:302-303) and the GPS time's offset in
-// a record by format (:305-330).  A format above 10 is reported as the reference's match arm does — "Invalid LAS format"
-// (:324-329) — not as the header parser's error.
-Status time_prologue(const MappedFile &file, const std::string &path, LasHeader *h, uint64_t *time_in_point) {
-    Status st = parse_las_header(file.data(), file.size(), /*mask_format=*/false, h);
-    if (!st.ok()) {
-        if (st.message.rfind("invalid point format number: ", 0) == 0) return invalid_format(file.data()[104], path);  // (the format byte)
-        return st;
+// The host-only part of ResidentDataset::load for one LAST file.  with_times: first everything the LAST time search's prologue
+// raises for this file, so a file fails here as it fails there (no GPS times, a format above 10, a block past the file's end).
+Status resident_file_blocks(const std::string &path, bool with_points, bool with_times, MappedFile *file, ResidentBlocks *out) {
+    *out = ResidentBlocks{};
+    if (path.size() < 5 || path.compare(path.size() - 5, 5, ".last") != 0)
+        return Status::Err(PCQ_ERR_EXTENSION, "resident datasets hold LAST files: " + path);
+    if (with_times) {
+        const FilePlan plan = plan_file(path, FileLayout::LAST, Query{PCQ_PRED_TIME, {}, 0, 0.0, 0.0});
+        if (!plan.status.ok()) return plan.status;
     }
-    const uint8_t fmt = h->point_data_record_format;
-    if (fmt == 0 || fmt == 2) return Status::Err(PCQ_ERR_FORMAT, "File " + path + " does not contain GPS times!");  // :306-318
-    *time_in_point = fmt <= 5 ? 20 : 22;  // :313, :319-320
+    Status st = file->open(path);
+    if (!st.ok()) return st;
+    st = parse_las_header(file->data(), file->size(), /*mask_format=*/false, &out->header);  // last.rs:53-54
+    if (!st.ok()) return st;
+    const ColumnLayout l = column_layout(out->header, FileLayout::LAST);
+    if (!columns_ok(*file, out->header, FileLayout::LAST, {l.xyz, l.cls})) return eof();
+    const bool colours = with_points && l.rgb.present;
+    if (colours && !columns_ok(*file, out->header, FileLayout::LAST, {l.rgb})) return eof();
+    out->xyz = l.xyz.offset, out->cls = l.cls.offset;
+    out->rgb = colours ? l.rgb.offset : 0, out->time = with_times ? l.time.offset : 0;
     return Status::Ok();
-}
-pcq_predicate time_predicate(double start, double end) {
-    pcq_predicate pred{};
-    pred.kind = PCQ_PRED_TIME;
-    pred.wmin[0] = start;  // Range { start, end }: start <= t && t < end (:336)
-    pred.wmax[0] = end;
-    return pred;
-}
-}  // namespace
-
-FilePlan plan_las_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);  // :302
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    uint64_t t_in_point = 0;
-    st = time_prologue(file, path, &h, &t_in_point);
-    if (!st.ok()) return done(st);
-    if (header) *header = h;
-    const uint64_t n = h.number_of_points, rl = h.point_data_record_length, otp = h.offset_to_point_data;
-    if (n == 0) return done();  // (no file-level early-out: the header has no time bounds, :332)
-    if (!block_ok(file, otp, (n - 1) * rl + t_in_point + 8)) return done(eof());
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;               // :340-344
-    cols.cls = file.data() + otp + t_in_point;  // :333-334 — the predicate's column: the GPS time
-    cols.xyz_stride = cols.cls_stride = rl;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];  // :347-351
-    return gpu(path, file, cols, time_predicate(start, end));
-}
-Status search_las_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc) {
-    FilePlan plan = plan_las_file_by_time_range_optimized(path, start, end);
-    return execute_plan(plan, rc);
-}
-
-// LAST: the record transposed by attribute (last_reader.rs:83-144) — the times are one block of n f64 at
-// offset_to_point_data + n * 20 (formats 1, 3-5) or + n * 22 (6-10); records as in las.rs:345-355.
-FilePlan plan_last_file_by_time_range_optimized(const std::string &path, double start, double end, LasHeader *header) {
-    auto holder = std::make_unique<MappedFile>();
-    MappedFile &file = *holder;
-    Status st = file.open(path);
-    if (!st.ok()) return done(st);
-    LasHeader h;
-    uint64_t t_in_point = 0;
-    st = time_prologue(file, path, &h, &t_in_point);
-    if (!st.ok()) return done(st);
-    if (header) *header = h;
-    const uint64_t n = h.number_of_points, otp = h.offset_to_point_data;
-    const uint64_t time_block = otp + n * t_in_point;
-    if (n == 0) return done();
-    if (!block_ok(file, otp, n * 12) || !block_ok(file, time_block, n * 8)) return done(eof());
-    pcq_columns cols{};
-    cols.xyz = file.data() + otp;
-    cols.xyz_stride = 12;
-    cols.cls = file.data() + time_block;
-    cols.cls_stride = 8;
-    cols.n = n;
-    for (int a = 0; a < 3; a++) cols.scale[a] = h.scale[a], cols.offset[a] = h.offset[a];
-    return gpu(path, file, cols, time_predicate(start, end));
-}
-Status search_last_file_by_time_range_optimized(const std::string &path, double start, double end, ResultCollector &rc) {
-    FilePlan plan = plan_last_file_by_time_range_optimized(path, start, end);
-    return execute_plan(plan, rc);
-}
-
-// ---- combined searches: the box AND a class byte or a GPS time range (not in the reference) -----------
-namespace {
-// The plan of a combined search, in this order: the attribute search's prologue as it stands (header, format, GPS and EOF
-// errors; its columns, predicate and records), then the bounds search's header early-out (last.rs:92-94: a disjoint file is
-// resolved on the host, 0 matches), then its box (last.rs:98-109).  The bounds search's own format check is not repeated and
-// no record size is printed.
-FilePlan with_box(FilePlan plan, const LasHeader &h, const AABB &bounds, int kind) {
-    if (!plan.status.ok()) return plan;
-    if (!h.bounds.intersects(bounds)) return done();
-    const int brc = pcq_box_to_local(bounds.min, bounds.max, h.scale, h.offset, plan.pred.lmin, plan.pred.lmax);
-    if (brc) return done(Status::FromLib(brc));
-    if (!plan.needs_gpu) return plan;  // (no points)
-    plan.pred.kind = kind;
-    return plan;
-}
-}  // namespace
-
-FilePlan plan_las_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls) {
-    LasHeader h;
-    FilePlan plan = plan_las_file_by_classification_optimized(path, cls, &h);
-    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_CLASS);
-}
-FilePlan plan_last_file_by_bounds_and_class_optimized(const std::string &path, const AABB &bounds, uint8_t cls) {
-    LasHeader h;
-    FilePlan plan = plan_last_file_by_classification_optimized(path, cls, &h);
-    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_CLASS);
-}
-FilePlan plan_las_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end) {
-    LasHeader h;
-    FilePlan plan = plan_las_file_by_time_range_optimized(path, start, end, &h);
-    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_TIME);
-}
-FilePlan plan_last_file_by_bounds_and_time_optimized(const std::string &path, const AABB &bounds, double start, double end) {
-    LasHeader h;
-    FilePlan plan = plan_last_file_by_time_range_optimized(path, start, end, &h);
-    return with_box(std::move(plan), h, bounds, PCQ_PRED_BOUNDS_TIME);
 }
 
 // ---- searcher.rs ---------------------------------------------------------------------------------------------
@@ -466,110 +269,31 @@ Status out_of_scope(const std::string &what, const std::string &path) {
 
 // The host-only prologue of search_file for the formats whose prologue needs no GPU (LAS / LAST --optimized): everything
 // the reference does before its per-point loop.  Other formats (and errors of the dispatch itself) are left to search_file.
-std::optional<FilePlan> BoundsSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
+std::optional<FilePlan> Searcher::plan_file(const std::string &path, SearchImplementation impl) const {
     const auto ext = extension_of(path);
     if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
-    if (*ext == "las") return plan_las_file_by_bounds_optimized(path, bounds_);
-    if (*ext == "last") return plan_last_file_by_bounds_optimized(path, bounds_);
-    return std::nullopt;
-}
-std::optional<FilePlan> ClassSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
-    const auto ext = extension_of(path);
-    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
-    if (*ext == "las") return plan_las_file_by_classification_optimized(path, class_);
-    if (*ext == "last") return plan_last_file_by_classification_optimized(path, class_);
+    if (*ext == "las") return pcq::plan_file(path, FileLayout::LAS, query_);
+    if (*ext == "last") return pcq::plan_file(path, FileLayout::LAST, query_);
     return std::nullopt;
 }
 
-std::optional<FilePlan> TimeSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
-    const auto ext = extension_of(path);
-    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
-    if (*ext == "las") return plan_las_file_by_time_range_optimized(path, start_, end_);
-    if (*ext == "last") return plan_last_file_by_time_range_optimized(path, start_, end_);
-    return std::nullopt;
-}
-
-std::optional<FilePlan> BoundsClassSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
-    const auto ext = extension_of(path);
-    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
-    if (*ext == "las") return plan_las_file_by_bounds_and_class_optimized(path, bounds_, class_);
-    if (*ext == "last") return plan_last_file_by_bounds_and_class_optimized(path, bounds_, class_);
-    return std::nullopt;
-}
-std::optional<FilePlan> BoundsTimeSearcher::plan_file(const std::string &path, SearchImplementation impl) const {
-    const auto ext = extension_of(path);
-    if (!ext || impl != SearchImplementation::Optimized) return std::nullopt;
-    if (*ext == "las") return plan_las_file_by_bounds_and_time_optimized(path, bounds_, start_, end_);
-    if (*ext == "last") return plan_last_file_by_bounds_and_time_optimized(path, bounds_, start_, end_);
-    return std::nullopt;
-}
-
-Status BoundsSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                                   SearchLog *log) const {  // searcher.rs:43-90
+Status Searcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *log) const {  // searcher.rs:43-90, :104-151
     const auto ext = extension_of(path);
     if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
     if (*ext == "las" || *ext == "last") {
         if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
-        return *ext == "las" ? search_las_file_by_bounds_optimized(path, bounds_, collector, log)
-                             : search_last_file_by_bounds_optimized(path, bounds_, collector);
-    }
-    if (*ext == "lazer") return search_lazer_file_by_bounds(path, bounds_, collector);  // searcher.rs:83, either implementation
-    if (*ext == "laz") return out_of_scope("compressed format .laz", path);
-    return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
-}
-
-Status ClassSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector,
-                                  SearchLog *) const {  // searcher.rs:104-151
-    const auto ext = extension_of(path);
-    if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
-    if (*ext == "las" || *ext == "last") {
-        if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
-        return *ext == "las" ? search_las_file_by_classification_optimized(path, class_, collector)
-                             : search_last_file_by_classification_optimized(path, class_, collector);
-    }
-    if (*ext == "lazer") return search_lazer_file_by_classification(path, class_, collector);  // searcher.rs:144
-    if (*ext == "laz") return out_of_scope("compressed format .laz", path);
-    return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
-}
-
-Status TimeSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
-    const auto ext = extension_of(path);
-    if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
-    if (*ext == "las" || *ext == "last") {
-        if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
-        return *ext == "las" ? search_las_file_by_time_range_optimized(path, start_, end_, collector)
-                             : search_last_file_by_time_range_optimized(path, start_, end_, collector);
-    }
-    // the reference's LAZ / LAZER time searches are todo!() stubs (laz.rs:131-146, lazer.rs:115-122)
-    if (*ext == "lazer") return out_of_scope("time search in .lazer files", path);
-    if (*ext == "laz") return out_of_scope("compressed format .laz", path);
-    return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
-}
-
-}  // namespace pcq
-
-namespace pcq {
-namespace {
-// search_file of the combined searchers: the LAS / LAST plan (optimized only), as the other searchers dispatch
-Status combined_search_file(const Searcher &searcher, const std::string &path, SearchImplementation impl, ResultCollector &collector) {
-    const auto ext = extension_of(path);
-    if (!ext) return Status::Err(PCQ_ERR_EXTENSION, "Invalid extension on file " + path);
-    if (*ext == "las" || *ext == "last") {
-        if (impl == SearchImplementation::Regular) return out_of_scope("the Regular (non --optimized) search implementation", path);
-        FilePlan plan = *searcher.plan_file(path, impl);
+        FilePlan plan = *plan_file(path, impl);
+        if (log) log->las_record_size = plan.las_record_size;
         return execute_plan(plan, collector);
     }
-    if (*ext == "lazer") return out_of_scope("combined search in .lazer files", path);
+    if (*ext == "lazer") {  // searcher.rs:83, :144, either implementation
+        if (query_.kind == PCQ_PRED_BOUNDS) return search_lazer_file_by_bounds(path, query_.box, collector);
+        if (query_.kind == PCQ_PRED_CLASS) return search_lazer_file_by_classification(path, query_.cls, collector);
+        // the reference's LAZ / LAZER time searches are todo!() stubs (laz.rs:131-146, lazer.rs:115-122)
+        return out_of_scope(query_.kind == PCQ_PRED_TIME ? "time search in .lazer files" : "combined search in .lazer files", path);
+    }
     if (*ext == "laz") return out_of_scope("compressed format .laz", path);
     return Status::Err(PCQ_ERR_EXTENSION, "Unsupported file extension in file " + path);
-}
-}  // namespace
-
-Status BoundsClassSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
-    return combined_search_file(*this, path, impl, collector);
-}
-Status BoundsTimeSearcher::search_file(const std::string &path, SearchImplementation impl, ResultCollector &collector, SearchLog *) const {
-    return combined_search_file(*this, path, impl, collector);
 }
 
 }  // namespace pcq
