@@ -213,6 +213,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_time_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, P(C.c_double), C.c_size_t, vp, vp]),
         "pcq_scan_dev_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]),
         "pcq_scan_dev_zrange_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "pcq_scan_dev_count_batch_polygon": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_int32), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
         "pcq_read_fd_to_device": (C.c_int, [vp, C.c_int, u64, u64, vp]),
@@ -510,6 +511,23 @@ class Context:
         wa = (C.c_uint32 * max(len(flat), 1))(*flat)
         _check(self.lib.pcq_scan_dev_zrange_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_zmin), C.c_void_p(d_zmax),
                                                          C.c_void_p(stream)))
+
+    def scan_dev_count_batch_polygon(self, cols: Sequence[Columns], preds: Sequence[Predicate], verts, d_total: int,
+                                     stream: Optional[int] = None) -> None:
+        """Box AND polygon (Predicate kind PCQ_PRED_BOUNDS; segments laid out as for scan_dev_count_batch_multi) over many resident
+        LAST files in ONE pass.  verts: per segment its outline as a sequence of (x, y) pairs of i32 in the segment's lattice, all of
+        one length (3 .. PCQ_POLYGON_VERTS_MAX); for every point inside its segment's box and inside the outline under the even-odd
+        rule of pcq.h, += 1 into the word d_total."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        assert len(verts) == n, "one outline per segment"
+        nverts = len(verts[0]) if n else 3
+        assert all(len(v) == nverts for v in verts), "outlines of one length"
+        flat = [int(w) for v in verts for xy in v for w in xy]
+        assert len(flat) == 2 * n * nverts, "(x, y) pairs"
+        va = (C.c_int32 * max(len(flat), 1))(*flat)
+        _check(self.lib.pcq_scan_dev_count_batch_polygon(self.handle, ca, pa, va, n, nverts, C.c_void_p(d_total), C.c_void_p(stream)))
 
     def scan_dev_count_batch_bounds_time(self, cols: Sequence[Columns], preds: Sequence[Predicate], device_total: int,
                                          stream: Optional[int] = None) -> None:

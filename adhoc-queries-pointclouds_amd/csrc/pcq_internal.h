@@ -167,6 +167,29 @@ struct DevRasterSegment {
 static_assert(sizeof(DevRasterSegment) == 72, "DevRasterSegment: DevSegment and four words");
 constexpr int PCQ_SEGMENTS_RASTER = 0x5253;  // ("RS") no pcq_predicate_kind
 
+// One segment of a box AND polygon count launch (scan_polygon.hip): DevSegment with the place of the segment's edges in the
+// trailer behind the table.  An edge is a DevPolygonEdge: the outline's edge with its lower end first; horizontal edges, which never
+// cross a point, do not travel.  At its own pitch in the same buffers, under a kind of its own; the edges are part of the bytes the
+// upload compares.
+struct DevPolygonSegment {
+    const int4 *xyz;       // 16-byte aligned positions block
+    uint64_t n;            // points
+    uint64_t tile_begin;   // first global step of this segment
+    int32_t lo[3];
+    uint32_t width[3];
+    int32_t empty;
+    int32_t _pad;
+    uint32_t edge_begin;   // first edge of the segment, counted in edges from the start of the trailer
+    uint32_t nedges;       // its edges (0 .. PCQ_POLYGON_VERTS_MAX)
+};
+static_assert(sizeof(DevPolygonSegment) == 64, "DevPolygonSegment: DevSegment and two words; the trailer behind a table stays 16-byte aligned");
+struct DevPolygonEdge {
+    int32_t ax, ay;        // the end with the smaller y
+    int32_t bx, by;        // the other end: by > ay
+};
+static_assert(sizeof(DevPolygonEdge) == 16, "DevPolygonEdge: one 16-byte scalar load");
+constexpr int PCQ_SEGMENTS_POLYGON = 0x5047;  // ("PG") no pcq_predicate_kind
+
 // SparseGrid parameters (grid_sampling.rs:9-47) in device form.
 struct DevGrid {
     double bmin[3], bmax[3];
@@ -351,6 +374,7 @@ struct pcq_ctx {
     int class_hist_copies = 0;    // ... and copies of the LDS histogram per wave, 1 / 2 / 4 / 8 / 16 (0 = the product's: CLASS_HIST_COPIES)
     int raster_waves_per_cu = 0;  // density raster (scan_raster.hip): workgroups per CU before the LDS limit (0 = the product's: RASTER_WAVES_PER_CU)
     int zrange_waves_per_cu = 0;  // height raster (scan_zrange.hip): workgroups per CU before the LDS limit (0 = the product's: ZRANGE_WAVES_PER_CU)
+    int polygon_waves_per_cu = 0; // box AND polygon count (scan_polygon.hip): workgroups per CU (0 = the product's: POLYGON_WAVES_PER_CU)
     int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif
     int numa_node = -1;               // NUMA node the GPU hangs off (sysfs), -1 if unknown

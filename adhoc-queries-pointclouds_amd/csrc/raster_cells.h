@@ -1,8 +1,8 @@
 // raster_cells.h — what the kernels that bin the points of a box into the cells of a 2-D raster over x and y share: the density
 // raster (scan_raster.hip: a count per cell) and the height raster (scan_zrange.hip: min and max z per cell).  The cursor kind of
 // seg_seek (scan_tiles.h) that carries a segment's origin, cell widths and division magics through SGPRs, the cell of a point,
-// the move of a value from the next lane, and — host side — the one fill of a DevRasterSegment with every refusal of the two
-// entries.
+// the move of a value from the next lane, the gather of a load's points (slot_xy, for the polygon count of scan_polygon.hip), and
+// — host side — the one fill of a DevRasterSegment with every refusal of the two entries.
 #pragma once
 
 #include "pcq_internal.h"
@@ -41,6 +41,20 @@ __device__ __forceinline__ uint32_t cell_of(int x, int y, const RasterCol &c, ui
 // v of lane + 1; lane 63 gets `last`
 __device__ __forceinline__ int next_lane(int v, int last) {
     return __builtin_amdgcn_update_dpp(last, v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+
+// The x and y of the points that start in load k of a tile, each pair in the lane that holds the point's first dword (the polygon
+// count, scan_polygon.hip; tile_raster of scan_raster.hip spells the same gather out: written through this helper its kernel came
+// out of the compiler with other code — 72 compares for 24, fewer SGPR spills — and 5 % slower at 8192 cells): (xa, ya) of the point every lane starts among j = 0..2, at j0 = (3 - (k + l) % 3)
+// % 3, both its own; (xb, yb) of the second point that starts at j = 3 where j0 == 0: x = v[k][3], y = the NEXT lane's v[k][0] — one
+// cross-lane move per load; for lane 63 of load 0 it is lane 0's v[1][0] (v_readlane), point 85 of the tile, the only one whose x
+// and y sit in different loads (lane 63 starts no second point in loads 1 and 2).  Where no second point starts (xb, yb) mean nothing.
+__device__ __forceinline__ void slot_xy(const v4i (&v)[3], int k, int lane, int &xa, int &ya, int &xb, int &yb) {
+    const bool j0_0 = (start_lanes(k) >> lane) & 1ull, j0_1 = (start_lanes(k + 1) >> lane) & 1ull;
+    xa = j0_0 ? v[k][0] : (j0_1 ? v[k][1] : v[k][2]);
+    ya = j0_0 ? v[k][1] : (j0_1 ? v[k][2] : v[k][3]);
+    xb = v[k][3];
+    yb = next_lane(v[k][0], k == 0 ? __builtin_amdgcn_readlane(v[1][0], 0) : 0);
 }
 
 // Segment i of a raster launch of nx x ny cells (dim) with cell widths cw, as k1_batch_launch's fill: the refusals that keep every

@@ -1,5 +1,5 @@
 // scan_batch_host.h — the host side of the K1-family batched launches (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip,
-// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip): host code only; the kernels and their constants are in scan_tiles.h.
+// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_polygon.hip): host code only; the kernels and their constants are in scan_tiles.h.
 #pragma once
 
 #include <vector>
@@ -14,7 +14,7 @@ namespace {
 // the finish.  The table first: nothing is touched when a segment is refused.  Per segment, in this order: admit(i) (the
 // entry's refusals that come before those of the positions), the positions' refusals, fill(seg, i) (the entry's columns and
 // predicates, or their refusal); xyz, n and tile_begin are filled here.  launch(workgroups, steps) enqueues the kernel, or refuses.
-// A trailer (the time histogram's edges) travels behind the table in the same upload, under the same compare of all bytes.
+// A trailer (the time histogram's edges, the polygon count's outlines) travels behind the table in the same upload, under the same compare of all bytes.
 // finish(workgroups) enqueues the fold of the partials into the caller's words: pcq_launch_finish_counts (`folded` slices added into
 // d_out) for every count; the height raster brings its own (pcq_launch_finish_zrange).
 struct K1Batch {

@@ -1,5 +1,5 @@
 // scan_tiles.h — what the count kernels (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip, scan_class_hist.hip,
-// scan_time_hist.hip, scan_raster.hip, scan_time.hip) and the chunk index (chunk_index.hip) share: the mask algebra of a 768-dword tile of packed LAST positions,
+// scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_polygon.hip, scan_time.hip) and the chunk index (chunk_index.hip) share: the mask algebra of a 768-dword tile of packed LAST positions,
 // K1's second column (class bytes or GPS times), the register sets of the software pipeline with their loads and counted waits
 // (PipeRegs for the K1 family, VecRegs for the one-column kernels K2 and K3; the loop itself is written in each kernel: see
 // scan_count.hip) and the batched K1 (k_bounds_count_batch_pipe: one template for the box, box AND class and box AND time

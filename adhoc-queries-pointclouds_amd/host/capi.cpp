@@ -411,6 +411,15 @@ extern "C" int pcq_query_resident_bounds_zrange_raster(pcq_host_resident *r, con
         return done(Status::Err(PCQ_ERR_ARG, "height raster: cell_size must be finite and above 0"));
     return done(r->ds->bounds_zrange_raster(bmin, zmax, cell_size, nx, ny, zlo, zhi, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
 }
+extern "C" int pcq_query_resident_count_polygon(pcq_host_resident *r, size_t nverts, const double *xy, double zmin, double zmax, uint64_t *matches,
+                                                uint64_t *points_scanned) {
+    if (!r || !xy || !matches) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nverts < 3 || nverts > PCQ_POLYGON_VERTS_MAX)  // (neither r nor a device is touched before these)
+        return done(Status::Err(PCQ_ERR_ARG, "polygon: " + std::to_string(nverts) + " vertices (3 .. " + std::to_string(PCQ_POLYGON_VERTS_MAX) + ")"));
+    for (size_t i = 0; i < 2 * nverts; i++)
+        if (xy[i] - xy[i] != 0.0) return done(Status::Err(PCQ_ERR_ARG, "polygon: vertex " + std::to_string(i / 2) + " is not finite"));
+    return done(r->ds->count_polygon(nverts, xy, zmin, zmax, matches, points_scanned));  // zmin > zmax: PCQ_ERR_PANIC
+}
 extern "C" int pcq_query_resident_search_bounds_time(pcq_host_resident *r, const double bmin[3], const double bmax[3], double start, double end,
                                                      pcq_host_collector *c) {
     if (!r || !bmin || !bmax || !c) return done(Status::Err(PCQ_ERR_ARG, "null argument"));

@@ -393,6 +393,11 @@ public:
     // scale is not finite or not above 0.
     Status bounds_zrange_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, double *zlo, double *zhi,
                                 uint64_t *points_scanned = nullptr);
+    // box AND polygon, count only: the points with z in [zmin, zmax] inside the outline of nverts finite world vertices xy[nverts][2]
+    // (even-odd, exact in each file's lattice: polygon_plan.h), from ONE pass.  The caller has checked nverts and the vertices.  A
+    // scanned file the outline cannot be asked of (its x or y scale, a vertex outside its i32 lattice, a span above 2^31 - 1):
+    // PCQ_ERR_UNSUPPORTED.
+    Status count_polygon(size_t nverts, const double *xy, double zmin, double zmax, uint64_t *matches, uint64_t *points_scanned = nullptr);
     // The per-file searches (search_last_file_by_*_optimized) over every loaded file in load order, into one collector
     Status search_bounds(const AABB &bounds, ResultCollector &rc);
     Status search_class(uint8_t cls, ResultCollector &rc);

@@ -34,11 +34,15 @@
 // The height raster of a box (bounds_zrange_raster): the lowest and the highest world z of the points of every cell of the same
 // lattice, one pcq_scan_dev_zrange_raster_batch per group of files of one z lattice and block of PCQ_ZRANGE_CELLS_MAX cells, instead of
 // a search into a buffer collector whose records the host would have to reduce.
+//
+// Box AND polygon (count_polygon): the points inside a world outline, one pcq_scan_dev_count_batch_polygon over the surviving files
+// with the outline rounded into each file's lattice (polygon_plan.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "pcq_host.hpp"
+#include "polygon_plan.h"
 
 namespace pcq {
 
@@ -303,6 +307,45 @@ Status ResidentDataset::count_bounds_by_time(const double bmin[3], const double 
     }, hist);
     if (st.ok() && points_scanned) *points_scanned = seg.scanned;
     return st;
+}
+
+// How many points lie inside this outline: the prologue of count_box with the world box of the outline, then per surviving file
+// the outline in that file's lattice (polygon_plan.h: the rounded vertices and their box, or PCQ_ERR_UNSUPPORTED) with the z range of
+// the converted box, then ONE pcq_scan_dev_count_batch_polygon over the positions of the surviving files.  `matches` and
+// `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::count_polygon(size_t nverts, const double *xy, double zmin, double zmax, uint64_t *matches, uint64_t *points_scanned) {
+    double lo[2], hi[2];
+    polygon_plan::world_box(nverts, xy, lo, hi);
+    const double bmin[3] = {lo[0], lo[1], zmin}, bmax[3] = {hi[0], hi[1], zmax};
+    AABB bounds;
+    Status st = AABB::from_min_max(bmin, bmax, &bounds);
+    if (!st.ok()) return st;
+    Segments seg;
+    std::vector<int32_t> verts;  // [segment][nverts][2]
+    pcq_predicate pred = predicate(PCQ_PRED_BOUNDS);
+    for (const auto &f : files_) {
+        bool go;
+        const int brc = box_prologue(f, bounds, &pred, &go);
+        if (brc) return Status::FromLib(brc);
+        if (!go) continue;
+        polygon_plan::Outline o;
+        const polygon_plan::Refusal why = polygon_plan::to_lattice(nverts, xy, f.header.scale, f.header.offset, &o);
+        if (why) return Status::Err(PCQ_ERR_UNSUPPORTED, polygon_plan::refusal_text(why) + f.path);
+        for (int a = 0; a < 2; a++) pred.lmin[a] = o.lo[a], pred.lmax[a] = o.hi[a];
+        verts.insert(verts.end(), o.xy.begin(), o.xy.end());
+        seg.cols.push_back(file_columns(f, PCQ_PRED_BOUNDS));
+        seg.preds.push_back(pred);
+        seg.scanned += f.header.number_of_points;
+    }
+    uint64_t got = 0;
+    st = read_counts(1, [&] {
+        return seg.cols.empty() ? (int)PCQ_OK
+                                : pcq_scan_dev_count_batch_polygon(ctx_, seg.cols.data(), seg.preds.data(), verts.data(), seg.cols.size(), nverts, counter_, nullptr);
+    }, &got);
+    if (!st.ok()) return st;
+    *matches = got;
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
 }
 
 // The prologue of the two rasters of a box (count_bounds_raster, bounds_zrange_raster): the prologue of count_box with the world

@@ -329,6 +329,41 @@ int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_p
 #define PCQ_ZRANGE_CELLS_MAX 4096
 int pcq_scan_dev_zrange_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                                      size_t nsegments, uint32_t nx, uint32_t ny, int32_t *device_zmin, int32_t *device_zmax, void *stream);
+/* Box AND polygon in ONE pass: "how many points of this box lie inside this outline?".  Every predicate is PCQ_PRED_BOUNDS and the
+ * layout is that of pcq_scan_dev_count_batch_multi: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.
+ * `verts_xy` is a HOST pointer to [nsegments][nverts][2] i32, in each segment's own lattice.  The rule, all in a segment's integer
+ * lattice:
+ *
+ * A polygon is `m` vertices `V_0 .. V_{m-1}` with `3 <= m <= PCQ_POLYGON_VERTS_MAX`. Each vertex is a pair of i32. The edges are
+ * `(V_i, V_{(i+1) mod m})`.
+ *
+ * For a stored point `(X, Y, Z)` and an edge `A -> B`, let
+ *
+ *     d = (B.x - A.x) * (Y - A.y) - (X - A.x) * (B.y - A.y)        (exact, in integers)
+ *
+ * The edge *crosses* the point iff `(A.y <= Y < B.y and d > 0)` or `(B.y <= Y < A.y and d < 0)`. A horizontal edge never crosses.
+ *
+ * The point is inside iff an odd number of edges cross it (even-odd rule). This means:
+ *
+ * - Orientation does not matter.
+ * - Self-intersecting outlines are legal.
+ * - There is no validity check beyond `m`.
+ *
+ * A point is **counted** iff it passes the `PCQ_PRED_BOUNDS` rule of its segment's predicate (x, y and z, as everywhere) AND is
+ * inside the polygon.
+ *
+ * So a rectangle (x0,y0),(x1,y0),(x1,y1),(x0,y1) contains exactly x0 <= X < x1, y0 <= Y < y1, half-open like the raster's cells,
+ * and two polygons that share an edge never both claim or both drop a point on it.  Exactness bound: for a non-empty predicate,
+ * take the hull of the box's x range clamped to i32 and the vertices' x range, and likewise on y; each hull must span at most
+ * 2^31 - 1.  Then every difference fits 32 signed bits, every product is below 2^62 and d fits an i64.  The count is ADDED to
+ * *device_total.  A predicate that is empty (lmin > lmax on an axis, or a box outside the i32 value range) matches nothing, its
+ * segment is not evaluated and its vertices are not examined.  nsegments == 0 is PCQ_OK after the argument checks.  A null argument,
+ * nverts < 3 or above PCQ_POLYGON_VERTS_MAX, any other predicate kind, any other layout and a non-empty predicate that breaks the
+ * exactness bound are refused (PCQ_ERR_ARG) before anything is uploaded or launched: device_total is untouched. */
+#define PCQ_POLYGON_VERTS_MAX 256
+int pcq_scan_dev_count_batch_polygon(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds,
+                                     const int32_t *verts_xy, size_t nsegments, size_t nverts,
+                                     uint64_t *device_total, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * On-the-fly chunk index for device-resident LAST columns — the reference authors' own next step

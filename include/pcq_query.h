@@ -203,6 +203,23 @@ int pcq_query_resident_count_bounds_raster(pcq_host_resident *r, const double bm
  * pcq_query_resident_count_bounds_raster reports.  On any failure zlo, zhi and points_scanned are left as they were. */
 int pcq_query_resident_bounds_zrange_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
                                             uint64_t ny, double *zlo, double *zhi, uint64_t *points_scanned);
+/* How many points lie inside this outline (count only): the outline is nverts world vertices xy[nverts][2], closed from the last to
+ * the first, and counts the points with z in [zmin, zmax]; even-odd over the edges, so orientation does not matter and a
+ * self-intersecting outline is legal (pcq.h, pcq_scan_dev_count_batch_polygon, has the rule, which is exact in each file's integer
+ * lattice).  The checks in their order, before the dataset or a device is touched: a null r, xy or matches is PCQ_ERR_ARG; nverts < 3
+ * or above PCQ_POLYGON_VERTS_MAX is PCQ_ERR_ARG; a vertex coordinate that is not finite is PCQ_ERR_ARG.  Then per file, in load
+ * order, the prologue of pcq_query_resident_count_bounds with the world box (min x, min y, zmin) .. (max x, max y, zmax) of the
+ * outline: the header early-out, pcq_box_to_local bug for bug, PCQ_ERR_PANIC for zmin > zmax.  lmin[2] and lmax[2] of that
+ * conversion are the z range.  A vertex becomes V.x = nearbyint((x - offset[0]) / scale[0]), V.y = nearbyint((y - offset[1]) /
+ * scale[1]): two f64 operations in this order under the default rounding (ties to even).  A surviving file whose scale[0] or
+ * scale[1] is not finite or not above 0, a vertex that lands outside the i32 range and an outline that spans more than 2^31 - 1
+ * lattice steps on an axis are PCQ_ERR_UNSUPPORTED naming the file.  The file's x and y range is the lattice bounding box of the
+ * ROUNDED vertices, not the converted world box (whose truncation and x-scale quirk would cut vertices off).  Then ONE
+ * pcq_scan_dev_count_batch_polygon over the positions of the surviving files.  points_scanned (NULL: not wanted): what
+ * pcq_query_resident_count_bounds reports for the world box.  On any failure matches and points_scanned are left as they were.
+ * Works on a dataset from any of the loaders. */
+int pcq_query_resident_count_polygon(pcq_host_resident *r, size_t nverts, const double *xy /* [nverts][2], world */,
+                                     double zmin, double zmax, uint64_t *matches, uint64_t *points_scanned);
 /* == pcq_query_search_file_bounds_time(path, bmin, bmax, start, end, optimized=1, c) for every loaded file, in load order, into
  * ONE collector: the same count, the same records byte for byte and in order (class 0, colour (0,0,0), whether or not colour
  * blocks are loaded), the same grid cells and winners; the header early-out leaves the collector's file-order index where it

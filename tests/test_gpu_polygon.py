@@ -1,0 +1,443 @@
+"""pcq_scan_dev_count_batch_polygon: box AND polygon over many resident segments in one pass, every count against the rule of
+include/pcq.h restated in integers (tests/_polygon_rule.py).
+
+Segments of n = 0, 1, 511, 512, 513, 1535, 4133 points, the sizes of test_gpu_raster.py (a step of the pipeline is 512 points),
+positions pieces 16-byte aligned in one buffer.  Every segment has its own origin, its own box and its own outline.  The count is
+ADDED: every call starts from a non-zero device word and the test looks at the difference.  Every comparison is exact equality.
+"""
+import importlib
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _pipeline_plan as pp  # noqa: E402
+import _polygon_rule as rule  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+
+NS = (0, 1, 511, 512, 513, 1535, 4133)
+ALL = tuple(range(len(NS)))
+PCQ_ERR_ARG = -8
+SENTINEL = 0x5EED0000BEEF
+EMPTY = ([5, 5, 5], [4, 4, 4])
+WIDE = 2**40
+
+
+def origin(k):
+    return 1000 * k - 300, 77 - 500 * k
+
+
+def shifted(verts, k):
+    ox, oy = origin(k)
+    return [(ox + x, oy + y) for x, y in verts]
+
+
+def regular(m, r, phase=0.1):
+    """m vertices on a circle of radius r around (r, r), rounded to the lattice (what they enclose is whatever the rule says)"""
+    return [(r + int(round(r * math.cos(phase + 2 * math.pi * i / m))), r + int(round(r * math.sin(phase + 2 * math.pi * i / m)))) for i in range(m)]
+
+
+def draw(rng, w, h, margin=20):
+    """Positions of every segment: x and y independent over w x h lattice steps from the segment's origin and a margin, z in 0..99"""
+    out = []
+    for k, n in enumerate(NS):
+        ox, oy = origin(k)
+        out.append(np.stack([ox + rng.integers(-margin, w + margin, n), oy + rng.integers(-margin, h + margin, n), rng.integers(0, 100, n)],
+                            axis=1).astype(np.int32))
+    return out
+
+
+class Dev:
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.poff, self.psize = pp.carve(NS, [0] * len(NS), 12)
+        self.blocks = [ctx.alloc(self.psize + 64), ctx.alloc(64)]
+        self.d_pos, self.d_total = self.blocks
+        assert all(p % 16 == 0 for p in self.blocks) and all(o % 16 == 0 for o in self.poff)
+        self.cols = [binding.make_columns(xyz=self.d_pos + p, n=n) for p, n in zip(self.poff, NS)]
+        self.xyz = None
+
+    def upload(self, xyz):
+        assert [len(a) for a in xyz] == list(NS)
+        img = np.zeros(self.psize, dtype=np.uint8)
+        for o, a in zip(self.poff, xyz):
+            img[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        self.ctx.to_device(self.d_pos, img)
+        self.xyz = xyz
+
+    def word(self):
+        out = np.zeros(1, dtype=np.uint64)
+        self.ctx.to_host(out, self.d_total)  # (waits for the context's stream)
+        return int(out[0])
+
+    def preset(self, value=SENTINEL):
+        self.ctx.to_device(self.d_total, np.asarray([value], dtype=np.uint64))
+
+    def launch(self, boxes, outlines, segments=ALL, cols=None, preds=None, d_total=None, stream=None):
+        if cols is None:
+            cols = [self.cols[k] for k in segments]
+        if preds is None:
+            preds = [pkg.Predicate.bounds(lo, hi) for lo, hi in boxes]
+        self.ctx.scan_dev_count_batch_polygon(cols, preds, outlines, self.d_total if d_total is None else d_total, stream)
+
+    def added(self, boxes, outlines, segments=ALL):
+        self.preset()
+        self.launch(boxes, outlines, segments)
+        return self.word() - SENTINEL
+
+    def want(self, boxes, outlines, segments=ALL):
+        return sum(int(rule.counted(self.xyz[k], lo, hi, v).sum()) for k, (lo, hi), v in zip(segments, boxes, outlines))
+
+    def check(self, boxes, outlines, segments=ALL):
+        got, want = self.added(boxes, outlines, segments), self.want(boxes, outlines, segments)
+        if got != want:  # which segment
+            per = [(k, self.added([b], [v], [k]), self.want([b], [v], [k])) for k, b, v in zip(segments, boxes, outlines)]
+            raise AssertionError(f"got {got}, want {want}; (segment, got, want) alone: {[p for p in per if p[1] != p[2]]}")
+        return want
+
+    def free(self):
+        for p in self.blocks:
+            self.ctx.free(p)
+
+
+@pytest.fixture(scope="module")
+def dev(gpu_ctx):
+    d = Dev(gpu_ctx)
+    yield d
+    d.free()
+
+
+# (a) ------------------------------------------------------------------------------------------------------------------
+GRID_W = 32
+CONCAVE = {"L": [(3, 2), (27, 2), (27, 7), (12, 7), (12, 14), (3, 14)],
+           "star": [(2, 1), (28, 3), (20, 8), (29, 14), (10, 12), (4, 15), (8, 7)]}
+
+
+def site_grid(k, roll):
+    """Segment k's points on the sites of a grid GRID_W wide from its origin, every site once: point i on site (i + roll) mod n"""
+    n = NS[k]
+    ox, oy = origin(k)
+    site = (np.arange(n) + roll) % n
+    return np.stack([ox + site % GRID_W, oy + site // GRID_W, np.full(n, 50)], axis=1).astype(np.int32)
+
+
+def bisect(dev, k, verts, x0, x1, y0, y1, found):
+    """The counted sites of segment k inside the sub-box [x0, x1] x [y0, y1] into `found`.  A sub-box whose count is 0 holds no counted
+    site, one whose count is its number of points holds only counted sites: both are settled without a look inside."""
+    lo, hi = [x0, y0, 0], [x1, y1, 99]
+    got = dev.added([(lo, hi)], [verts], [k])
+    p = dev.xyz[k]
+    here = p[rule.in_box(p, lo, hi)]
+    assert 0 <= got <= len(here), (k, lo, hi, got, len(here))
+    if got == 0:
+        return
+    if got == len(here):
+        found.update((int(x), int(y)) for x, y, _ in here)
+        return
+    assert (x0, y0) != (x1, y1), (k, x0, y0, got)
+    if x1 - x0 >= y1 - y0:
+        xm = (x0 + x1) // 2
+        bisect(dev, k, verts, x0, xm, y0, y1, found), bisect(dev, k, verts, xm + 1, x1, y0, y1, found)
+    else:
+        ym = (y0 + y1) // 2
+        bisect(dev, k, verts, x0, x1, y0, ym, found), bisect(dev, k, verts, x0, x1, ym + 1, y1, found)
+
+
+LAYOUTS = [("L", 0), ("star", 171), ("L", 256)]
+
+
+@pytest.mark.parametrize("name,roll", LAYOUTS)
+def test_one_point_per_lattice_site(dev, name, roll):
+    """Segments of 512, 513 and 1535 points on a grid around a small concave outline: the count, and by bisection over sub-boxes the
+    set of counted sites, are the rule's.  Every position of a step holds a site: points 85 and 170 of both tiles (x and y in
+    different loads, or brought from the next lane) and the leftover loop's among them."""
+    ks = (3, 4, 5)
+    xyz = [np.full((n, 3), -10**6, dtype=np.int32) for n in NS]
+    for k in ks:
+        xyz[k] = site_grid(k, roll)
+    dev.upload(xyz)
+    outlines = [shifted(CONCAVE[name], k) for k in ks]
+    boxes = [([origin(k)[0], origin(k)[1], 0], [origin(k)[0] + GRID_W - 1, origin(k)[1] + 63, 99]) for k in ks]
+    total = dev.check(boxes, outlines, ks)
+    assert total > 3 * 100
+    for k, (lo, hi), v in zip(ks, boxes, outlines):
+        want = rule.counted(xyz[k], lo, hi, v)
+        found = set()
+        bisect(dev, k, v, lo[0], hi[0], lo[1], hi[1], found)
+        sites = set((int(x), int(y)) for x, y, _ in xyz[k][want])
+        assert found == sites, (k, sorted(found ^ sites)[:12])
+
+
+def test_the_seam_points_are_inside_in_some_layout():
+    """Points 84 .. 86 and 169 .. 171 of both tiles of a step are counted in at least one of the layouts of the test above"""
+    seen = set()
+    for name, roll in LAYOUTS:
+        for k in (3, 5):
+            p = site_grid(k, roll)
+            lo, hi = [origin(k)[0], origin(k)[1], 0], [origin(k)[0] + GRID_W - 1, origin(k)[1] + 63, 99]
+            seen |= set(int(i) % 512 for i in np.flatnonzero(rule.counted(p, lo, hi, shifted(CONCAVE[name], k))) if i < 512 * (NS[k] // 512))
+    for t in (0, 256):
+        assert {t + 84, t + 85, t + 86, t + 169, t + 170, t + 171} <= seen, sorted(seen)
+
+
+# (b) ------------------------------------------------------------------------------------------------------------------
+def test_rectangle_is_the_half_open_box(dev):
+    dev.upload(draw(np.random.default_rng(41), 60, 40, margin=6))
+    rects, boxes, half_open = [], [], []
+    for k in ALL:
+        ox, oy = origin(k)
+        x0, y0, x1, y1 = ox + 3 + k, oy + 2, ox + 50 + k, oy + 37 - k
+        rects.append([(x0, y0), (x1, y0), (x1, y1), (x0, y1)])
+        boxes.append(([x0 - 10, y0 - 10, 10 + k], [x1 + 10, y1 + 10, 90 - k]))
+        half_open.append(([x0, y0, 10 + k], [x1 - 1, y1 - 1, 90 - k]))
+    want = dev.check(boxes, rects)
+    dev.ctx.memset(dev.d_total, 0, 8)
+    dev.ctx.scan_dev_count_batch(dev.cols, [pkg.Predicate.bounds(lo, hi) for lo, hi in half_open], dev.d_total)
+    assert dev.word() == want and 0 < want < sum(NS)
+    # points exactly on the four sides exist in the data: the closed box counts more
+    dev.ctx.memset(dev.d_total, 0, 8)
+    dev.ctx.scan_dev_count_batch(dev.cols, [pkg.Predicate.bounds(lo, [hi[0] + 1, hi[1] + 1, hi[2]]) for lo, hi in half_open], dev.d_total)
+    assert dev.word() > want
+
+
+# (c) ------------------------------------------------------------------------------------------------------------------
+def test_boundaries(dev):
+    """Every lattice site of a 40 x 38 window around an outline with vertical sides, a horizontal top and bottom, and diagonals
+    through lattice points (steps (1, 2), (3, 1) and (-2, 3)): points on the left, right, top and bottom sides, on vertices, on the
+    horizontal edges and on the diagonals' lattice points are in or out as the rule says, and both orientations agree."""
+    k = 5
+    ox, oy = origin(k)
+    outline = [(4, 3), (16, 3), (22, 15), (34, 19), (34, 27), (28, 36), (10, 36), (4, 27)]
+    assert (22 - 16, 15 - 3) == (6, 12) and (34 - 22, 19 - 15) == (12, 4) and (28 - 34, 36 - 27) == (-6, 9)
+    xyz = [np.full((n, 3), -10**6, dtype=np.int32) for n in NS]
+    i = np.arange(40 * 38)
+    xyz[k][:len(i)] = np.stack([ox + i % 40, oy + i // 40, np.full(len(i), 50)], axis=1)
+    dev.upload(xyz)
+    v = shifted(outline, k)
+    box = rule.bbox(v)
+    box = ([box[0][0] - 5, box[0][1] - 5, 0], [box[1][0] + 5, box[1][1] + 5, 99])
+    want = dev.check([box], [v], [k])
+    assert dev.check([box], [v[::-1]], [k]) == want and dev.check([box], [v[3:] + v[:3]], [k]) == want
+    # what the rule says about the sides, spelled out: left and bottom in, right and top out
+    at = lambda x, y: bool(rule.inside([ox + x], [oy + y], v)[0])
+    assert at(4, 10) and not at(34, 22) and at(10, 3) and not at(12, 36)
+    assert at(4, 3) and not at(16, 3) and not at(34, 19) and not at(10, 36) and not at(28, 36)  # vertices
+    assert not at(17, 5) and at(16, 5) and not at(25, 16) and at(24, 16)  # the diagonals' lattice points: right-hand sides are out
+    # row by row
+    for y in range(38):
+        row = ([box[0][0], oy + y, 0], [box[1][0], oy + y, 99])
+        dev.check([row], [v], [k])
+
+
+# (d) ------------------------------------------------------------------------------------------------------------------
+def egcd(a, b):
+    if b == 0:
+        return a, 1, 0
+    g, x, y = egcd(b, a % b)
+    return g, y, x - (a // b) * y
+
+
+def test_near_degenerate_edge(dev):
+    """The edge (0, 0) -> (2^30 + 3, 2^30 + 1), closed into a triangle: lattice points with d in -5 .. 5 — d = +-1 and 0 among them,
+    where the plain f64 expression gives 0.0 — found by extended Euclid, and their mirror images under x -> -x."""
+    a, b = 2**30 + 3, 2**30 + 1
+    g, u, w = egcd(a, b)  # a u + b w = 1
+    assert g == 1
+    pts = []
+    for d in range(-5, 6):  # a Y - b X = d: Y = d u + t b, X = -d w + t a
+        y0, x0 = (d * u) % b, None
+        t = (y0 - d * u) // b
+        x0 = -d * w + t * a
+        assert a * y0 - b * x0 == d and 0 <= y0 < b
+        pts.append((x0, y0))
+        if d == 0:
+            pts.append((a, b))  # the edge's upper end: on it (d = 0), but Y = B.y
+    assert len(set(pts)) == len(pts)
+    assert (536870914, 536870913) in pts and (536870913, 536870912) in pts  # d = +1 and d = -1: 0.0 in f64
+    tri = [(0, 0), (a, b), (0, b)]
+    for sign in (1, -1):
+        v = [(sign * x, y) for x, y in tri]
+        k = 6
+        xyz = [np.full((n, 3), 7, dtype=np.int32) for n in NS]  # (7, 7, 7): d = 7 (a - b) = 14 > 0, far from the edge
+        xyz[k][:, 2] = 50
+        where = [3, 84, 85, 86, 170, 255, 256 + 85, 511, 512 + 17, 2048 + 85, 4096 + 1, 4096 + 20, 4096 + 36, 4132]
+        assert len(where) >= len(pts)
+        for i, (x, y) in zip(where, pts):
+            xyz[k][i] = sign * x, y, 50
+        dev.upload(xyz)
+        box = ([min(0, sign * a), 0, 0], [max(0, sign * a), b, 99])
+        want = sum(rule.inside_exact(x, y, v) for x, y, _ in xyz[k].tolist())
+        assert want == int(rule.counted(xyz[k], *box, v).sum())
+        ins = [rule.inside_exact(sign * x, y, v) for x, y in pts]
+        assert any(ins) and not all(ins)
+        assert dev.added([box], [v], [k]) == want, (sign, want)
+        for i, (x, y) in zip(where, pts):  # one at a time
+            one = ([sign * x, y, 0], [sign * x, y, 99])
+            assert dev.added([one], [v], [k]) == int(rule.inside_exact(sign * x, y, v)), (sign, x, y, a * y - b * x)
+
+
+# (e) ------------------------------------------------------------------------------------------------------------------
+def test_partition_and_odd_outlines(dev):
+    dev.upload(draw(np.random.default_rng(42), 200, 200, margin=10))
+    gon = regular(12, 100)
+    i, j = 2, 9
+    part1, part2 = gon[i:j + 1], gon[j:] + gon[:i + 1]
+    assert len(part1) + len(part2) == 14
+    boxes = [rule.bbox(shifted(gon, k), 5, 95) for k in ALL]
+    whole = dev.check(boxes, [shifted(gon, k) for k in ALL])
+    one = dev.check(boxes, [shifted(part1, k) for k in ALL])
+    two = dev.check(boxes, [shifted(part2, k) for k in ALL])
+    assert whole == one + two and 0 < one and 0 < two and whole < sum(NS)
+    # collinear and repeated vertices; a self-intersecting bow-tie
+    odd = [(10, 10), (60, 10), (110, 10), (110, 10), (160, 10), (160, 90), (160, 170), (85, 170), (85, 170), (10, 170), (10, 90), (10, 90)]
+    bow = [(10, 10), (190, 180), (190, 20), (10, 190)]
+    for v in (odd, bow):
+        assert 0 < dev.check([rule.bbox(shifted(v, k)) for k in ALL], [shifted(v, k) for k in ALL]) < sum(NS)
+
+
+# (f) ------------------------------------------------------------------------------------------------------------------
+def test_z_and_the_box_matter(dev):
+    dev.upload(draw(np.random.default_rng(43), 200, 200, margin=10))
+    outlines = [shifted(regular(7, 95), k) for k in ALL]
+    full = [rule.bbox(v) for v in outlines]
+    everything = dev.check(full, outlines)
+    slab = [([lo[0], lo[1], 30], [hi[0], hi[1], 60 + k]) for k, (lo, hi) in enumerate(full)]
+    narrow = [([lo[0] + 40, lo[1] + 55, -WIDE], [hi[0] - 30, hi[1] - 45, WIDE]) for lo, hi in full]
+    in_slab, in_narrow = dev.check(slab, outlines), dev.check(narrow, outlines)
+    assert 0 < in_slab < everything and 0 < in_narrow < everything
+
+
+# (g) ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("m", [3, 4, 255, 256])
+def test_vertex_counts(dev, m):
+    dev.upload(draw(np.random.default_rng(44 + m), 400, 400, margin=10))
+    outlines = [shifted(regular(m, 200, phase=0.1 + 0.05 * k), k) for k in ALL]
+    want = dev.check([rule.bbox(v, 3, 96) for v in outlines], outlines)
+    assert 0 < want < sum(NS)
+
+
+# (h) ------------------------------------------------------------------------------------------------------------------
+def swapped(seq, k, v):
+    out = list(seq)
+    out[k] = v
+    return out
+
+
+def test_refusals_leave_the_word_alone(dev):
+    dev.upload(draw(np.random.default_rng(45), 200, 200))
+    outlines = [shifted(regular(5, 100), k) for k in ALL]
+    boxes = [rule.bbox(v) for v in outlines]
+    dev.check(boxes, outlines)
+    good = [pkg.Predicate.bounds(lo, hi) for lo, hi in boxes]
+    dev.preset()
+
+    def refused(cols=dev.cols, preds=good, verts=outlines, d_total=None):
+        with pytest.raises(binding.PcqError) as e:
+            dev.launch(None, verts, cols=cols, preds=preds, d_total=d_total)
+        assert e.value.code == PCQ_ERR_ARG, e.value
+        assert dev.word() == SENTINEL
+
+    refused(d_total=0)                                                                          # a null argument
+    refused(verts=[v[:2] for v in outlines])                                                    # 2 vertices
+    refused(verts=[(v * 52)[:257] for v in outlines])                                           # 257 vertices
+    refused(preds=swapped(good, 3, pkg.Predicate.bounds_class(*boxes[3], 2)))                   # the wrong kind
+    c = dev.cols[5]
+    refused(cols=swapped(dev.cols, 5, binding.make_columns(xyz=c.xyz, n=100, xyz_stride=16)))   # stride 16
+    refused(cols=swapped(dev.cols, 5, binding.make_columns(xyz=c.xyz + 4, n=c.n - 1)))          # a misaligned block
+    refused(cols=swapped(dev.cols, 5, binding.make_columns(xyz=None, n=100)))                   # a null block with n > 0
+    three, top = [v[:3] for v in outlines], 2**31 - 1
+    for a in (0, 1):                                                                            # a hull of 2^31
+        turn = (lambda v: [(y, x) for x, y in v]) if a else (lambda v: v)
+        lo = [0, 0, 0]
+        lo[a] = -1
+        refused(preds=swapped(good, 2, pkg.Predicate.bounds(lo, [5, 5, 5])), verts=swapped(three, 2, turn([(0, 0), (top, 5), (0, 9)])))  # the box reaches it
+        refused(preds=swapped(good, 2, pkg.Predicate.bounds([0, 0, 0], [5, 5, 5])), verts=swapped(three, 2, turn([(-1, 0), (top, 5), (0, 9)])))
+    # one step less is accepted, and the table stored before the refusals serves the next call
+    ok = pkg.Predicate.bounds([0, 0, 0], [5, 5, 5])
+    dev.launch(None, swapped(three, 2, [(0, 0), (top, 5), (0, 9)]), preds=swapped(good, 2, ok))
+    dev.word()
+    dev.check(boxes, outlines)
+
+
+def test_an_empty_predicate_with_garbage_vertices_and_two_calls_add(dev):
+    dev.upload(draw(np.random.default_rng(46), 200, 200))
+    outlines = [shifted(regular(6, 100), k) for k in ALL]
+    boxes = [rule.bbox(v) for v in outlines]
+    everything = dev.check(boxes, outlines)
+    garbage = [(-2**31, 2**31 - 1), (2**31 - 1, -2**31), (-2**31, -2**31), (2**31 - 1, 2**31 - 1), (0, 0), (-2**31, 0)]
+    odd_boxes = [EMPTY if k % 2 else boxes[k] for k in ALL]
+    odd_outlines = [garbage if k % 2 else outlines[k] for k in ALL]
+    live = sum(int(rule.counted(dev.xyz[k], *boxes[k], outlines[k]).sum()) for k in ALL if k % 2 == 0)
+    assert dev.added(odd_boxes, odd_outlines) == live and 0 < live < everything
+    assert dev.added([EMPTY] * len(NS), [garbage] * len(NS)) == 0
+    assert dev.added([], [], ()) == 0  # nsegments == 0
+    dev.preset(1000)
+    dev.launch(boxes, outlines), dev.launch(odd_boxes, odd_outlines)
+    assert dev.word() == 1000 + everything + live
+
+
+def test_a_callers_stream_is_honoured(dev):
+    """The call held back behind torch work on a caller's stream returns while the stream is busy and counts right; a changed call
+    on the context's stream in between does not disturb it (test_gpu_batch_streams.py has the full story for the other kinds)."""
+    import torch
+    dev.upload(draw(np.random.default_rng(47), 200, 200))
+    first = [shifted(regular(8, 100), k) for k in ALL]
+    changed = [shifted(regular(8, 60), k) for k in ALL]
+    b1, b2 = [rule.bbox(v) for v in first], [rule.bbox(v) for v in changed]
+    w1, w2 = dev.want(b1, first), dev.want(b2, changed)
+    assert w1 != w2 and w1 > 0 and w2 > 0
+    d_other = dev.ctx.alloc(64)
+    try:
+        ts = torch.cuda.Stream()
+        with torch.cuda.stream(ts):
+            x = torch.zeros(1 << 27, device="cuda")  # 128 adds in place over 512 MiB: some tens of milliseconds
+            x.add_(1.0)
+        dev.preset(0)
+        dev.ctx.memset(d_other, 0, 8)
+        dev.launch(b1, first, stream=ts.cuda_stream)  # the table travels
+        ts.synchronize()
+        with torch.cuda.stream(ts):
+            for _ in range(128):
+                x.add_(1.0)
+        dev.launch(b1, first, stream=ts.cuda_stream)  # queued behind the filler, without a wait of the host's
+        assert not ts.query(), "the repeated call returned only when the stream had run empty"
+        dev.launch(b2, changed, d_total=d_other)      # another table on the context's stream
+        ts.synchronize()
+        other = np.zeros(1, dtype=np.uint64)
+        dev.ctx.to_host(other, d_other)
+        assert dev.word() == 2 * w1 and int(other[0]) == w2
+        del x
+    finally:
+        dev.ctx.free(d_other)
+
+
+def test_between_a_raster_call_and_a_box_call(dev):
+    """The segment tables of the three entries share one buffer under different keys: raster, polygon, box, polygon again"""
+    dev.upload(draw(np.random.default_rng(48), 64, 64, margin=4))
+    nx = ny = 8
+    cws = [(8, 8)] * len(NS)
+    rboxes = [([origin(k)[0], origin(k)[1], 0], [origin(k)[0] + 63, origin(k)[1] + 63, 99]) for k in ALL]
+    outlines = [shifted(regular(9, 30), k) for k in ALL]
+    pboxes = [rule.bbox(v) for v in outlines]
+    d_ras = dev.ctx.alloc(8 * nx * ny)
+    try:
+        dev.ctx.memset(d_ras, 0, 8 * nx * ny)
+        preds = [pkg.Predicate.bounds(lo, hi) for lo, hi in rboxes]
+        dev.ctx.scan_dev_raster_batch(dev.cols, preds, cws, nx, ny, d_ras)
+        got_poly = dev.added(pboxes, outlines)
+        dev.ctx.scan_dev_count_batch(dev.cols, preds, d_ras)  # (added to cell 0)
+        again = dev.added(pboxes, outlines)
+        ras = np.zeros(nx * ny, dtype=np.uint64)
+        dev.ctx.to_host(ras, d_ras)
+        in_box = sum(int(rule.in_box(dev.xyz[k], *rboxes[k]).sum()) for k in ALL)
+        assert got_poly == again == dev.want(pboxes, outlines) > 0
+        assert int(ras.sum()) == 2 * in_box > 0
+    finally:
+        dev.ctx.free(d_ras)

@@ -1,0 +1,101 @@
+"""Box AND polygon: the libpcq entry (include/pcq.h: pcq_scan_dev_count_batch_polygon) and the host entry (include/pcq_query.h:
+pcq_query_resident_count_polygon) are declared and exported beside the old batch entries with the vertex limit, the binding has the
+method, the ABI number is what it was, the host entry makes its three device-free checks in their order with a handle it never
+dereferences, and host/polygon_plan.h gives the numbers worked out by hand in tests/native/polygon_plan_driver.cpp, a stand-alone
+program built with ASan and UBSan.  No GPU call."""
+import ctypes as C
+import importlib
+import os
+import subprocess
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+PCQ_ERR_ARG = -8
+LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
+           "pcq_scan_dev_count_batch_multi", "pcq_scan_dev_class_hist_batch", "pcq_scan_dev_time_hist_batch", "pcq_scan_dev_raster_batch",
+           "pcq_scan_dev_zrange_raster_batch"]
+QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
+             "pcq_query_resident_count_bounds_many", "pcq_query_resident_count_bounds_by_class", "pcq_query_resident_count_bounds_by_time",
+             "pcq_query_resident_count_bounds_raster", "pcq_query_resident_bounds_zrange_raster"]
+
+
+def test_both_entries_are_declared_and_exported_beside_the_old_ones():
+    declared = pkg.declared_symbols(["pcq.h"])
+    exported = pkg.exported_symbols(pkg.lib_path())
+    for name in ["pcq_scan_dev_count_batch_polygon"] + LIB_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    declared = pkg.declared_symbols(["pcq_query.h"])
+    exported = pkg.exported_symbols(os.path.join(PKG, "libpcq_query.so"))
+    for name in ["pcq_query_resident_count_polygon"] + QUERY_OLD:
+        assert name in declared, name
+        assert name in exported, name
+    with open(os.path.join(ROOT, "include", "pcq.h")) as f:
+        text = f.read()
+    assert "#define PCQ_POLYGON_VERTS_MAX 256" in text
+    # the header carries the rule
+    for line in ("d = (B.x - A.x) * (Y - A.y) - (X - A.x) * (B.y - A.y)        (exact, in integers)",
+                 "The edge *crosses* the point iff `(A.y <= Y < B.y and d > 0)` or `(B.y <= Y < A.y and d < 0)`. A horizontal edge never crosses.",
+                 "The point is inside iff an odd number of edges cross it (even-odd rule)."):
+        assert line in text, line
+
+
+def test_abi_number_is_unchanged_and_the_binding_has_the_method():
+    assert pkg.load_library().pcq_abi_version() == 6
+    binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+    assert callable(binding.Context.scan_dev_count_batch_polygon)
+    assert callable(binding.Context.scan_dev_raster_batch) and callable(binding.Context.scan_dev_count_batch_multi)
+    assert pkg.load_library().pcq_scan_dev_count_batch_polygon.argtypes is not None
+
+
+def test_host_entry_checks_its_arguments_without_a_device():
+    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    lib.pcq_query_last_error.restype = C.c_char_p
+    f = lib.pcq_query_resident_count_polygon
+    f.argtypes = [C.c_void_p, C.c_size_t, dd, C.c_double, C.c_double, u64p, u64p]
+    dummy = C.c_void_p(1)  # never dereferenced: a check refuses first
+    inf, nan = float("inf"), float("nan")
+    tri = (C.c_double * 6)(0, 0, 1, 0, 0, 1)
+    many = (C.c_double * (2 * 300))(*[float(i % 7) for i in range(600)])
+    m, s = C.c_uint64(11), C.c_uint64(15)
+
+    def bad_at(i, v, n=3):
+        a = [float(j % 5) for j in range(2 * n)]
+        a[i] = v
+        return (C.c_double * (2 * n))(*a)
+
+    cases = [((None, 3, tri, 0.0, 1.0, C.byref(m)), b"null argument"), ((dummy, 3, None, 0.0, 1.0, C.byref(m)), b"null argument"),
+             ((dummy, 3, tri, 0.0, 1.0, None), b"null argument"), ((None, 0, None, 0.0, 1.0, None), b"null argument"),
+             ((dummy, 0, tri, 0.0, 1.0, C.byref(m)), b"vertices"), ((dummy, 2, tri, 0.0, 1.0, C.byref(m)), b"vertices"),
+             ((dummy, 257, many, 0.0, 1.0, C.byref(m)), b"vertices"), ((dummy, 2**64 - 1, many, 0.0, 1.0, C.byref(m)), b"vertices"),
+             ((dummy, 3, bad_at(0, nan), 0.0, 1.0, C.byref(m)), b"not finite"), ((dummy, 3, bad_at(5, inf), 0.0, 1.0, C.byref(m)), b"not finite"),
+             ((dummy, 3, bad_at(3, -inf), 0.0, 1.0, C.byref(m)), b"not finite"),
+             ((dummy, 256, bad_at(511, nan, 256), 0.0, 1.0, C.byref(m)), b"not finite")]
+    for args, text in cases:
+        for scanned in (C.byref(s), None):
+            assert f(*args, scanned) == PCQ_ERR_ARG, args
+            assert text in lib.pcq_query_last_error(), (args, lib.pcq_query_last_error())
+            assert m.value == 11 and s.value == 15
+    # a null output comes before the number of vertices, the number of vertices before the vertices' values (zmin > zmax is the dataset's)
+    assert f(dummy, 2, bad_at(0, nan), 5.0, -5.0, None, None) == PCQ_ERR_ARG and b"null argument" in lib.pcq_query_last_error()
+    assert f(dummy, 2, bad_at(0, nan), 5.0, -5.0, C.byref(m), None) == PCQ_ERR_ARG and b"vertices" in lib.pcq_query_last_error()
+    assert f(dummy, 3, bad_at(0, nan), 5.0, -5.0, C.byref(m), None) == PCQ_ERR_ARG and b"not finite" in lib.pcq_query_last_error()
+    assert m.value == 11 and s.value == 15
+
+
+def test_polygon_plan_under_address_sanitizer(tmp_path):
+    """host/polygon_plan.h against hand-worked numbers under ASan + UBSan, through a stand-alone program (nothing sanitized is loaded
+    into python; no device is touched): ties to even on both sides of zero, an anisotropic scale, INT32_MAX and one step beyond, spans of
+    2^31 - 1 and 2^31, bad scales, and the box of the rounded vertices."""
+    exe = str(tmp_path / "polygon_plan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
+           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "native", "polygon_plan_driver.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
+    assert r.stdout.split() == ["ok", "44"]
