@@ -1,0 +1,300 @@
+"""host/resident.cpp with more files than any batched kernel has workgroups: F = 16 * CUs + 37 small LAST files with GPS times,
+every resident batched query asked once against numpy on the files' stored integers.
+
+The kernels' side of this is test_gpu_many_segments.py; here the host layer builds the segment tables: one segment per surviving
+file, so a launch has F segments when the query's box meets every header.  Every file's header box is the same wide box (a header
+may be looser than its points), every query's box lies inside it, and points_scanned equal to the total point count is asserted:
+the header early-out dropped nothing and the launch really had F segments — more than the widest grid (16 * CUs: rasters and
+polygon), so the leftover loop of every kernel makes a second pass, and a third in 37 workgroups of the widest.
+
+Point counts come from the cycle 1, 3, 63, 64, 65, 200, 511 (no file reaches a whole step of 512 points: everything is
+leftovers).  All files share one z scale and offset, so the height raster stays one launch; two x / y scales are used in turn and
+every file has its own offset, so every segment's local box, cell widths and outline differ.
+
+The smallest F at which these assertions can still fail where the five-file resident tests cannot is grid + 1 per kind
+(test_gpu_many_segments.py lists them); F is that of the widest grid plus the 37 third passes.
+"""
+import ctypes as C
+import importlib
+import os
+import struct
+import sys
+import time
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _polygon_rule as rule  # noqa: E402
+import _time_images as ti  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+
+TIME = 2  # PCQ_RESIDENT_TIME
+CYCLE = (1, 3, 63, 64, 65, 200, 511)
+SCALES = ((0.01, 0.01, 0.01), (0.02, 0.02, 0.01))
+Z_OFFSET = 7.5
+WIDE = 1000.0  # every header: -WIDE .. WIDE on every axis
+BOX = ((-4.003, -2.001, 0.0), (4.5, 1.9, 14.0))
+BOXES9 = [((BOX[0][0] + 0.3 * j, BOX[0][1] + 0.1 * j, BOX[0][2] + j), (BOX[1][0] - 0.2 * j, BOX[1][1] - 0.15 * j, BOX[1][2] - 0.5 * j)) for j in range(9)]
+CLASS = 2
+RANGE = (1200.0, 1800.0)
+EDGES = np.asarray([1000.0, 1100.0, 1250.0, 1400.0, 1550.0, 1700.0, 1850.0, 1990.0])
+RASTER = ((-4.0, -2.0, 0.0), 14.0, 0.5, 16, 8)  # bmin, zmax, cell, nx, ny: 50 and 25 lattice steps per cell
+OUTLINE = ([(-3.5, -1.8), (4.2, -1.5), (0.5, 0.2), (3.9, 1.7), (-3.0, 1.6)], 0.0, 14.0)
+TIMES = {}
+
+
+class Q:
+    def __init__(self):
+        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
+        dd, dbl = P(C.c_double), C.c_double
+        lib.pcq_query_last_error.restype = C.c_char_p
+        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
+        lib.pcq_query_collector_free.argtypes = [vp]
+        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
+        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
+        lib.pcq_query_resident_free.argtypes = [vp]
+        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
+        lib.pcq_query_resident_count_class.argtypes = [vp, C.c_uint8, P(u64), P(u64)]
+        lib.pcq_query_resident_search_time.argtypes = [vp, dbl, dbl, vp]
+        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
+        lib.pcq_query_resident_count_bounds_time.argtypes = [vp, dd, dd, dbl, dbl, P(u64), P(u64)]
+        lib.pcq_query_resident_count_bounds_many.argtypes = [vp, C.c_size_t, dd, dd, P(u64), P(u64), P(u64)]
+        lib.pcq_query_resident_count_bounds_by_class.argtypes = [vp, dd, dd, P(u64), P(u64)]
+        lib.pcq_query_resident_count_bounds_by_time.argtypes = [vp, dd, dd, dd, C.c_size_t, P(u64), P(u64)]
+        lib.pcq_query_resident_count_bounds_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, P(u64), P(u64)]
+        lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, dd, dd, P(u64)]
+        lib.pcq_query_resident_count_polygon.argtypes = [vp, C.c_size_t, dd, dbl, dbl, P(u64), P(u64)]
+
+    def err(self):
+        return self.lib.pcq_query_last_error()
+
+    def counted(self, fn, *args):
+        """An entry that ends with (matches, points_scanned)"""
+        m, s = C.c_uint64(7), C.c_uint64(7)
+        rc = fn(*args, C.byref(m), C.byref(s))
+        assert rc == 0, self.err()
+        return m.value, s.value
+
+
+def d3(v):
+    return (C.c_double * 3)(*v)
+
+
+@pytest.fixture(scope="module")
+def q():
+    return Q()
+
+
+class Held:
+    """The files' stored integers, concatenated, with a per-point file index"""
+
+    def __init__(self, nfiles):
+        rng = np.random.default_rng(4133)
+        k = np.arange(nfiles)
+        self.n = np.asarray([CYCLE[i % 7] for i in range(nfiles)])
+        self.file = np.repeat(k, self.n)
+        self.start = np.cumsum(self.n) - self.n
+        N = int(self.n.sum())
+        coarse = (k % 2 == 1)[self.file]  # the 0.02 lattice: half the steps for the same world extent
+        self.xyz = np.stack([rng.integers(-600, 600, N) // np.where(coarse, 2, 1), rng.integers(-300, 300, N) // np.where(coarse, 2, 1),
+                             rng.integers(-1000, 1000, N)], axis=1).astype(np.int32)
+        self.cls = rng.choice(np.asarray([1, 2, 6], dtype=np.uint8), N)
+        self.t = rng.uniform(1000.0, 2000.0, N)
+        self.scale = [SCALES[i % 2] for i in range(nfiles)]
+        self.offset = [(-2.0 + 0.37 * (i % 11), -0.6 + 0.21 * (i % 7), Z_OFFSET) for i in range(nfiles)]
+
+    def local(self, box):
+        """pcq_box_to_local of the world box per file: ([F, 3] lmin, [F, 3] lmax)"""
+        lo, hi = [], []
+        for s, o in zip(self.scale, self.offset):
+            a, b = pkg.box_to_local(list(box[0]), list(box[1]), list(s), list(o))
+            lo.append(a), hi.append(b)
+        return np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
+
+    def inside(self, lo, hi):
+        """Per point: inside its file's local box, in int64"""
+        sel = np.ones(len(self.xyz), dtype=bool)
+        for a in range(3):
+            x = self.xyz[:, a].astype(np.int64)
+            sel &= (x >= lo[self.file, a]) & (x <= hi[self.file, a])
+        return sel
+
+    def in_box(self, box):
+        return self.inside(*self.local(box))
+
+    def in_range(self, t0, t1):
+        return (self.t >= t0) & (self.t < t1)
+
+
+@pytest.fixture(scope="module")
+def dataset(q, tmp_path_factory):
+    """F files written, loaded once with their time blocks; (handle, Held).  The time it takes is reported: F small files and
+    three device allocations each."""
+    began = time.perf_counter()
+    ctx = pkg.Context(0)
+    cus = ctx.device_info()["compute_units"]
+    ctx.close()
+    nfiles = 16 * cus + 37
+    held = Held(nfiles)
+    d = tmp_path_factory.mktemp("resident_many_files")
+    wide = b"".join(struct.pack("<2d", WIDE, -WIDE) for _ in range(3))
+    paths = []
+    none = np.zeros((0, 3), dtype=np.uint16)
+    made = time.perf_counter()
+    for k in range(nfiles):
+        a, b = int(held.start[k]), int(held.start[k] + held.n[k])
+        img = ti.last_image(1, held.xyz[a:b], held.cls[a:b], none, held.t[a:b], scale=held.scale[k], offset=held.offset[k]).copy()
+        img[179:179 + 48] = np.frombuffer(wide, dtype=np.uint8)
+        p = str(d / f"f{k}.last")
+        img.tofile(p)
+        paths.append(p)
+    written = time.perf_counter()
+    arr = (C.c_char_p * nfiles)(*[p.encode() for p in paths])
+    h = C.c_void_p()
+    assert q.lib.pcq_query_resident_load_with(0, arr, nfiles, TIME, C.byref(h)) == 0, q.err()
+    loaded = time.perf_counter()
+    TIMES["fixture"] = loaded - began
+    print(f"\n{cus} CUs, F = {nfiles} files, {int(held.n.sum())} points: numpy data {made - began:.2f} s, files written {written - made:.2f} s, "
+          f"loaded into HBM {loaded - written:.2f} s", file=sys.stderr)
+    yield h, held
+    q.lib.pcq_query_resident_free(h)
+
+
+def test_box(q, dataset):
+    r, held = dataset
+    m, s = q.counted(q.lib.pcq_query_resident_count_bounds, r, d3(BOX[0]), d3(BOX[1]))
+    want = int(held.in_box(BOX).sum())
+    assert s == len(held.xyz) and m == want and 0 < want < s
+
+
+def test_class(q, dataset):
+    r, held = dataset
+    m, s = q.counted(q.lib.pcq_query_resident_count_class, r, CLASS)
+    assert s == len(held.xyz) and m == int((held.cls == CLASS).sum()) > 0
+
+
+def test_time(q, dataset):
+    """No batched entry: the per-file time search through each file's chunk index, into a count collector"""
+    r, held = dataset
+    c = C.c_void_p()
+    assert q.lib.pcq_query_collector_new_count(0, C.byref(c)) == 0, q.err()
+    try:
+        assert q.lib.pcq_query_resident_search_time(r, RANGE[0], RANGE[1], c) == 0, q.err()
+        n = C.c_uint64(7)
+        assert q.lib.pcq_query_collector_point_count(c, C.byref(n)) == 0, q.err()
+    finally:
+        q.lib.pcq_query_collector_free(c)
+    assert n.value == int(held.in_range(*RANGE).sum()) > 0
+
+
+def test_box_and_class(q, dataset):
+    r, held = dataset
+    m, s = q.counted(q.lib.pcq_query_resident_count_bounds_class, r, d3(BOX[0]), d3(BOX[1]), CLASS)
+    assert s == len(held.xyz) and m == int((held.in_box(BOX) & (held.cls == CLASS)).sum()) > 0
+
+
+def test_box_and_time(q, dataset):
+    r, held = dataset
+    m, s = q.counted(q.lib.pcq_query_resident_count_bounds_time, r, d3(BOX[0]), d3(BOX[1]), RANGE[0], RANGE[1])
+    assert s == len(held.xyz) and m == int((held.in_box(BOX) & held.in_range(*RANGE)).sum()) > 0
+
+
+def test_nine_boxes(q, dataset):
+    """A group of eight and a group of one"""
+    r, held = dataset
+    n = len(BOXES9)
+    lo = (C.c_double * (3 * n))(*[v for b in BOXES9 for v in b[0]])
+    hi = (C.c_double * (3 * n))(*[v for b in BOXES9 for v in b[1]])
+    m, s = (C.c_uint64 * n)(*[77] * n), (C.c_uint64 * n)(*[77] * n)
+    read = C.c_uint64(77)
+    assert q.lib.pcq_query_resident_count_bounds_many(r, n, lo, hi, m, s, C.byref(read)) == 0, q.err()
+    want = [int(held.in_box(b).sum()) for b in BOXES9]
+    assert list(m) == want and len(set(want)) == n and min(want) > 0
+    assert list(s) == [len(held.xyz)] * n and read.value == 2 * len(held.xyz)
+
+
+def test_by_class(q, dataset):
+    r, held = dataset
+    hist = np.full(256, 77, dtype=np.uint64)
+    s = C.c_uint64(7)
+    assert q.lib.pcq_query_resident_count_bounds_by_class(r, d3(BOX[0]), d3(BOX[1]), hist.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(s)) == 0, q.err()
+    want = np.bincount(held.cls[held.in_box(BOX)], minlength=256)
+    assert s.value == len(held.xyz) and np.array_equal(hist.astype(np.int64), want) and (want > 0).sum() == 3
+
+
+def test_by_time(q, dataset):
+    r, held = dataset
+    nbins = len(EDGES) - 1
+    hist = np.full(nbins, 77, dtype=np.uint64)
+    s = C.c_uint64(7)
+    assert q.lib.pcq_query_resident_count_bounds_by_time(r, d3(BOX[0]), d3(BOX[1]), EDGES.ctypes.data_as(C.POINTER(C.c_double)), nbins,
+                                                         hist.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(s)) == 0, q.err()
+    sel = held.in_box(BOX)
+    want = [int((sel & held.in_range(EDGES[b], EDGES[b + 1])).sum()) for b in range(nbins)]
+    assert s.value == len(held.xyz) and hist.astype(np.int64).tolist() == want and min(want) > 0 and sum(want) < sel.sum()
+
+
+def raster_cells(held):
+    """Per point: inside its file's raster box (lmin .. lmin + n k - 1 on x and y, the converted z range), and its cell"""
+    bmin, zmax, cell, nx, ny = RASTER
+    box = (tuple(bmin), (bmin[0] + nx * cell, bmin[1] + ny * cell, zmax))
+    lo, hi = held.local(box)
+    k = np.asarray([[round(cell / s[a]) for a in range(2)] for s in held.scale], dtype=np.int64)
+    assert all(abs(cell / s[a] - round(cell / s[a])) <= 1e-9 * round(cell / s[a]) for s in SCALES for a in range(2))
+    hi[:, 0], hi[:, 1] = lo[:, 0] + nx * k[:, 0] - 1, lo[:, 1] + ny * k[:, 1] - 1
+    sel = held.inside(lo, hi)
+    f = held.file[sel]
+    cx = (held.xyz[sel, 0].astype(np.int64) - lo[f, 0]) // k[f, 0]
+    cy = (held.xyz[sel, 1].astype(np.int64) - lo[f, 1]) // k[f, 1]
+    return sel, cy * nx + cx
+
+
+def test_density_raster(q, dataset):
+    r, held = dataset
+    bmin, zmax, cell, nx, ny = RASTER
+    words = np.full(nx * ny, 77, dtype=np.uint64)
+    s = C.c_uint64(7)
+    assert q.lib.pcq_query_resident_count_bounds_raster(r, d3(bmin), zmax, cell, nx, ny, words.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(s)) == 0, q.err()
+    sel, cells = raster_cells(held)
+    want = np.bincount(cells, minlength=nx * ny)
+    assert s.value == len(held.xyz) and np.array_equal(words.astype(np.int64), want) and want.min() > 0
+
+
+def test_height_raster(q, dataset):
+    r, held = dataset
+    bmin, zmax, cell, nx, ny = RASTER
+    zlo, zhi = np.full(nx * ny, 77.5), np.full(nx * ny, -77.25)
+    s = C.c_uint64(7)
+    dd = C.POINTER(C.c_double)
+    assert q.lib.pcq_query_resident_bounds_zrange_raster(r, d3(bmin), zmax, cell, nx, ny, zlo.ctypes.data_as(dd), zhi.ctypes.data_as(dd), C.byref(s)) == 0, q.err()
+    sel, cells = raster_cells(held)
+    z = held.xyz[sel, 2].astype(np.float64) * SCALES[0][2] + Z_OFFSET  # (Z as f64 * scale[2]) + offset[2], two roundings
+    lo, hi = np.full(nx * ny, np.nan), np.full(nx * ny, np.nan)
+    np.fmin.at(lo, cells, z), np.fmax.at(hi, cells, z)
+    assert s.value == len(held.xyz) and not np.isnan(lo).any() and (lo < hi).all()
+    assert np.array_equal(zlo.view(np.uint64), lo.view(np.uint64)) and np.array_equal(zhi.view(np.uint64), hi.view(np.uint64))
+
+
+def test_polygon(q, dataset):
+    r, held = dataset
+    xy, zmin, zmax = OUTLINE
+    flat = [float(c) for p in xy for c in p]
+    m, s = q.counted(q.lib.pcq_query_resident_count_polygon, r, len(xy), (C.c_double * len(flat))(*flat), zmin, zmax)
+    v = np.asarray(xy, dtype=np.float64)
+    box = ((v[:, 0].min(), v[:, 1].min(), zmin), (v[:, 0].max(), v[:, 1].max(), zmax))
+    lo, hi = held.local(box)
+    want = 0
+    for k in range(len(held.n)):
+        lv = np.stack([np.rint((v[:, a] - np.float64(held.offset[k][a])) / np.float64(held.scale[k][a])) for a in range(2)], axis=1).astype(np.int64)
+        a, b = int(held.start[k]), int(held.start[k] + held.n[k])
+        flo, fhi = [int(lv[:, 0].min()), int(lv[:, 1].min()), int(lo[k, 2])], [int(lv[:, 0].max()), int(lv[:, 1].max()), int(hi[k, 2])]
+        want += int(rule.counted(held.xyz[a:b], flo, fhi, lv.tolist()).sum())
+    in_hull = int(held.in_box(box).sum())
+    assert s == len(held.xyz) and m == want and 0 < want < in_hull  # the concave outline cuts something out of its box
