@@ -19,6 +19,7 @@ PCQ_OK = 0
 PCQ_ERR_IO, PCQ_ERR_HEADER, PCQ_ERR_FORMAT, PCQ_ERR_EXTENSION, PCQ_ERR_EOF = -1, -2, -3, -4, -5
 PCQ_ERR_GRID, PCQ_ERR_PANIC, PCQ_ERR_ARG, PCQ_ERR_HIP, PCQ_ERR_CAPACITY = -6, -7, -8, -9, -10
 PCQ_ERR_UNSUPPORTED, PCQ_ERR_NOMEM = -11, -12
+PCQ_RESIDENT_COLOUR, PCQ_RESIDENT_TIME = 1, 2   # include/pcq_query.h: the `blocks` bits of pcq_query_resident_load_with
 PRED_BOUNDS, PRED_CLASS, PRED_BOUNDS_F64, PRED_TIME, PRED_BOUNDS_CLASS, PRED_BOUNDS_TIME = 0, 1, 2, 3, 4, 5
 
 # readers/src/lib.rs:10-19 — packed 31-byte result record

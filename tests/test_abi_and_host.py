@@ -45,10 +45,9 @@ def test_libpcq_query_exports_every_declared_symbol():
     declared = pkg.declared_symbols(["pcq_query.h"])
     declared = [s for s in declared if s.startswith("pcq_query")]
     assert len(declared) >= 15
-    path = os.path.join(PKG, "libpcq_query.so")
-    exported = pkg.exported_symbols(path)
+    exported = pkg.exported_symbols(pkg.query_lib_path())
     assert [s for s in declared if s not in exported] == []
-    C.CDLL(path)
+    pkg.load_query_library()
 
 
 def test_product_library_ships_no_lab_code():
@@ -96,8 +95,6 @@ def test_the_query_binary_has_no_test_hooks():
 def _schedule(qlib, cost, ready_ms, ms_per_unit=1.0):
     n, k = len(cost), len(ready_ms)
     slot, home, end = (C.c_int * n)(), (C.c_int * n)(), C.c_double()
-    qlib.pcq_query_simulate_schedule.argtypes = [C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_double), C.c_int, C.c_double,
-                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     assert qlib.pcq_query_simulate_schedule((C.c_uint64 * n)(*cost), n, (C.c_double * k)(*ready_ms), k, ms_per_unit, slot, home, C.byref(end)) == 0
     return list(slot), list(home), end.value
 
@@ -162,22 +159,9 @@ def test_box_to_local_matches_golden_and_oracle(oracle):
         assert pkg.box_to_local(lo, hi, sc, off) == want
 
 
-class HeaderInfo(C.Structure):
-    _fields_ = [("version_major", C.c_uint8), ("version_minor", C.c_uint8), ("point_data_record_format", C.c_uint8),
-                ("_pad", C.c_uint8), ("header_size", C.c_uint16), ("point_data_record_length", C.c_uint16),
-                ("offset_to_point_data", C.c_uint32), ("_pad2", C.c_uint32), ("number_of_points", C.c_uint64),
-                ("scale", C.c_double * 3), ("offset", C.c_double * 3), ("min", C.c_double * 3), ("max", C.c_double * 3)]
-
-
 @pytest.fixture(scope="module")
 def qlib():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_parse_las_header.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(HeaderInfo)]
-    lib.pcq_query_parse_aabb.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.pcq_query_is_valid_file.argtypes = [C.c_char_p]
-    lib.pcq_query_collector_new_count.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    return lib
+    return pkg.load_query_library()
 
 
 def _mutations(image: np.ndarray):
@@ -208,7 +192,7 @@ def test_host_header_parse_matches_oracle(oracle, qlib):
     for name, img in _mutations(last):
         img = np.ascontiguousarray(img)
         for mask in (0, 1):
-            h = HeaderInfo()
+            h = pkg.LasHeaderInfo()
             rc = qlib.pcq_query_parse_las_header(img.ctypes.data_as(C.c_void_p), img.size, mask, C.byref(h))
             try:
                 oh = oracle.parse_header(img.tobytes(), bool(mask))
@@ -287,7 +271,6 @@ def test_get_total_bounds_is_the_union_of_header_boxes(oracle, qlib, tmp_path):
         paths.append(p)
         mins.append(list(h.min))
         maxs.append(list(h.max))
-    qlib.pcq_query_get_total_bounds.argtypes = [C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
     mn, mx = (C.c_double * 3)(), (C.c_double * 3)()
     assert qlib.pcq_query_get_total_bounds(arr, len(paths), mn, mx) == 0

@@ -5,13 +5,14 @@ from python, and from a stand-alone driver built with ASan and UBSan (tests/nati
 import ctypes as C
 import importlib
 import os
-import subprocess
+
+import _host
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
            "pcq_scan_dev_count_batch_multi"]
 QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
@@ -41,10 +42,7 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_method():
 
 
 def test_host_entry_refuses_null_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_count_bounds_by_class.argtypes = [C.c_void_p, dd, dd, u64p, u64p]
+    lib = pkg.load_query_library()
     dummy = C.c_void_p(1)  # never dereferenced: another argument is null
     lo, hi = (C.c_double * 3)(0, 0, 0), (C.c_double * 3)(1, 1, 1)
     sentinel = [1000 + 7 * c for c in range(256)]
@@ -63,14 +61,8 @@ def test_host_entry_under_address_sanitizer(tmp_path):
     built sanitized into the program, where their definitions come first; the rest of the host layer is the libpcq_query.so
     beside them, which keeps the build to a few seconds."""
     host = os.path.join(PKG, "host")
-    exe = str(tmp_path / "class_hist_asan")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread",
            "-I" + os.path.join(ROOT, "include"), "-I" + host, os.path.join(ROOT, "tests", "native", "class_hist_asan_driver.cpp"),
-           os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG,
-           "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+           os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
-    assert r.stdout.split() == ["ok", "10"]
+    assert _host.build_and_run(tmp_path, "class_hist_asan", cmd, env) == ["ok", "10"]

@@ -19,6 +19,7 @@ import _time_images as ti  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
 QUERY = os.path.join(PKG, "host", "query")
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
 NEITHER = "Error: Found neither BOUNDS nor CLASS argument but exactly one of these arguments is required!"
@@ -93,11 +94,7 @@ def _write(path, img):
 
 @pytest.fixture(scope="module")
 def qlib():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    lib.pcq_query_test_plan_combined.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double,
-                                                 C.POINTER(binding.Columns), C.POINTER(binding.Predicate), C.POINTER(C.c_int)]
-    lib.pcq_query_last_error.restype = C.c_char_p
-    return lib
+    return pkg.load_query_library()
 
 
 def _plan(qlib, path, bmin, bmax, cls=-1, start=0.0, end=0.0):
@@ -209,7 +206,7 @@ def test_query_library_exports_the_combined_searches():
                      r"int optimized,\s+pcq_host_collector \*c\);", hdr)
     assert re.search(r"int pcq_query_search_file_bounds_time\(const char \*path, const double bmin\[3\], const double bmax\[3\], double start, "
                      r"double end, int optimized,\s+pcq_host_collector \*c\);", hdr)
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    lib = pkg.load_query_library()
     for sym in ("pcq_query_search_file_bounds_class", "pcq_query_search_file_bounds_time", "pcq_query_test_plan_combined"):
         assert hasattr(lib, sym), sym
     pcq_h = open(os.path.join(ROOT, "include", "pcq.h")).read()

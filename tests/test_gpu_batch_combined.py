@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 I32_MAX = 2**31 - 1
 
 SIZES = [30_011, 1, 255, 1_100_003, 256, 511, 50_000, 512, 513, 70_003, 1027, 41_999, 20_001, 33_333, 12_345, 60_001]

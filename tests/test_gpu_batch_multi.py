@@ -17,7 +17,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
 NS = (0, 1, 511, 512, 513, 1535, 4133)
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
 VARIED = (6, 2)  # the (segment, query) whose box changes from one call to the next
 PRESET = [1000 + 7 * q for q in range(8)]

@@ -26,7 +26,7 @@ binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 NS = (0, 1, 511, 512, 513, 1535, 4133)
 CLASS_PHASES = (0, 5, 2, 7, 8, 13, 3)  # byte phases of the class pieces in a 16-byte line: 1, 2, 3, 0, 1, 3 modulo 4 for the six non-empty segments
 STRIDE_SEG = 3                          # the 512-point segment whose x encodes the point index
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
 BINS = 256
 PRESET = np.asarray([1000 + 7 * c for c in range(BINS)], dtype=np.uint64)

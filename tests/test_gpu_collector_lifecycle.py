@@ -469,14 +469,6 @@ def test_host_collectors_across_files_searches_and_reads(oracle, tmp_path):
     search in a LAZER file) fails the same way on both sides and leaves the collectors as they were."""
     q = Q()
     lib = q.lib
-    vp, dd = C.c_void_p, C.POINTER(C.c_double)
-    lib.pcq_query_search_file_time.argtypes = [C.c_char_p, C.c_double, C.c_double, C.c_int, vp]
-    lib.pcq_query_search_file_bounds_class.argtypes = [C.c_char_p, dd, dd, C.c_uint8, C.c_int, vp]
-    lib.pcq_query_search_file_bounds_time.argtypes = [C.c_char_p, dd, dd, C.c_double, C.c_double, C.c_int, vp]
-    lib.pcq_query_resident_load_points.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(vp)]
-    lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
-    lib.pcq_query_resident_search_class.argtypes = [vp, C.c_uint8, vp]
-    lib.pcq_query_resident_free.argtypes = [vp]
     rng = np.random.default_rng(4100 + cm.SEED_BASE)
     files = []
     for k, (fmt, layout) in enumerate([(1, "las"), (3, "las"), (7, "las"), (3, "last"), (6, "last"), (2, "last"), (3, "lazer")]):
@@ -493,7 +485,7 @@ def test_host_collectors_across_files_searches_and_reads(oracle, tmp_path):
              ((500.0, 500.0, 500.0), (600.0, 600.0, 600.0))]
     calls = [(s, f) for s in ("bounds", "class", "time", "bounds_class", "bounds_time") for f in files] + [("resident_bounds", None), ("resident_class", None)] * 2
     calls = [calls[i] for i in rng.permutation(len(calls))]
-    res = vp()
+    res = C.c_void_p()
     arr = (C.c_char_p * len(lasts))(*[p.encode() for p in lasts])
     assert lib.pcq_query_resident_load_points(0, arr, len(lasts), C.byref(res)) == 0, lib.pcq_query_last_error()
     hs = {"count": q.collector("count"), "buffer": q.collector("buffer"), "grid": q.collector("grid", grid_box[0], grid_box[1], cell)}

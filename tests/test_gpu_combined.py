@@ -557,13 +557,8 @@ def test_cli_regular_implementation_fails_like_the_other_searches(tmp_path):
 
 
 def test_c_view_search_file_bounds_class_and_time(tmp_path):
-    q = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
+    q = pkg.load_query_library()
     D3 = C.c_double * 3
-    q.pcq_query_search_file_bounds_class.argtypes = [C.c_char_p, D3, D3, C.c_uint8, C.c_int, C.c_void_p]
-    q.pcq_query_search_file_bounds_time.argtypes = [C.c_char_p, D3, D3, C.c_double, C.c_double, C.c_int, C.c_void_p]
-    q.pcq_query_collector_new_count.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    q.pcq_query_collector_point_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    q.pcq_query_collector_free.argtypes = [C.c_void_p]
     xyz, cls, rgb, t = ti.points(10_000, 3)
     bmin, bmax = (60.0, -250.0, -20.0), (140.0, -150.0, 40.0)
     lmin, lmax = pkg.box_to_local(bmin, bmax, list(ti.SCALE), list(ti.OFFSET))

@@ -13,6 +13,9 @@ import sys
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,60 +29,19 @@ POINT_DTYPE = pkg.POINT_DTYPE
 
 
 class Q:
-    """ctypes view of include/pcq_query.h"""
+    """include/pcq_query.h through the package's view; the collector calls are tests/_host.py's"""
 
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
-        lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, P(vp)]
-        lib.pcq_query_collector_new_grid.argtypes = [C.c_int, dd, dd, C.c_double, P(vp)]
-        lib.pcq_query_collector_free.argtypes = [vp]
-        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
-        lib.pcq_query_collector_has_points.argtypes = [vp]
-        lib.pcq_query_collector_points.argtypes = [vp, vp, u64, P(u64)]
-        lib.pcq_query_collector_grid_cells.argtypes = [vp, vp, u64, P(u64)]
-        lib.pcq_query_search_file_bounds.argtypes = [C.c_char_p, dd, dd, C.c_int, vp, P(C.c_int)]
-        lib.pcq_query_search_file_class.argtypes = [C.c_char_p, C.c_uint8, C.c_int, vp]
-        lib.pcq_query_test_plan_replace_execute.argtypes = [C.c_char_p, C.c_char_p, dd, dd, vp]
+        self.lib = _host.lib()
+
+    d3 = staticmethod(_host.d3)
+    count = staticmethod(_host.count)
+    points = staticmethod(_host.points)
+    cells = staticmethod(_host.cells)
 
     @staticmethod
-    def d3(v):
-        return (C.c_double * 3)(*[float(x) for x in v])
-
-    def collector(self, kind, bmin=None, bmax=None, cell=None):
-        h = C.c_void_p()
-        if kind == "count":
-            rc = self.lib.pcq_query_collector_new_count(0, C.byref(h))
-        elif kind == "buffer":
-            rc = self.lib.pcq_query_collector_new_buffer(0, C.byref(h))
-        else:
-            rc = self.lib.pcq_query_collector_new_grid(0, self.d3(bmin), self.d3(bmax), cell, C.byref(h))
-        assert rc == 0, self.lib.pcq_query_last_error()
-        return h
-
-    def count(self, h):
-        n = C.c_uint64()
-        assert self.lib.pcq_query_collector_point_count(h, C.byref(n)) == 0, self.lib.pcq_query_last_error()
-        return n.value
-
-    def points(self, h):
-        n = C.c_uint64()
-        assert self.lib.pcq_query_collector_points(h, None, 0, C.byref(n)) == 0
-        out = np.zeros(n.value, dtype=POINT_DTYPE)
-        if n.value:
-            assert self.lib.pcq_query_collector_points(h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
-        return out
-
-    def cells(self, h):
-        n = C.c_uint64()
-        assert self.lib.pcq_query_collector_grid_cells(h, None, 0, C.byref(n)) == 0
-        out = np.zeros(n.value, dtype=np.uint64)
-        if n.value:
-            assert self.lib.pcq_query_collector_grid_cells(h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
-        return out
+    def collector(kind, bmin=None, bmax=None, cell=None):
+        return _host.collector(kind, (bmin, bmax, cell))
 
     def search_bounds(self, path, bmin, bmax, h, optimized=1):
         rec = C.c_int(-1)
@@ -89,8 +51,9 @@ class Q:
     def search_class(self, path, cls, h, optimized=1):
         return self.lib.pcq_query_search_file_class(path.encode(), cls, optimized, h)
 
-    def free(self, h):
-        self.lib.pcq_query_collector_free(h)
+    @staticmethod
+    def free(h):
+        _host.free_collector(h)
 
 
 @pytest.fixture(scope="module")
@@ -631,11 +594,6 @@ def test_resident_dataset_batched_counts_equal_per_file_searches(oracle, q, file
     prologue (early-out, box conversion) plus ONE batched launch.  Same totals as the per-file searches of the oracle."""
     lasts = [f for f in files if f.endswith(".last")]
     lib = q.lib
-    lib.pcq_query_resident_load.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_void_p)]
-    lib.pcq_query_resident_free.argtypes = [C.c_void_p]
-    lib.pcq_query_resident_count_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
-                                                    C.POINTER(C.c_uint64)]
-    lib.pcq_query_resident_count_class.argtypes = [C.c_void_p, C.c_uint8, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     arr = (C.c_char_p * len(lasts))(*[p.encode() for p in lasts])
     h = C.c_void_p()
     assert lib.pcq_query_resident_load(0, arr, len(lasts), C.byref(h)) == 0, lib.pcq_query_last_error()

@@ -36,7 +36,7 @@ T0, T1 = 1000.0, 2000.0
 SC = dict(scale=list(ti.SCALE), offset=list(ti.OFFSET))
 PAIRS = [(b, t) for b in (NONE, SCAN, ALL) for t in (NONE, SCAN, ALL)]
 SECOND_TILE_ONLY = 5
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 
 
 class Dev:

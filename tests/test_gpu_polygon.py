@@ -24,7 +24,7 @@ binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
 NS = (0, 1, 511, 512, 513, 1535, 4133)
 ALL = tuple(range(len(NS)))
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 SENTINEL = 0x5EED0000BEEF
 EMPTY = ([5, 5, 5], [4, 4, 4])
 WIDE = 2**40

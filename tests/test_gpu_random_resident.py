@@ -8,6 +8,7 @@ histograms, every raster cell — both rasters have more cells than one launch h
 the world z of the height raster bit for bit with NaN where no point lies, and points_scanned / points_read.
 """
 import ctypes as C
+import importlib
 import os
 import sys
 
@@ -19,29 +20,14 @@ import _random_resident as rr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "adhoc-queries-pointclouds_amd")
-PCQ_RESIDENT_TIME = 2
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+PCQ_RESIDENT_TIME = pkg.PCQ_RESIDENT_TIME
 SENTINEL = 77
 
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd, dbl = P(C.c_double), C.c_double
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_class.argtypes = [vp, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_time.argtypes = [vp, dd, dd, dbl, dbl, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_many.argtypes = [vp, C.c_size_t, dd, dd, P(u64), P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_class.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_time.argtypes = [vp, dd, dd, dd, C.c_size_t, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, P(u64), P(u64)]
-        lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, dd, dd, P(u64)]
-        lib.pcq_query_resident_count_polygon.argtypes = [vp, C.c_size_t, dd, dbl, dbl, P(u64), P(u64)]
+        self.lib = pkg.load_query_library()
 
     def err(self):
         return self.lib.pcq_query_last_error()
@@ -52,8 +38,7 @@ def q():
     return Q()
 
 
-def d3(v):
-    return (C.c_double * 3)(*[float(x) for x in v])
+d3 = pkg.d3
 
 
 def u64s(n):

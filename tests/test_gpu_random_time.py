@@ -49,11 +49,6 @@ SPECIALS = np.concatenate([[np.nan, -np.nan, np.inf, -np.inf, 0.0, -0.0, 5e-324,
 
 def view_q():
     q = Q()
-    D3, vp = C.c_double * 3, C.c_void_p
-    q.lib.pcq_query_search_file_time.argtypes = [C.c_char_p, C.c_double, C.c_double, C.c_int, vp]
-    q.lib.pcq_query_search_file_bounds_class.argtypes = [C.c_char_p, D3, D3, C.c_uint8, C.c_int, vp]
-    q.lib.pcq_query_search_file_bounds_time.argtypes = [C.c_char_p, D3, D3, C.c_double, C.c_double, C.c_int, vp]
-    q.lib.pcq_query_last_error.restype = C.c_char_p
     return q
 
 

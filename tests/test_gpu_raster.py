@@ -23,7 +23,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
 NS = (0, 1, 511, 512, 513, 1535, 4133)
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
 CELLS_MAX = 8192
 WORDS = CELLS_MAX + 64

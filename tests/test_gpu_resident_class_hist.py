@@ -3,39 +3,32 @@ pcq_query_resident_count_bounds_by_class must give, for every class byte c in 0.
 pcq_query_resident_count_bounds_class gives for c — zeros included — with the same points_scanned, and its bins must sum to what
 pcq_query_resident_count_bounds counts.
 
-Five small LAST files written here as tests/test_gpu_resident_multi.py writes its own: formats 1, 3 and 6; 3*4096+17, 4096, 100, 0
+The five small LAST files of tests/_resident_files.py (FIVE_FILES), with classes of its own: formats 1, 3 and 6; 3*4096+17, 4096, 100, 0
 and 2*4096+5 points; differing scales and offsets, one of them anisotropic; and one file whose header bounds are tighter than its
 points, so that the header early-out (last.rs:92-94) is observable.  Classes are drawn from {0, 1, 2, 5, 6, 255}.
 """
 import ctypes as C
 import importlib
 import os
-import struct
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
-import _time_images as ti  # noqa: E402
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_PANIC = -7
-TIME = 2
+PCQ_ERR_PANIC = pkg.PCQ_ERR_PANIC
+TIME = pkg.PCQ_RESIDENT_TIME
 CLASSES = (0, 1, 2, 5, 6, 255)
-ISO = (0.01, 0.01, 0.01)
-# (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
-FILES = [(1, 3 * 4096 + 17, ti.SCALE, ti.OFFSET),             # world x [50, 150), y [-300, -100), z [-42.5, 57.5): anisotropic
-         (3, 4096, ISO, (0.0, 0.0, 0.0)),                      # x, y [-50, 50), z [-10, 10)
-         (6, 100, (0.001, 0.001, 0.001), (100.0, -200.0, 0.0)),  # x [95, 105), y [-205, -195), z [-1, 1)
-         (1, 0, ISO, (0.0, 0.0, 0.0)),
-         (3, 2 * 4096 + 5, ISO, (300.0, 0.0, 0.0))]            # x [250, 350): its header says x <= 300
-LYING, LYING_XMAX = 4, 300.0
+FILES = rf.FIVE_FILES
+meets = rf.meets
+LYING = rf.LYING
 BIG = 1e6
 BOXES = {"every": ((-BIG, -BIG, -BIG), (BIG, BIG, BIG)),                # meets every header
          "single": ((-20.0, -20.0, -5.0), (20.0, 20.0, 5.0)),            # a single file
@@ -46,34 +39,11 @@ BOXES = {"every": ((-BIG, -BIG, -BIG), (BIG, BIG, BIG)),                # meets 
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_class.argtypes = [vp, dd, dd, P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths, blocks=None):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        if blocks is None:
-            rc = self.lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h))
-        else:
-            rc = self.lib.pcq_query_resident_load_with(0, arr, len(paths), blocks, C.byref(h))
-        assert rc == 0, self.err()
-        return h
-
-    def bounds(self, r, box):
-        m, s = C.c_uint64(7), C.c_uint64(7)
-        rc = self.lib.pcq_query_resident_count_bounds(r, (C.c_double * 3)(*box[0]), (C.c_double * 3)(*box[1]), C.byref(m), C.byref(s))
-        return rc, m.value, s.value
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
+    bounds = staticmethod(_host.bounds)
 
     def one_class(self, r, box, c):
         m, s = C.c_uint64(7), C.c_uint64(7)
@@ -92,31 +62,14 @@ def q():
     return Q()
 
 
+def corpus(d):
+    return rf.write_files(d, FILES, 950, LYING, classes=CLASSES)
+
+
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    """The five files, and per file (xyz, cls, scale, offset, header min, header max)."""
-    d = tmp_path_factory.mktemp("resident_class_hist")
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(FILES):
-        xyz, _, rgb, t = ti.points(n, 950 + k)
-        cls = np.random.default_rng(960 + k).choice(np.asarray(CLASSES, dtype=np.uint8), n)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset).copy()
-        w = ti.world(xyz, scale, offset) if n else np.zeros((1, 3))
-        hmin, hmax = w.min(axis=0), w.max(axis=0)
-        if k == LYING:
-            assert hmax[0] > LYING_XMAX + 40.0
-            hmax[0] = LYING_XMAX
-            img[179:195] = np.frombuffer(struct.pack("<2d", hmax[0], hmin[0]), dtype=np.uint8)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, cls, scale, offset, hmin, hmax))
-    return paths, held
-
-
-def meets(h, box):
-    """The header early-out: the file's header AABB meets the box (inclusive)."""
-    return bool(np.all(h[4] <= np.asarray(box[1])) and np.all(h[5] >= np.asarray(box[0])))
+    """The files, and per file what tests/_resident_files.py holds of it."""
+    return corpus(tmp_path_factory.mktemp("resident_class_hist"))
 
 
 def numpy_hist(held, box):
@@ -124,12 +77,12 @@ def numpy_hist(held, box):
     whose headers meet the box"""
     out = np.zeros(256, dtype=np.int64)
     for h in held:
-        if not meets(h, box) or not len(h[0]):
+        if not meets(h, box) or not len(h.xyz):
             continue
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
-        x = h[0].astype(np.int64)
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+        x = h.xyz.astype(np.int64)
         sel = np.all((x >= np.asarray(lmin, dtype=np.int64)) & (x <= np.asarray(lmax, dtype=np.int64)), axis=1)
-        out += np.bincount(h[1][sel], minlength=256)
+        out += np.bincount(h.cls[sel], minlength=256)
     return out
 
 
@@ -146,7 +99,7 @@ def test_every_bin_is_the_combined_count_of_its_class(q, files, dataset, name):
     box = BOXES[name]
     rc, hist, scanned = q.by_class(dataset, box)
     assert rc == 0, q.err()
-    want_scanned = sum(len(h[0]) for h in held if meets(h, box))
+    want_scanned = sum(len(h.xyz) for h in held if meets(h, box))
     for c in range(256):
         rc, m, s = q.one_class(dataset, box, c)
         assert rc == 0, q.err()
@@ -157,7 +110,7 @@ def test_every_bin_is_the_combined_count_of_its_class(q, files, dataset, name):
     assert hist == numpy_hist(held, box).tolist()
     assert all(hist[c] == 0 for c in range(256) if c not in CLASSES)
     # the boxes are what they are meant to be
-    n = [len(h[0]) for h in held]
+    n = [len(h.xyz) for h in held]
     if name == "every":
         assert sum(hist) == sum(n) == scanned and all(hist[c] > 0 for c in CLASSES)
     elif name == "single":
@@ -168,8 +121,8 @@ def test_every_bin_is_the_combined_count_of_its_class(q, files, dataset, name):
         assert 0 < sum(hist) < scanned
     else:  # the lying file: its points match in integer space, its header says no, and the header decides
         h = held[LYING]
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
-        x = h[0].astype(np.int64)
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+        x = h.xyz.astype(np.int64)
         assert np.all((x >= np.asarray(lmin)) & (x <= np.asarray(lmax)), axis=1).sum() > 0
         assert not any(meets(f, box) for f in held) and scanned == 0 and sum(hist) == 0
 

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
 import _polygon_rule as rule  # noqa: E402
 import _time_images as ti  # noqa: E402
 
@@ -34,7 +35,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-TIME = 2  # PCQ_RESIDENT_TIME
+TIME = pkg.PCQ_RESIDENT_TIME
 CYCLE = (1, 3, 63, 64, 65, 200, 511)
 SCALES = ((0.01, 0.01, 0.01), (0.02, 0.02, 0.01))
 Z_OFFSET = 7.5
@@ -51,29 +52,9 @@ TIMES = {}
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd, dbl = P(C.c_double), C.c_double
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
-        lib.pcq_query_collector_free.argtypes = [vp]
-        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_class.argtypes = [vp, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_search_time.argtypes = [vp, dbl, dbl, vp]
-        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_time.argtypes = [vp, dd, dd, dbl, dbl, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_many.argtypes = [vp, C.c_size_t, dd, dd, P(u64), P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_class.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_time.argtypes = [vp, dd, dd, dd, C.c_size_t, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, P(u64), P(u64)]
-        lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, dbl, dbl, u64, u64, dd, dd, P(u64)]
-        lib.pcq_query_resident_count_polygon.argtypes = [vp, C.c_size_t, dd, dbl, dbl, P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
+    err = staticmethod(_host.err)
 
     def counted(self, fn, *args):
         """An entry that ends with (matches, points_scanned)"""
@@ -83,8 +64,7 @@ class Q:
         return m.value, s.value
 
 
-def d3(v):
-    return (C.c_double * 3)(*v)
+d3 = _host.d3
 
 
 @pytest.fixture(scope="module")

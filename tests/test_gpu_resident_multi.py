@@ -3,7 +3,7 @@ every box, what pcq_query_resident_count_bounds gives for it alone — matches a
 the number of boxes (one group of up to eight per launch), and points_read must be the points of the files met by any box of a
 group, summed over the groups.
 
-Five small LAST files written here: formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and 2*4096+5 points; differing scales and
+The five small LAST files of tests/_resident_files.py (FIVE_FILES): formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and 2*4096+5 points; differing scales and
 offsets, one of them anisotropic (the box conversion of last.rs:100-102 then moves a min corner); and one file whose header
 bounds are tighter than its points, so that the header early-out (last.rs:92-94) is observable: a box that meets those points
 but not the header counts nothing.
@@ -11,31 +11,25 @@ but not the header counts nothing.
 import ctypes as C
 import importlib
 import os
-import struct
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 import _time_images as ti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_PANIC = -7
-COLOUR, TIME = 1, 2
-ISO = (0.01, 0.01, 0.01)
-# (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
-FILES = [(1, 3 * 4096 + 17, ti.SCALE, ti.OFFSET),             # world x [50, 150), y [-300, -100), z [-42.5, 57.5): anisotropic
-         (3, 4096, ISO, (0.0, 0.0, 0.0)),                      # x, y [-50, 50), z [-10, 10)
-         (6, 100, (0.001, 0.001, 0.001), (100.0, -200.0, 0.0)),  # x [95, 105), y [-205, -195), z [-1, 1)
-         (1, 0, ISO, (0.0, 0.0, 0.0)),
-         (3, 2 * 4096 + 5, ISO, (300.0, 0.0, 0.0))]            # x [250, 350): its header says x <= 300
-LYING, LYING_XMAX = 4, 300.0
+PCQ_ERR_PANIC = pkg.PCQ_ERR_PANIC
+COLOUR, TIME = pkg.PCQ_RESIDENT_COLOUR, pkg.PCQ_RESIDENT_TIME
+FILES = rf.FIVE_FILES
+meets = rf.meets
+LYING = rf.LYING
 A, B, CC, E = 0, 1, 2, 4
 BIG = 1e6
 BOXES = [((-BIG, -BIG, -BIG), (BIG, BIG, BIG)),                          # 0 meets every header
@@ -54,30 +48,10 @@ assert len(BOXES) == 17
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd, dbl = P(C.c_double), C.c_double
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_time.argtypes = [vp, dd, dd, dbl, dbl, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_many.argtypes = [vp, C.c_size_t, dd, dd, P(u64), P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths, blocks=None):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        if blocks is None:
-            rc = self.lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h))
-        else:
-            rc = self.lib.pcq_query_resident_load_with(0, arr, len(paths), blocks, C.byref(h))
-        assert rc == 0, self.err()
-        return h
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
 
     def one(self, r, box):
         m, s = C.c_uint64(7), C.c_uint64(7)
@@ -99,41 +73,25 @@ def q():
     return Q()
 
 
+def corpus(d):
+    return rf.write_files(d, FILES, 900, LYING)
+
+
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    """The five files, and per file (xyz, scale, offset, header min, header max)."""
-    d = tmp_path_factory.mktemp("resident_multi")
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(FILES):
-        xyz, cls, rgb, t = ti.points(n, 900 + k)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset).copy()
-        w = ti.world(xyz, scale, offset) if n else np.zeros((1, 3))
-        hmin, hmax = w.min(axis=0), w.max(axis=0)
-        if k == LYING:
-            assert hmax[0] > LYING_XMAX + 40.0
-            hmax[0] = LYING_XMAX
-            img[179:195] = np.frombuffer(struct.pack("<2d", hmax[0], hmin[0]), dtype=np.uint8)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, scale, offset, hmin, hmax))
-    return paths, held
-
-
-def meets(h, box):
-    """The header early-out: the file's header AABB meets the box (inclusive)."""
-    return bool(np.all(h[3] <= np.asarray(box[1])) and np.all(h[4] >= np.asarray(box[0])))
+    """The files, and per file what tests/_resident_files.py holds of it."""
+    return corpus(tmp_path_factory.mktemp("resident_multi"))
 
 
 def integer_matches(h, box):
     """numpy's count of the stored integer coordinates inside the local box of pcq_box_to_local, header or no header"""
-    lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[1]), list(h[2]))
-    x = h[0].astype(np.int64)
+    lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+    x = h.xyz.astype(np.int64)
     return int(np.all((x >= np.asarray(lmin, dtype=np.int64)) & (x <= np.asarray(lmax, dtype=np.int64)), axis=1).sum())
 
 
 def expected_read(held, boxes):
-    return sum(sum(len(h[0]) for h in held if any(meets(h, b) for b in boxes[g:g + 8])) for g in range(0, len(boxes), 8))
+    return sum(sum(len(h.xyz) for h in held if any(meets(h, b) for b in boxes[g:g + 8])) for g in range(0, len(boxes), 8))
 
 
 @pytest.fixture(scope="module")
@@ -152,14 +110,14 @@ def single(q, files, dataset):
         rc, m, s = q.one(dataset, box)
         assert rc == 0, q.err()
         assert m == sum(integer_matches(h, box) for h in held if meets(h, box)), box
-        assert s == sum(len(h[0]) for h in held if meets(h, box)), box
+        assert s == sum(len(h.xyz) for h in held if meets(h, box)), box
         out.append((m, s))
     return out
 
 
 def test_the_boxes_are_what_they_are_meant_to_be(files, single):
     _, held = files
-    n = [len(h[0]) for h in held]
+    n = [len(h.xyz) for h in held]
     assert single[EVERY] == (sum(n), sum(n)) and single[4] == single[EVERY] and single[5] == single[SLAB]
     assert single[SINGLE][1] == n[B] and single[SINGLE][0] > 0
     assert single[MISSED] == (0, 0)
@@ -184,8 +142,8 @@ def test_many_equals_the_single_box_entry(q, files, dataset, single, nboxes):
     assert s == [x[1] for x in single[:nboxes]]
     assert read == expected_read(held, BOXES[:nboxes])
     if nboxes == 17:  # (the third group is the last box alone: it meets one file, and only that file is read for it)
-        assert [k for k, h in enumerate(held) if len(h[0]) and meets(h, BOXES[16])] == [A]
-        assert read == expected_read(held, BOXES[:16]) + len(held[A][0])
+        assert [k for k, h in enumerate(held) if len(h.xyz) and meets(h, BOXES[16])] == [A]
+        assert read == expected_read(held, BOXES[:16]) + len(held[A].xyz)
 
 
 def test_reordering_the_boxes_permutes_the_answers(q, files, dataset, single):

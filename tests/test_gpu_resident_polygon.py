@@ -3,14 +3,13 @@ pcq_query_resident_count_polygon must give the rule of include/pcq.h (tests/_pol
 integers: the vertices numpy.rint((x - offset) / scale) in the file's lattice, the z range of pcq_box_to_local of the outline's world
 box, the header early-out applied — with the points_scanned of pcq_query_resident_count_bounds for that world box.
 
-The five small LAST files of tests/test_gpu_resident_raster.py, written here: formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and
+The five small LAST files of tests/_resident_files.py (FIVE_FILES): formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and
 2*4096+5 points; differing scales and offsets, one of them anisotropic; and one file whose header bounds are tighter than its
 points, so that the header early-out (last.rs:92-94) is observable.
 """
 import ctypes as C
 import importlib
 import os
-import struct
 import sys
 
 import numpy as np
@@ -18,23 +17,17 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
 import _polygon_rule as rule  # noqa: E402
-import _time_images as ti  # noqa: E402
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = -7, -11
-ISO = (0.01, 0.01, 0.01)
-# (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
-FILES = [(1, 3 * 4096 + 17, ti.SCALE, ti.OFFSET),             # world x [50, 150), y [-300, -100), z [-42.5, 57.5): anisotropic
-         (3, 4096, ISO, (0.0, 0.0, 0.0)),                      # x, y [-50, 50), z [-10, 10)
-         (6, 100, (0.001, 0.001, 0.001), (100.0, -200.0, 0.0)),  # x [95, 105), y [-205, -195), z [-1, 1)
-         (1, 0, ISO, (0.0, 0.0, 0.0)),
-         (3, 2 * 4096 + 5, ISO, (300.0, 0.0, 0.0))]            # x [250, 350): its header says x <= 300
-LYING, LYING_XMAX, FINE = 4, 300.0, 2
+PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = pkg.PCQ_ERR_PANIC, pkg.PCQ_ERR_UNSUPPORTED
+FILES = rf.FIVE_FILES
+meets = rf.meets
+LYING, FINE = rf.LYING, 2
 # (vertices, zmin, zmax)
 OUTLINES = {"every": ([(-40.0, -310.0), (160.0, -280.0), (340.0, -40.0), (330.0, 45.0), (0.0, 30.0), (-45.0, -100.0)], -1e6, 1e6),  # meets every header
             "single": ([(-20.0, -20.0), (25.005, -10.0), (10.0, 30.015), (-15.0, 12.5)], -5.0, 5.0),                              # a single file
@@ -50,28 +43,11 @@ def world_box(outline):
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_polygon.argtypes = [vp, C.c_size_t, dd, C.c_double, C.c_double, P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        assert self.lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h)) == 0, self.err()
-        return h
-
-    def bounds(self, r, box):
-        m, s = C.c_uint64(7), C.c_uint64(7)
-        rc = self.lib.pcq_query_resident_count_bounds(r, (C.c_double * 3)(*box[0]), (C.c_double * 3)(*box[1]), C.byref(m), C.byref(s))
-        return rc, m.value, s.value
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
+    bounds = staticmethod(_host.bounds)
 
     def polygon(self, r, outline, sentinel=77, scanned=True):
         xy, zmin, zmax = outline
@@ -87,36 +63,20 @@ def q():
     return Q()
 
 
+def corpus(d):
+    return rf.write_files(d, FILES, 950, LYING)
+
+
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    """The five files, and per file (xyz, cls, scale, offset, header min, header max)."""
-    d = tmp_path_factory.mktemp("resident_polygon")
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(FILES):
-        xyz, cls, rgb, t = ti.points(n, 950 + k)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset).copy()
-        w = ti.world(xyz, scale, offset) if n else np.zeros((1, 3))
-        hmin, hmax = w.min(axis=0), w.max(axis=0)
-        if k == LYING:
-            assert hmax[0] > LYING_XMAX + 40.0
-            hmax[0] = LYING_XMAX
-            img[179:195] = np.frombuffer(struct.pack("<2d", hmax[0], hmin[0]), dtype=np.uint8)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, cls, scale, offset, hmin, hmax))
-    return paths, held
-
-
-def meets(h, box):
-    """The header early-out: the file's header AABB meets the box (inclusive)."""
-    return bool(np.all(h[4] <= np.asarray(box[1])) and np.all(h[5] >= np.asarray(box[0])))
+    """The files, and per file what tests/_resident_files.py holds of it."""
+    return corpus(tmp_path_factory.mktemp("resident_polygon"))
 
 
 def lattice(xy, h):
     """numpy.rint((w - offset) / scale): two f64 operations in this order, ties to even"""
     v = np.asarray(xy, dtype=np.float64)
-    return np.stack([np.rint((v[:, a] - np.float64(h[3][a])) / np.float64(h[2][a])) for a in range(2)], axis=1).astype(np.int64)
+    return np.stack([np.rint((v[:, a] - np.float64(h.offset[a])) / np.float64(h.scale[a])) for a in range(2)], axis=1).astype(np.int64)
 
 
 def rule_count(held, outline, header=True):
@@ -124,12 +84,12 @@ def rule_count(held, outline, header=True):
     box = world_box(outline)
     total = 0
     for h in held:
-        if (header and not meets(h, box)) or not len(h[0]):
+        if (header and not meets(h, box)) or not len(h.xyz):
             continue
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
         v = lattice(outline[0], h)
         lo, hi = [int(v[:, 0].min()), int(v[:, 1].min()), lmin[2]], [int(v[:, 0].max()), int(v[:, 1].max()), lmax[2]]
-        total += int(rule.counted(h[0], lo, hi, v.tolist()).sum())
+        total += int(rule.counted(h.xyz, lo, hi, v.tolist()).sum())
     return total
 
 
@@ -150,11 +110,11 @@ def test_matches_are_the_rule_on_the_files_integers(q, files, dataset, name):
     want = rule_count(held, outline)
     assert got == want
     rc, m, s = q.bounds(dataset, box)
-    assert rc == 0 and s == scanned == sum(len(h[0]) for h in held if meets(h, box))
-    n = [len(h[0]) for h in held]
+    assert rc == 0 and s == scanned == sum(len(h.xyz) for h in held if meets(h, box))
+    n = [len(h.xyz) for h in held]
     if name == "every":
         assert scanned == sum(n) and 0 < got < sum(n)
-        assert all(rule_count([h], outline) > 0 for h in held if len(h[0]))  # every file with points contributes
+        assert all(rule_count([h], outline) > 0 for h in held if len(h.xyz))  # every file with points contributes
     elif name == "single":
         assert scanned == n[1] and 100 < got < n[1]
     elif name == "missed":

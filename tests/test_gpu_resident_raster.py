@@ -3,37 +3,30 @@ pcq_query_resident_count_bounds_raster must give, for every cell of the raster, 
 files inside that cell's integer sub-box — lmin from pcq_box_to_local, the cell a whole number of each file's lattice steps — with
 the points_scanned of pcq_query_resident_count_bounds for the same world box.
 
-The five small LAST files of tests/test_gpu_resident_class_hist.py, written here: formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and
+The five small LAST files of tests/_resident_files.py (FIVE_FILES): formats 1, 3 and 6; 3*4096+17, 4096, 100, 0 and
 2*4096+5 points; differing scales and offsets, one of them anisotropic; and one file whose header bounds are tighter than its
 points, so that the header early-out (last.rs:92-94) is observable.  The rasters lie over that test's boxes, cut to whole cells.
 """
 import ctypes as C
 import importlib
 import os
-import struct
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
-import _time_images as ti  # noqa: E402
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = -7, -11
-ISO = (0.01, 0.01, 0.01)
-# (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
-FILES = [(1, 3 * 4096 + 17, ti.SCALE, ti.OFFSET),             # world x [50, 150), y [-300, -100), z [-42.5, 57.5): anisotropic
-         (3, 4096, ISO, (0.0, 0.0, 0.0)),                      # x, y [-50, 50), z [-10, 10)
-         (6, 100, (0.001, 0.001, 0.001), (100.0, -200.0, 0.0)),  # x [95, 105), y [-205, -195), z [-1, 1)
-         (1, 0, ISO, (0.0, 0.0, 0.0)),
-         (3, 2 * 4096 + 5, ISO, (300.0, 0.0, 0.0))]            # x [250, 350): its header says x <= 300
-LYING, LYING_XMAX = 4, 300.0
+PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = pkg.PCQ_ERR_PANIC, pkg.PCQ_ERR_UNSUPPORTED
+FILES = rf.FIVE_FILES
+meets, world_box = rf.meets, rf.world_box
+LYING = rf.LYING
 BIG = 1e6
 # (bmin, zmax, cell_size, nx, ny): every cell size is a whole number of lattice steps of every file
 RASTERS = {"every": ((-BIG, -BIG, -BIG), BIG, 62500.0, 32, 32),        # meets every header
@@ -43,35 +36,13 @@ RASTERS = {"every": ((-BIG, -BIG, -BIG), BIG, 62500.0, 32, 32),        # meets e
            "lie": ((320.0, -50.0, -10.0), 10.0, 0.25, 80, 400)}         # the lying file's points outside its header
 
 
-def world_box(ras):
-    bmin, zmax, cell, nx, ny = ras
-    return tuple(bmin), (bmin[0] + nx * cell, bmin[1] + ny * cell, zmax)
-
-
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_raster.argtypes = [vp, dd, C.c_double, C.c_double, u64, u64, P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        assert self.lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h)) == 0, self.err()
-        return h
-
-    def bounds(self, r, box):
-        m, s = C.c_uint64(7), C.c_uint64(7)
-        rc = self.lib.pcq_query_resident_count_bounds(r, (C.c_double * 3)(*box[0]), (C.c_double * 3)(*box[1]), C.byref(m), C.byref(s))
-        return rc, m.value, s.value
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
+    bounds = staticmethod(_host.bounds)
 
     def raster(self, r, ras, sentinel=77, scanned=True):
         bmin, zmax, cell, nx, ny = ras
@@ -87,30 +58,14 @@ def q():
     return Q()
 
 
+def corpus(d):
+    return rf.write_files(d, FILES, 950, LYING)
+
+
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    """The five files, and per file (xyz, cls, scale, offset, header min, header max)."""
-    d = tmp_path_factory.mktemp("resident_raster")
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(FILES):
-        xyz, cls, rgb, t = ti.points(n, 950 + k)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset).copy()
-        w = ti.world(xyz, scale, offset) if n else np.zeros((1, 3))
-        hmin, hmax = w.min(axis=0), w.max(axis=0)
-        if k == LYING:
-            assert hmax[0] > LYING_XMAX + 40.0
-            hmax[0] = LYING_XMAX
-            img[179:195] = np.frombuffer(struct.pack("<2d", hmax[0], hmin[0]), dtype=np.uint8)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, cls, scale, offset, hmin, hmax))
-    return paths, held
-
-
-def meets(h, box):
-    """The header early-out: the file's header AABB meets the box (inclusive)."""
-    return bool(np.all(h[4] <= np.asarray(box[1])) and np.all(h[5] >= np.asarray(box[0])))
+    """The files, and per file what tests/_resident_files.py holds of it."""
+    return corpus(tmp_path_factory.mktemp("resident_raster"))
 
 
 def numpy_raster(held, ras, header=True):
@@ -120,12 +75,12 @@ def numpy_raster(held, ras, header=True):
     box = world_box(ras)
     out = np.zeros((ny, nx), dtype=np.int64)
     for h in held:
-        if (header and not meets(h, box)) or not len(h[0]):
+        if (header and not meets(h, box)) or not len(h.xyz):
             continue
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
-        k = [round(cell / h[2][a]) for a in range(2)]
-        assert all(abs(cell / h[2][a] - k[a]) <= 1e-9 * k[a] for a in range(2))
-        x = h[0].astype(np.int64)
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+        k = [round(cell / h.scale[a]) for a in range(2)]
+        assert all(abs(cell / h.scale[a] - k[a]) <= 1e-9 * k[a] for a in range(2))
+        x = h.xyz.astype(np.int64)
         cx, cy = (x[:, 0] - lmin[0]) // k[0], (x[:, 1] - lmin[1]) // k[1]
         sel = (x[:, 0] >= lmin[0]) & (cx < nx) & (x[:, 1] >= lmin[1]) & (cy < ny) & (x[:, 2] >= lmin[2]) & (x[:, 2] <= lmax[2])
         np.add.at(out, (cy[sel], cx[sel]), 1)
@@ -150,8 +105,8 @@ def test_every_cell_is_numpy_on_the_files_integers(q, files, dataset, name):
     bad = np.argwhere(got != want)
     assert len(bad) == 0, [(int(y), int(x), int(got[y, x]), int(want[y, x])) for y, x in bad[:12]]
     rc, m, s = q.bounds(dataset, box)
-    assert rc == 0 and s == scanned == sum(len(h[0]) for h in held if meets(h, box))
-    n = [len(h[0]) for h in held]
+    assert rc == 0 and s == scanned == sum(len(h.xyz) for h in held if meets(h, box))
+    n = [len(h.xyz) for h in held]
     if name == "every":
         assert scanned == sum(n) and got.sum() == sum(n) and (got > 0).sum() > 1
     elif name == "single":
@@ -172,7 +127,7 @@ def test_a_raster_above_the_launch_limit_is_its_blocks(q, files, dataset):
     rc, whole, scanned = q.raster(dataset, (bmin, zmax, cell, 96, 96))
     assert rc == 0, q.err()
     assert np.array_equal(whole, numpy_raster(held, (bmin, zmax, cell, 96, 96)))
-    assert scanned == len(held[1][0]) and whole.sum() > 300
+    assert scanned == len(held[1].xyz) and whole.sum() > 300
     for j in range(3):
         for i in range(3):
             sub = ((bmin[0] + 32 * i * cell, bmin[1] + 32 * j * cell, bmin[2]), zmax, cell, 32, 32)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
 import _time_images as ti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -21,95 +22,38 @@ PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 POINT_DTYPE = pkg.POINT_DTYPE
-PCQ_ERR_ARG, PCQ_ERR_FORMAT = -8, -3
-COLOUR, TIME = 1, 2
+PCQ_ERR_ARG, PCQ_ERR_FORMAT = pkg.PCQ_ERR_ARG, pkg.PCQ_ERR_FORMAT
+COLOUR, TIME = pkg.PCQ_RESIDENT_COLOUR, pkg.PCQ_RESIDENT_TIME
 FILES = [(1, 3 * 4096 + 17), (3, 4096), (6, 100), (7, 0)]  # (format, points)
 GRID = ((40.0, -320.0, -60.0), (160.0, -80.0, 120.0), 2.0)
 RANGES = [(1200.0, 1300.0), (1000.0, 1500.0), (1999.0, 2001.0), (-np.inf, np.inf), (1500.0, 1500.0), (5.0, 6.0), (np.nan, 1.0)]
 
 
-class IndexStats(C.Structure):
-    _fields_ = [("chunks", C.c_uint64), ("skipped", C.c_uint64), ("whole", C.c_uint64), ("scanned", C.c_uint64), ("built", C.c_uint64)]
-
-
 class Q:
-    """ctypes view of the parts of include/pcq_query.h used here"""
+    """include/pcq_query.h through the package's view; the shared calls are tests/_host.py's"""
 
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_collector_new_count.argtypes = [C.c_int, P(vp)]
-        lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, P(vp)]
-        lib.pcq_query_collector_new_grid.argtypes = [C.c_int, dd, dd, C.c_double, P(vp)]
-        lib.pcq_query_collector_free.argtypes = [vp]
-        lib.pcq_query_collector_point_count.argtypes = [vp, P(u64)]
-        lib.pcq_query_collector_points.argtypes = [vp, vp, u64, P(u64)]
-        lib.pcq_query_collector_grid_cells.argtypes = [vp, vp, u64, P(u64)]
-        lib.pcq_query_search_file_time.argtypes = [C.c_char_p, C.c_double, C.c_double, C.c_int, vp]
-        lib.pcq_query_search_file_bounds.argtypes = [C.c_char_p, dd, dd, C.c_int, vp, P(C.c_int)]
-        lib.pcq_query_search_file_class.argtypes = [C.c_char_p, C.c_uint8, C.c_int, vp]
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_load_points.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_search_time.argtypes = [vp, C.c_double, C.c_double, vp]
-        lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
-        lib.pcq_query_resident_search_class.argtypes = [vp, C.c_uint8, vp]
-        lib.pcq_query_resident_count_bounds.argtypes = [vp, dd, dd, P(u64), P(u64)]
-        lib.pcq_query_resident_count_class.argtypes = [vp, C.c_uint8, P(u64), P(u64)]
-        lib.pcq_query_resident_last_stats.argtypes = [vp, P(IndexStats)]
+        self.lib = _host.lib()
+
+    d3 = staticmethod(_host.d3)
+    err = staticmethod(_host.err)
+    stats = staticmethod(_host.last_stats)
 
     @staticmethod
-    def d3(v):
-        return (C.c_double * 3)(*[float(x) for x in v])
+    def collector(kind, device=0):
+        return _host.collector(kind, GRID, device)
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def collector(self, kind, device=0):
-        h = C.c_void_p()
-        if kind == "count":
-            rc = self.lib.pcq_query_collector_new_count(device, C.byref(h))
-        elif kind == "buffer":
-            rc = self.lib.pcq_query_collector_new_buffer(device, C.byref(h))
-        else:
-            rc = self.lib.pcq_query_collector_new_grid(device, self.d3(GRID[0]), self.d3(GRID[1]), GRID[2], C.byref(h))
-        assert rc == 0, self.err()
-        return h
-
-    def result(self, h, kind):
+    @staticmethod
+    def result(h, kind):
         """count, or the records (buffer: file order), or (sorted cell keys, winners in key order); frees the collector"""
         try:
-            n = C.c_uint64()
-            assert self.lib.pcq_query_collector_point_count(h, C.byref(n)) == 0, self.err()
-            if kind == "count":
-                return n.value
-            assert self.lib.pcq_query_collector_points(h, None, 0, C.byref(n)) == 0
-            pts = np.zeros(n.value, dtype=POINT_DTYPE)
-            if n.value:
-                assert self.lib.pcq_query_collector_points(h, pts.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
-            if kind == "buffer":
-                return pts.tobytes()
-            assert self.lib.pcq_query_collector_grid_cells(h, None, 0, C.byref(n)) == 0
-            keys = np.zeros(n.value, dtype=np.uint64)
-            if n.value:
-                assert self.lib.pcq_query_collector_grid_cells(h, keys.ctypes.data_as(C.c_void_p), n.value, C.byref(n)) == 0
-            order = np.argsort(keys, kind="stable")
-            return keys[order].tobytes(), pts[order].tobytes()
+            return _host.result(h, kind)
         finally:
-            self.lib.pcq_query_collector_free(h)
+            _host.free_collector(h)
 
-    def load(self, paths, blocks, device=0):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p(99)
-        rc = self.lib.pcq_query_resident_load_with(device, arr, len(paths), blocks, C.byref(h))
-        return rc, h
-
-    def stats(self, r):
-        st = IndexStats()
-        assert self.lib.pcq_query_resident_last_stats(r, C.byref(st)) == 0, self.err()
-        return {k: getattr(st, k) for k, _ in IndexStats._fields_}
+    @staticmethod
+    def load(paths, blocks, device=0):
+        return _host.try_load(paths, blocks, device, preset=99)
 
 
 @pytest.fixture(scope="module")

@@ -2,7 +2,7 @@
 pcq_query_resident_count_bounds_by_time must give, for every bin b of the caller's edge table, what
 pcq_query_resident_count_bounds_time gives for [edges[b], edges[b + 1]) — zeros included — with the same points_scanned.
 
-Six small LAST files with time blocks, built as tests/test_gpu_resident_bounds_time.py builds its own (tests/_time_images.py):
+Six small LAST files with time blocks, written by tests/_resident_files.py (images of tests/_time_images.py):
 formats 1 and 6 (whose time blocks lie at n*20 and n*22 behind the point data's start) and 3; 3*4096+17, 4096, 100, 0, 513 and
 2*4096+5 points; differing scales and offsets; one file far from the others, whose header misses the boxes of the others.  Times
 are uniform in [1000, 2000), sorted per file.  A handful of bins are also checked against the oracle's box AND time search, and all
@@ -17,16 +17,16 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 import _time_images as ti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_ARG, PCQ_ERR_PANIC = -8, -7
-COLOUR, TIME = 1, 2
+PCQ_ERR_ARG, PCQ_ERR_PANIC = pkg.PCQ_ERR_ARG, pkg.PCQ_ERR_PANIC
+COLOUR, TIME = pkg.PCQ_RESIDENT_COLOUR, pkg.PCQ_RESIDENT_TIME
 BINS_MAX = 1024  # include/pcq.h: PCQ_TIME_BINS_MAX
 ISO = (0.01, 0.01, 0.01)
 # (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
@@ -52,24 +52,10 @@ TABLES = {"ten": np.linspace(1000.0, 2000.0, 11),
 
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd, dbl = P(C.c_double), C.c_double
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load_with.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, C.c_uint, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds_time.argtypes = [vp, dd, dd, dbl, dbl, P(u64), P(u64)]
-        lib.pcq_query_resident_count_bounds_by_time.argtypes = [vp, dd, dd, dd, C.c_size_t, P(u64), P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths, blocks):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        rc = self.lib.pcq_query_resident_load_with(0, arr, len(paths), blocks, C.byref(h))
-        assert rc == 0, self.err()
-        return h
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
 
     def one_range(self, r, box, start, end):
         m, s = C.c_uint64(7), C.c_uint64(7)
@@ -90,31 +76,27 @@ def q():
     return Q()
 
 
+def corpus(d):
+    return rf.write_files(d, FILES, 970)
+
+
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    """The files, and per file (xyz, t, scale, offset, image)."""
-    d = tmp_path_factory.mktemp("resident_time_hist")
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(FILES):
-        xyz, cls, rgb, t = ti.points(n, 970 + k)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset)
-        hdr = 375 if fmt >= 6 else 227
+    """The files, and per file what tests/_resident_files.py holds of it."""
+    paths, held = corpus(tmp_path_factory.mktemp("resident_time_hist"))
+    for (fmt, n, _, _), h in zip(FILES, held):
         assert ti.time_offset(fmt) == (22 if fmt >= 6 else 20)
         if n:  # the time block is where the loader looks for it
-            at = hdr + n * ti.time_offset(fmt)
-            assert np.array_equal(np.frombuffer(img[at:at + 8 * n].tobytes(), dtype=np.float64), t)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, t, scale, offset, img))
+            at = (375 if fmt >= 6 else 227) + n * ti.time_offset(fmt)
+            assert np.array_equal(np.frombuffer(h.image[at:at + 8 * n].tobytes(), dtype=np.float64), h.t)
     return paths, held
 
 
 def meets(h, box):
     """The header early-out: the file's world AABB meets the box (inclusive)."""
-    if not len(h[0]):
+    if not len(h.xyz):
         return False
-    w = ti.world(h[0], h[2], h[3])
+    w = ti.world(h.xyz, h.scale, h.offset)
     return bool(np.all(w.min(axis=0) <= np.asarray(box[1])) and np.all(w.max(axis=0) >= np.asarray(box[0])))
 
 
@@ -125,10 +107,10 @@ def numpy_hist(held, box, edges):
     for h in held:
         if not meets(h, box):
             continue
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
-        x = h[0].astype(np.int64)
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+        x = h.xyz.astype(np.int64)
         sel = np.all((x >= np.asarray(lmin, dtype=np.int64)) & (x <= np.asarray(lmax, dtype=np.int64)), axis=1)
-        out += np.asarray([int((sel & ti.select(h[1], edges[b], edges[b + 1])).sum()) for b in range(len(edges) - 1)])
+        out += np.asarray([int((sel & ti.select(h.t, edges[b], edges[b + 1])).sum()) for b in range(len(edges) - 1)])
     return out
 
 
@@ -146,14 +128,14 @@ def test_every_bin_is_the_box_and_time_count_of_its_range(q, files, dataset, nam
     box, edges = BOXES[name], TABLES[table]
     rc, hist, scanned = q.by_time(dataset, box, edges)
     assert rc == 0, q.err()
-    want_scanned = sum(len(h[0]) for h in held if meets(h, box))
+    want_scanned = sum(len(h.xyz) for h in held if meets(h, box))
     for b in range(len(edges) - 1):
         rc, m, s = q.one_range(dataset, box, float(edges[b]), float(edges[b + 1]))
         assert rc == 0, q.err()
         assert hist[b] == m, (name, table, b, hist[b], m)
         assert s == scanned == want_scanned
     assert hist == numpy_hist(held, box, edges).tolist()
-    n = [len(h[0]) for h in held]
+    n = [len(h.xyz) for h in held]
     if name == "every":
         assert scanned == sum(n)
         if table in ("ten", "uneven"):
@@ -180,9 +162,9 @@ def test_a_handful_of_bins_against_the_oracle(q, files, dataset, oracle):
     for b in (0, 3, 4, 9):
         c = oracle.count_collector()
         for h in held:
-            if not len(h[0]):
+            if not len(h.xyz):
                 continue
-            assert oracle.search_bounds_time(h[4], "last", box[0], box[1], float(edges[b]), float(edges[b + 1]), c) == 0, oracle.err()
+            assert oracle.search_bounds_time(h.image, "last", box[0], box[1], float(edges[b]), float(edges[b + 1]), c) == 0, oracle.err()
         assert c.point_count() == hist[b], b
         c.free()
     assert sum(hist[b] for b in (0, 3, 4, 9)) > 0

@@ -3,37 +3,31 @@ pcq_query_resident_bounds_zrange_raster must give, for every cell of the raster,
 scale[2]) + offset[2], tests/_time_images.world — of the stored integer points of the surviving files inside that cell's integer
 sub-box, NaN where there is none, with the points_scanned of pcq_query_resident_count_bounds_raster.
 
-The five small LAST files and the five rasters of tests/test_gpu_resident_raster.py, written here: the files with points have three z lattices
+The five small LAST files of tests/_resident_files.py (FIVE_FILES) and the five rasters of tests/test_gpu_resident_raster.py: the files with points have three z lattices
 (the two isotropic files of offset 0 share one), so a raster that meets every header runs three launch groups, merged on the host; the "single", "missed", "slab" and "lie"
 rasters exceed PCQ_ZRANGE_CELLS_MAX and are cut into blocks.  A second dataset of two files of ONE z lattice goes through one launch.
 """
 import ctypes as C
 import importlib
 import os
-import struct
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
+import _host  # noqa: E402
+import _resident_files as rf  # noqa: E402
 import _time_images as ti  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(os.path.dirname(HERE), "adhoc-queries-pointclouds_amd")
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
-PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = -7, -11
-ISO = (0.01, 0.01, 0.01)
-# (format, points, scale, offset); ints are x, y in [-5000, 5000), z in [-1000, 1000)
-FILES = [(1, 3 * 4096 + 17, ti.SCALE, ti.OFFSET),             # world x [50, 150), y [-300, -100), z [-42.5, 57.5): anisotropic
-         (3, 4096, ISO, (0.0, 0.0, 0.0)),                      # x, y [-50, 50), z [-10, 10)
-         (6, 100, (0.001, 0.001, 0.001), (100.0, -200.0, 0.0)),  # x [95, 105), y [-205, -195), z [-1, 1)
-         (1, 0, ISO, (0.0, 0.0, 0.0)),
-         (3, 2 * 4096 + 5, ISO, (300.0, 0.0, 0.0))]            # x [250, 350): its header says x <= 300
-LYING, LYING_XMAX = 4, 300.0
+PCQ_ERR_PANIC, PCQ_ERR_UNSUPPORTED = pkg.PCQ_ERR_PANIC, pkg.PCQ_ERR_UNSUPPORTED
+ISO, FILES = rf.ISO, rf.FIVE_FILES
+meets, world_box = rf.meets, rf.world_box
+LYING = rf.LYING
 BIG = 1e6
 # (bmin, zmax, cell_size, nx, ny): every cell size is a whole number of lattice steps of every file
 RASTERS = {"every": ((-BIG, -BIG, -BIG), BIG, 62500.0, 32, 32),        # meets every header
@@ -44,30 +38,12 @@ RASTERS = {"every": ((-BIG, -BIG, -BIG), BIG, 62500.0, 32, 32),        # meets e
 assert len({(f[2][2], f[3][2]) for f in FILES if f[1]}) == 3  # three z lattices among the four files with points
 
 
-def world_box(ras):
-    bmin, zmax, cell, nx, ny = ras
-    return tuple(bmin), (bmin[0] + nx * cell, bmin[1] + ny * cell, zmax)
-
-
 class Q:
     def __init__(self):
-        lib = self.lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-        vp, P, u64 = C.c_void_p, C.POINTER, C.c_uint64
-        dd = P(C.c_double)
-        lib.pcq_query_last_error.restype = C.c_char_p
-        lib.pcq_query_resident_load.argtypes = [C.c_int, P(C.c_char_p), C.c_size_t, P(vp)]
-        lib.pcq_query_resident_free.argtypes = [vp]
-        lib.pcq_query_resident_count_bounds_raster.argtypes = [vp, dd, C.c_double, C.c_double, u64, u64, P(u64), P(u64)]
-        lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, C.c_double, C.c_double, u64, u64, dd, dd, P(u64)]
+        self.lib = _host.lib()
 
-    def err(self):
-        return self.lib.pcq_query_last_error()
-
-    def load(self, paths):
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        h = C.c_void_p()
-        assert self.lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h)) == 0, self.err()
-        return h
+    err = staticmethod(_host.err)
+    load = staticmethod(_host.load)
 
     def raster(self, r, ras):
         bmin, zmax, cell, nx, ny = ras
@@ -101,33 +77,13 @@ def q():
     return Q()
 
 
-def write_files(d, specs, seed, lying=None):
-    """The files, and per file (xyz, cls, scale, offset, header min, header max)."""
-    paths, held = [], []
-    for k, (fmt, n, scale, offset) in enumerate(specs):
-        xyz, cls, rgb, t = ti.points(n, seed + k)
-        img = ti.last_image(fmt, xyz, cls, rgb, t, scale=scale, offset=offset).copy()
-        w = ti.world(xyz, scale, offset) if n else np.zeros((1, 3))
-        hmin, hmax = w.min(axis=0), w.max(axis=0)
-        if k == lying:
-            assert hmax[0] > LYING_XMAX + 40.0
-            hmax[0] = LYING_XMAX
-            img[179:195] = np.frombuffer(struct.pack("<2d", hmax[0], hmin[0]), dtype=np.uint8)
-        p = str(d / f"f{k}_{fmt}_{n}.last")
-        img.tofile(p)
-        paths.append(p)
-        held.append((xyz, cls, scale, offset, hmin, hmax))
-    return paths, held
+def corpus(d):
+    return rf.write_files(d, FILES, 950, LYING)
 
 
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
-    return write_files(tmp_path_factory.mktemp("resident_zrange"), FILES, 950, LYING)
-
-
-def meets(h, box):
-    """The header early-out: the file's header AABB meets the box (inclusive)."""
-    return bool(np.all(h[4] <= np.asarray(box[1])) and np.all(h[5] >= np.asarray(box[0])))
+    return corpus(tmp_path_factory.mktemp("resident_zrange"))
 
 
 def numpy_zrange(held, ras, header=True):
@@ -139,15 +95,15 @@ def numpy_zrange(held, ras, header=True):
     lo, hi = np.full((ny, nx), np.nan), np.full((ny, nx), np.nan)
     cnt = np.zeros((ny, nx), dtype=np.int64)
     for h in held:
-        if (header and not meets(h, box)) or not len(h[0]):
+        if (header and not meets(h, box)) or not len(h.xyz):
             continue
-        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h[2]), list(h[3]))
-        k = [round(cell / h[2][a]) for a in range(2)]
-        assert all(abs(cell / h[2][a] - k[a]) <= 1e-9 * k[a] for a in range(2))
-        x = h[0].astype(np.int64)
+        lmin, lmax = pkg.box_to_local(list(box[0]), list(box[1]), list(h.scale), list(h.offset))
+        k = [round(cell / h.scale[a]) for a in range(2)]
+        assert all(abs(cell / h.scale[a] - k[a]) <= 1e-9 * k[a] for a in range(2))
+        x = h.xyz.astype(np.int64)
         cx, cy = (x[:, 0] - lmin[0]) // k[0], (x[:, 1] - lmin[1]) // k[1]
         sel = (x[:, 0] >= lmin[0]) & (cx < nx) & (x[:, 1] >= lmin[1]) & (cy < ny) & (x[:, 2] >= lmin[2]) & (x[:, 2] <= lmax[2])
-        z = ti.world(h[0], h[2], h[3])[:, 2]
+        z = ti.world(h.xyz, h.scale, h.offset)[:, 2]
         np.fmin.at(lo, (cy[sel], cx[sel]), z[sel])
         np.fmax.at(hi, (cy[sel], cx[sel]), z[sel])
         np.add.at(cnt, (cy[sel], cx[sel]), 1)
@@ -167,7 +123,7 @@ def check(q, r, held, ras):
     assert len(bad) == 0, [(int(y), int(x), float(zlo[y, x]), float(lo[y, x]), float(zhi[y, x]), float(hi[y, x])) for y, x in bad[:8]]
     assert same_bytes(zlo, lo) and same_bytes(zhi, hi)
     rc, counts, s = q.raster(r, ras)
-    assert rc == 0 and s == scanned == sum(len(h[0]) for h in held if meets(h, world_box(ras)))
+    assert rc == 0 and s == scanned == sum(len(h.xyz) for h in held if meets(h, world_box(ras)))
     assert np.array_equal(counts, cnt)
     return zlo, zhi, cnt, scanned
 
@@ -185,10 +141,10 @@ def test_every_cell_is_numpy_on_the_files_integers(q, files, dataset, name):
     ras = RASTERS[name]
     box = world_box(ras)
     zlo, zhi, cnt, scanned = check(q, dataset, held, ras)
-    n = [len(h[0]) for h in held]
+    n = [len(h.xyz) for h in held]
     if name == "every":  # three groups merged: a cell holds points of several files
         assert scanned == sum(n) and cnt.sum() == sum(n) and (cnt > 0).sum() > 1
-        groups = [numpy_zrange([h], ras)[2] > 0 for h in held if len(h[0])]
+        groups = [numpy_zrange([h], ras)[2] > 0 for h in held if len(h.xyz)]
         assert (np.sum(groups, axis=0) > 1).any() and (zlo < zhi).any()
     elif name == "single":
         assert scanned == n[1] and 0 < cnt.sum() < n[1] and (cnt > 0).sum() > 200 and (cnt == 0).sum() > 200
@@ -207,7 +163,7 @@ def test_a_raster_above_the_launch_limit_is_its_blocks(q, files, dataset):
     _, held = files
     bmin, zmax, cell = (-24.0, -24.0, -5.0), 5.0, 0.5
     wlo, whi, cnt, scanned = check(q, dataset, held, (bmin, zmax, cell, 96, 96))
-    assert scanned == len(held[1][0]) and cnt.sum() > 300
+    assert scanned == len(held[1].xyz) and cnt.sum() > 300
     for j in range(3):
         for i in range(3):
             sub = ((bmin[0] + 32 * i * cell, bmin[1] + 32 * j * cell, bmin[2]), zmax, cell, 32, 32)
@@ -244,7 +200,7 @@ def test_a_file_without_a_z_scale_is_unsupported(q, tmp_path_factory):
     """scale[2] = 0: the conversion to world z is not monotone; the file is named, the outputs stay, and a raster whose world box
     its header misses is served"""
     d = tmp_path_factory.mktemp("resident_zrange_flat")
-    paths, held = write_files(d, [(3, 4096, ISO, (0.0, 0.0, 0.0)), (1, 600, (0.01, 0.01, 0.0), (200.0, 0.0, 1.0))], 970)
+    paths, held = rf.write_files(d, [(3, 4096, ISO, (0.0, 0.0, 0.0)), (1, 600, (0.01, 0.01, 0.0), (200.0, 0.0, 1.0))], 970)
     r = q.load(paths)
     try:
         rc, zlo, zhi, s = q.zrange(r, ((-BIG, -BIG, -BIG), BIG, 62500.0, 32, 32))
@@ -267,13 +223,13 @@ def test_two_files_of_one_z_lattice(q, tmp_path_factory):
     numpy's fold over all three, whatever the grouping"""
     d = tmp_path_factory.mktemp("resident_zrange_shared")
     specs = [(1, 4096 + 9, (0.01, 0.02, 0.05), (0.0, 0.0, 7.5)), (3, 700, ISO, (1.0, -1.0, 0.0)), (3, 2 * 4096, (0.02, 0.01, 0.05), (10.0, -10.0, 7.5))]
-    paths, held = write_files(d, specs, 980)
+    paths, held = rf.write_files(d, specs, 980)
     r = q.load(paths)
     shared = []
     try:
         for ras in (((-100.0, -100.0, -20.0), 30.0, 2.0, 100, 100), ((-60.0, -60.0, -BIG), BIG, 4.0, 30, 30)):
             zlo, zhi, cnt, scanned = check(q, r, held, ras)
-            assert scanned == sum(len(h[0]) for h in held) and cnt.sum() > 4096
+            assert scanned == sum(len(h.xyz) for h in held) and cnt.sum() > 4096
             shared.append(int(((numpy_zrange([held[0]], ras)[2] > 0) & (numpy_zrange([held[2]], ras)[2] > 0)).sum()))
         assert max(shared) > 50  # cells that hold points of both files of the group
     finally:

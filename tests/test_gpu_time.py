@@ -383,11 +383,7 @@ def test_cli_regular_implementation_fails_like_the_other_searches(tmp_path):
 
 def test_c_view_search_file_time(tmp_path):
     """pcq_query_search_file_time == the CLI's per-file search: counts through the C view's count collector."""
-    q = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
-    q.pcq_query_search_file_time.argtypes = [C.c_char_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
-    q.pcq_query_collector_new_count.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    q.pcq_query_collector_point_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    q.pcq_query_collector_free.argtypes = [C.c_void_p]
+    q = pkg.load_query_library()
     xyz, cls, rgb, t = ti.points(10_000, 3)
     p = tmp_path / "f.last"
     ti.last_image(6, xyz, cls, rgb, t).tofile(p)

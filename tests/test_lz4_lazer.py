@@ -3,6 +3,7 @@ host decoder) pinned against the real liblz4 the reference's `lz4` crate wraps, 
 frames, and the oracle's LAZER searches against numpy restatements of query/src/search/lazer.rs.
 """
 import ctypes as C
+import importlib
 import json
 import os
 
@@ -14,6 +15,7 @@ from _oracle import ERR_EOF, ERR_HEADER, ERR_PANIC, OK, POINT_DTYPE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 REAL = _lz4ref.load()
@@ -23,9 +25,7 @@ needs_liblz4 = pytest.mark.skipif(REAL is None, reason="liblz4.so.1 not on this 
 @pytest.fixture(scope="module")
 def product():
     """The product's host-side LZ4 Frame reader through the C view (no GPU call)."""
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    lib.pcq_query_lz4_frame_decode.argtypes = [C.c_char_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]
-    lib.pcq_query_last_error.restype = C.c_char_p
+    lib = pkg.load_query_library()
 
     def decode(frame: bytes, need: int, unit: int = 0):
         out = np.zeros(max(need, 1), dtype=np.uint8)

@@ -10,7 +10,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time"]
 QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time"]
 
@@ -38,10 +38,7 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_method():
 
 
 def host_lib():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_count_bounds_many.argtypes = [C.c_void_p, C.c_size_t, dd, dd, u64p, u64p, u64p]
+    lib = pkg.load_query_library()
     return lib
 
 

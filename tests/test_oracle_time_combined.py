@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QUERY = os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "host", "query")
 QUERY_ORACLE = os.path.join(ROOT, "oracle", "query_oracle")
 POINT_DTYPE = _oracle.POINT_DTYPE
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 COLOR_READ = {2: 20, 3: 28, 5: 28}  # the colour offsets the optimized searches know (las.rs:38-45, last.rs:83-88)
 ALL_FORMATS = sorted(ti.FORMATS)
@@ -303,12 +304,7 @@ def test_search_file_dispatches_the_new_kinds(oracle, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def qlib():
-    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
-    cp, pp, ip, dp = C.POINTER(binding.Columns), C.POINTER(binding.Predicate), C.POINTER(C.c_int), C.POINTER(C.c_double)
-    lib.pcq_query_test_plan_time.argtypes = [C.c_char_p, C.c_double, C.c_double, cp, pp, ip]
-    lib.pcq_query_test_plan_combined.argtypes = [C.c_char_p, dp, dp, C.c_int, C.c_double, C.c_double, cp, pp, ip]
-    lib.pcq_query_last_error.restype = C.c_char_p
-    return lib
+    return pkg.load_query_library()
 
 
 def _column(img, cols, n, width):

@@ -6,13 +6,14 @@ program built with ASan and UBSan.  No GPU call."""
 import ctypes as C
 import importlib
 import os
-import subprocess
+
+import _host
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
            "pcq_scan_dev_count_batch_multi", "pcq_scan_dev_class_hist_batch", "pcq_scan_dev_time_hist_batch", "pcq_scan_dev_raster_batch",
            "pcq_scan_dev_zrange_raster_batch"]
@@ -51,11 +52,8 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_method():
 
 
 def test_host_entry_checks_its_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
+    lib = pkg.load_query_library()
     f = lib.pcq_query_resident_count_polygon
-    f.argtypes = [C.c_void_p, C.c_size_t, dd, C.c_double, C.c_double, u64p, u64p]
     dummy = C.c_void_p(1)  # never dereferenced: a check refuses first
     inf, nan = float("inf"), float("nan")
     tri = (C.c_double * 6)(0, 0, 1, 0, 0, 1)
@@ -90,12 +88,7 @@ def test_polygon_plan_under_address_sanitizer(tmp_path):
     """host/polygon_plan.h against hand-worked numbers under ASan + UBSan, through a stand-alone program (nothing sanitized is loaded
     into python; no device is touched): ties to even on both sides of zero, an anisotropic scale, INT32_MAX and one step beyond, spans of
     2^31 - 1 and 2^31, bad scales, and the box of the rounded vertices."""
-    exe = str(tmp_path / "polygon_plan")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra",
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "native", "polygon_plan_driver.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "native", "polygon_plan_driver.cpp")]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
-    assert r.stdout.split() == ["ok", "44"]
+    assert _host.build_and_run(tmp_path, "polygon_plan", cmd, env) == ["ok", "44"]

@@ -7,13 +7,14 @@ call."""
 import ctypes as C
 import importlib
 import os
-import subprocess
+
+import _host
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_count_batch_bounds_time",
            "pcq_scan_dev_count_batch_multi", "pcq_scan_dev_class_hist_batch", "pcq_scan_dev_time_hist_batch"]
 QUERY_OLD = ["pcq_query_resident_count_bounds", "pcq_query_resident_count_bounds_class", "pcq_query_resident_count_bounds_time",
@@ -45,11 +46,8 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_method():
 
 
 def test_host_entry_checks_its_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
+    lib = pkg.load_query_library()
     f = lib.pcq_query_resident_count_bounds_raster
-    f.argtypes = [C.c_void_p, dd, C.c_double, C.c_double, C.c_uint64, C.c_uint64, u64p, u64p]
     dummy = C.c_void_p(1)  # never dereferenced: a check refuses first
     lo = (C.c_double * 3)(0, 0, 0)
     sentinel = [1000 + 7 * c for c in range(64)]
@@ -72,15 +70,6 @@ def test_host_entry_checks_its_arguments_without_a_device():
         assert list(words) == sentinel and s.value == 15
 
 
-def _build_and_run(tmp_path, name, cmd, env=None):
-    exe = str(tmp_path / name)
-    r = subprocess.run(cmd + ["-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-4000:])
-    return r.stdout.split()
-
-
 def test_host_entry_under_address_sanitizer(tmp_path):
     """The argument checks of the new host entry under ASan + UBSan, through a stand-alone program (nothing sanitized is loaded
     into python; no device is touched).  The two translation units the entry lives in — capi.cpp and resident.cpp — are built
@@ -91,12 +80,12 @@ def test_host_entry_under_address_sanitizer(tmp_path):
            "-I" + os.path.join(ROOT, "include"), "-I" + host, os.path.join(ROOT, "tests", "native", "raster_asan_driver.cpp"),
            os.path.join(host, "capi.cpp"), os.path.join(host, "resident.cpp"), "-L" + PKG, "-lpcq_query", "-lpcq", "-Wl,-rpath," + PKG]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
-    assert _build_and_run(tmp_path, "raster_asan", cmd, env) == ["ok", "28", "4"]
+    assert _host.build_and_run(tmp_path, "raster_asan", cmd, env) == ["ok", "28", "4"]
 
 
 def test_division_against_the_operator(tmp_path):
     """raster_div.h as host code under UBSan: the listed divisors with every quotient below 8192 at its edges, and 10^6 random pairs"""
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undefined",
            "-I" + os.path.join(PKG, "csrc"), os.path.join(ROOT, "tests", "native", "raster_div_driver.cpp")]
-    out = _build_and_run(tmp_path, "raster_div", cmd, dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    out = _host.build_and_run(tmp_path, "raster_div", cmd, dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
     assert out[0] == "ok" and int(out[1]) > 1_000_000 + 12 * 8192

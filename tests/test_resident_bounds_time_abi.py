@@ -16,7 +16,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_NEW = ["pcq_scan_dev_count_batch_bounds_time", "pcq_scan_dev_indexed_bounds_time"]
 QUERY_NEW = ["pcq_query_resident_count_bounds_time", "pcq_query_resident_search_bounds_time"]
 LIB_OLD = ["pcq_scan_dev_count_batch", "pcq_scan_dev_count_batch_combined", "pcq_scan_dev_indexed", "pcq_scan_dev_indexed_combined",
@@ -44,12 +44,8 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_methods():
 
 
 def test_host_entries_refuse_null_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    vp, d3 = C.c_void_p, C.c_double * 3
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_count_bounds_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
-                                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.pcq_query_resident_search_bounds_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, vp]
+    lib = pkg.load_query_library()
+    d3 = C.c_double * 3
     dummy = C.c_void_p(1)  # never dereferenced: another argument is null
     lo, hi = d3(0.0, 0.0, 0.0), d3(1.0, 1.0, 1.0)
     m = C.c_uint64(7)

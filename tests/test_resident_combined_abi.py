@@ -10,7 +10,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_NEW = ["pcq_scan_dev_count_batch_combined", "pcq_scan_dev_indexed_combined"]
 QUERY_NEW = ["pcq_query_resident_count_bounds_class", "pcq_query_resident_search_bounds_class"]
 
@@ -43,16 +43,13 @@ def test_binding_has_the_two_context_methods():
 
 
 def test_host_entries_refuse_null_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    vp, dd = C.c_void_p, C.POINTER(C.c_double)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_count_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, vp, vp]
-    lib.pcq_query_resident_search_bounds_class.argtypes = [vp, dd, dd, C.c_uint8, vp]
+    lib = pkg.load_query_library()
     d3 = (C.c_double * 3)(0.0, 0.0, 0.0)
     dummy = C.c_void_p(1)  # never dereferenced: another argument is null
-    assert lib.pcq_query_resident_count_bounds_class(None, d3, d3, 2, dummy, None) == PCQ_ERR_ARG
-    assert lib.pcq_query_resident_count_bounds_class(dummy, None, d3, 2, dummy, None) == PCQ_ERR_ARG
-    assert lib.pcq_query_resident_count_bounds_class(dummy, d3, None, 2, dummy, None) == PCQ_ERR_ARG
+    words = C.cast(dummy, C.POINTER(C.c_uint64))  # the same address as the pointer type of `matches`
+    assert lib.pcq_query_resident_count_bounds_class(None, d3, d3, 2, words, None) == PCQ_ERR_ARG
+    assert lib.pcq_query_resident_count_bounds_class(dummy, None, d3, 2, words, None) == PCQ_ERR_ARG
+    assert lib.pcq_query_resident_count_bounds_class(dummy, d3, None, 2, words, None) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_count_bounds_class(dummy, d3, d3, 2, None, None) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_search_bounds_class(None, d3, d3, 2, dummy) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_search_bounds_class(dummy, None, d3, 2, dummy) == PCQ_ERR_ARG

@@ -9,7 +9,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 NEW = ["pcq_query_resident_load_points", "pcq_query_resident_search_bounds", "pcq_query_resident_search_class",
        "pcq_query_resident_last_stats"]
 
@@ -23,13 +23,7 @@ def test_resident_point_entries_are_declared_and_exported():
 
 
 def test_resident_point_entries_refuse_null_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    vp, dd = C.c_void_p, C.POINTER(C.c_double)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_load_points.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(vp)]
-    lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
-    lib.pcq_query_resident_search_class.argtypes = [vp, C.c_uint8, vp]
-    lib.pcq_query_resident_last_stats.argtypes = [vp, vp]
+    lib = pkg.load_query_library()
     d3 = (C.c_double * 3)(0.0, 0.0, 0.0)
     dummy = C.c_void_p(1)  # never dereferenced: another argument is null
     h = C.c_void_p()
@@ -44,6 +38,6 @@ def test_resident_point_entries_refuse_null_arguments_without_a_device():
     assert lib.pcq_query_resident_search_bounds(dummy, d3, d3, None) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_search_class(None, 6, dummy) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_search_class(dummy, 6, None) == PCQ_ERR_ARG
-    assert lib.pcq_query_resident_last_stats(None, dummy) == PCQ_ERR_ARG
+    assert lib.pcq_query_resident_last_stats(None, C.cast(dummy, C.POINTER(pkg.IndexStats))) == PCQ_ERR_ARG
     assert lib.pcq_query_resident_last_stats(dummy, None) == PCQ_ERR_ARG
     assert b"null argument" in lib.pcq_query_last_error()

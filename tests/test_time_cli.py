@@ -22,6 +22,7 @@ import _time_images as ti  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
 QUERY = os.path.join(PKG, "host", "query")
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
 
 NEITHER = "Error: Found neither BOUNDS nor CLASS argument but exactly one of these arguments is required!"
@@ -101,11 +102,7 @@ def test_formats_above_10_fail_on_the_host(datadir, fmt_byte, ext):
 
 @pytest.fixture(scope="module")
 def qlib():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    lib.pcq_query_test_plan_time.argtypes = [C.c_char_p, C.c_double, C.c_double, C.POINTER(binding.Columns),
-                                             C.POINTER(binding.Predicate), C.POINTER(C.c_int)]
-    lib.pcq_query_last_error.restype = C.c_char_p
-    return lib
+    return pkg.load_query_library()
 
 
 def _plan(qlib, path, start, end):
@@ -172,7 +169,7 @@ def test_query_library_exports_the_time_search():
     hdr = open(os.path.join(ROOT, "include", "pcq_query.h")).read()
     assert re.search(r"int pcq_query_search_file_time\(const char \*path, double start, double end, int optimized,\s+"
                      r"pcq_host_collector \*c\);", hdr)
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
+    lib = pkg.load_query_library()
     assert hasattr(lib, "pcq_query_search_file_time") and hasattr(lib, "pcq_query_test_plan_time")
     assert re.search(r"PCQ_PRED_TIME = 3\b", open(os.path.join(ROOT, "include", "pcq.h")).read())
     assert binding.PRED_TIME == 3

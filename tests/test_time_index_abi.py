@@ -18,7 +18,7 @@ pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "adhoc-queries-pointclouds_amd")
-PCQ_ERR_ARG = -8
+PCQ_ERR_ARG = pkg.PCQ_ERR_ARG
 LIB_NEW = ["pcq_scan_dev_indexed_time"]
 QUERY_NEW = ["pcq_query_resident_load_with", "pcq_query_resident_search_time"]
 
@@ -45,11 +45,7 @@ def test_abi_number_is_unchanged_and_the_binding_has_the_method():
 
 
 def test_host_entries_refuse_null_arguments_without_a_device():
-    lib = C.CDLL(os.path.join(PKG, "libpcq_query.so"))
-    vp = C.c_void_p
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_load_with.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.c_uint, C.POINTER(vp)]
-    lib.pcq_query_resident_search_time.argtypes = [vp, C.c_double, C.c_double, vp]
+    lib = pkg.load_query_library()
     dummy = C.c_void_p(1)  # never dereferenced: another argument is null
     out = C.c_void_p(7)
     one = (C.c_char_p * 1)(None)

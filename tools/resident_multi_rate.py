@@ -139,13 +139,7 @@ try:
         p = os.path.join(d, f"ca13_{i}.last")
         oracle.synth_write(s, p, threads=16)
         paths.append(p)
-    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
-    dd, u64p = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_load.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_void_p)]
-    lib.pcq_query_resident_count_bounds.argtypes = [C.c_void_p, dd, dd, u64p, u64p]
-    lib.pcq_query_resident_count_bounds_many.argtypes = [C.c_void_p, C.c_size_t, dd, dd, u64p, u64p, u64p]
-    lib.pcq_query_resident_free.argtypes = [C.c_void_p]
+    lib = pkg.load_query_library()
     arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
     h = C.c_void_p()
     assert lib.pcq_query_resident_load(0, arr, len(paths), C.byref(h)) == 0, lib.pcq_query_last_error()

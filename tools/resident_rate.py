@@ -28,13 +28,7 @@ try:
         p = os.path.join(d, f"doc{i}.last")
         oracle.synth_write(s, p)
         paths.append(p)
-    pkg.load_library()
-    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
-    lib.pcq_query_resident_load.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_void_p)]
-    lib.pcq_query_resident_count_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.pcq_query_resident_count_class.argtypes = [C.c_void_p, C.c_uint8, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.pcq_query_resident_free.argtypes = [C.c_void_p]
-    lib.pcq_query_last_error.restype = C.c_char_p
+    lib = pkg.load_query_library()
     arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
     h = C.c_void_p()
     t0 = time.perf_counter()

@@ -167,16 +167,8 @@ try:
         oracle.synth_write(s, p, threads=16)
         paths.append(p)
     t1 = time.perf_counter()
-    lib = C.CDLL(os.path.join(ROOT, "adhoc-queries-pointclouds_amd", "libpcq_query.so"))
-    vp, dd, u64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)
-    lib.pcq_query_last_error.restype = C.c_char_p
-    lib.pcq_query_resident_load_points.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(vp)]
-    lib.pcq_query_resident_free.argtypes = [vp]
-    lib.pcq_query_resident_bounds_zrange_raster.argtypes = [vp, dd, C.c_double, C.c_double, C.c_uint64, C.c_uint64, dd, dd, u64p]
-    lib.pcq_query_resident_search_bounds.argtypes = [vp, dd, dd, vp]
-    lib.pcq_query_collector_new_buffer.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.pcq_query_collector_free.argtypes = [vp]
-    lib.pcq_query_collector_points.argtypes = [vp, vp, C.c_uint64, u64p]
+    lib = pkg.load_query_library()
+    vp, dd = C.c_void_p, C.POINTER(C.c_double)
     arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
     h = vp()
     assert lib.pcq_query_resident_load_points(0, arr, len(paths), C.byref(h)) == 0, lib.pcq_query_last_error()
