@@ -4,7 +4,8 @@ product with one operation list (test_gpu_collector_lifecycle.py, test_collector
 The model: a count collector is a running sum of matches (an external counter also holds what a batched count added to
 it), a buffer collector the concatenation, in call order, of each scan's 31-byte records in file order, a grid collector
 the oracle's SparseGrid fed every match in call order, then file order.  The selection is numpy on the columns:
-lmin <= (x, y, z) <= lmax per axis in i64, cls == C, start <= t < end on float64 (NaN -> False), wmin <= world <= wmax; a
+lmin <= (x, y, z) <= lmax per axis in i64, cls == C, start <= t < end on float64 (NaN -> False), no axis with world < wmin
+or world > wmax (_world_box.keeps: NaN never rejects); a
 record is x * scale + offset (two roundings), the class byte and the colour of the scanned columns — class 0 and colour
 (0, 0, 0) for the time kinds, colour (0, 0, 0) where the scan had no colour column.  The grid's rule is never restated
 here.  reset empties a model; freeing a collector and creating another replaces it.
@@ -25,6 +26,7 @@ import re
 import numpy as np
 
 import _time_images as ti
+import _world_box
 
 _pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
 POINT_DTYPE = _pkg.POINT_DTYPE
@@ -169,9 +171,8 @@ def select(ds, p, n=None):
         sel &= ds.cls[:n] == p["cls"]
     if time_kind(kind):
         sel &= ti.select(ds.t[:n], p["start"], p["end"])
-    if kind == "BOUNDS_F64":
-        w = ds.world()[:n]
-        sel &= np.all((w >= np.asarray(p["wmin"])) & (w <= np.asarray(p["wmax"])), axis=1)
+    if kind == "BOUNDS_F64":  # AABB::contains: a NaN coordinate or face never rejects (_world_box.keeps)
+        sel &= _world_box.keeps(ds.world()[:n], p["wmin"], p["wmax"])
     return sel
 
 
