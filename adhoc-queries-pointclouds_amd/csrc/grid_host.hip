@@ -208,7 +208,9 @@ int pcq_grid_scan(pcq_ctx *ctx, pcq_collector *c, const DevCols &cols_in, const 
         pk16.block_bytes = block_bytes;
 
         const DevGrid &g = c->grid;
-        const unsigned nblocks = ntiles < (uint32_t)ctx->num_cus ? ntiles : (unsigned)ctx->num_cus;  // one workgroup per CU is resident (LDS)
+        const unsigned per_cu = ntiles < (uint32_t)ctx->num_cus ? ntiles : (unsigned)ctx->num_cus;  // one workgroup per CU is resident (LDS)
+        // (tests: grid_p0_blocks > 0 lowers the count, so that a small scan takes a workgroup through many trips of the tile loop)
+        const unsigned nblocks = ctx->grid_p0_blocks > 0 && (unsigned)ctx->grid_p0_blocks < per_cu ? (unsigned)ctx->grid_p0_blocks : per_cu;
         const int agg = ctx->grid_agg;
         // LAST blocks (12-byte positions at an aligned address, a class byte per point, 6-byte colours): the short index arithmetic
         // (TIME: the time column in cls, 8-byte aligned f64s)

@@ -327,6 +327,7 @@ static const Option k_options[] = {
     {"grid_stream", &pcq_ctx::grid_stream, 0, 1, OPT_SET},
     {"grid_tuple16", &pcq_ctx::grid_tuple16, 0, 2, OPT_SET},
     {"grid_block_pad", &pcq_ctx::grid_block_pad, 0, 65536, OPT_SET},
+    {"grid_p0_blocks", &pcq_ctx::grid_p0_blocks, 0, 65536, OPT_SET},  // (lowers pass 0's workgroup count only: grid_host.hip)
     {"emit_park_max", &pcq_ctx::emit_park_max, 0, 256, OPT_SET},
     {"emit_sparse_max", &pcq_ctx::emit_sparse_max, 0, 2048, OPT_SET},
     {"scratch_cap_words", &pcq_ctx::scratch_cap_words, 0, INT64_MAX, OPT_SET},

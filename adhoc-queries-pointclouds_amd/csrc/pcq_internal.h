@@ -351,6 +351,7 @@ struct pcq_ctx {
     int emit_sparse_max = 64;           // option: a tile of 2048 points with at most this many matches is written by k_emit_sparse (0 = never)
     bool scanned_before = false;        // (PCQ_TIMING: the first host / file scan of a context prints where its time goes)
     int grid_block_pad = 0;             // option: 16-byte units between the end of a tile's block of tuples and the next block
+    int grid_p0_blocks = 0;             // option (tests): > 0 = pass 0 runs on at most this many workgroups (never more than one per CU); 0 = one per CU
     int grid_tuple16 = 1;               // option (tests): 0 = every scan writes 24-byte tuples (the form a 16-byte tuple falls back to), 2 = 16-byte tuples without the second level's selector
     int64_t grid_last_tuples = 0;       // diagnostics: tuples the last fold found pending (after pass 0's own fold)
     int64_t grid_last_tuple_bytes = 0;  // diagnostics: bytes per tuple (16 or 24) of the last grid scan's run

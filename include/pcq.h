@@ -483,7 +483,8 @@ int pcq_bind_thread_near_device(pcq_ctx *ctx);
  * the grid collector's tuple size — 1 = 16 bytes with the selector, 2 = without, 0 = 24 bytes — and the coarse fold's form —
  * 1 = k_fold_stream, 0 = k_fold<BIG>; same results in every combination), "grid_block_pad" (tests: 0 .. 65536 units of 16
  * bytes left between a tile's block of tuples and the next one — moves every block's address and phase; same results for
- * every value; default 0), "scratch_cap_words" (tests: while > 0, growing the
+ * every value; default 0), "grid_p0_blocks" (tests: k > 0 = pass 0 of a grid scan runs on min(k, one per CU) workgroups, so that
+ * each takes more tiles in turn; it only lowers the count; same results for every value; 0 = one per CU, the default), "scratch_cap_words" (tests: while > 0, growing the
  * context's device scratch beyond that many 8-byte words fails with PCQ_ERR_NOMEM without an allocation — a buffer scan then
  * emits without parking its matches; 0 = no cap, the default).  pcq_get_option also
  * reads "numa_node" and the grid diagnostics "grid_folds", "grid_level2" (folds that needed a second partition level),

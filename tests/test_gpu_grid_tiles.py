@@ -6,47 +6,16 @@ every mode of the tile fold, on scan-ordered files with equal-distance ties that
 keys inside tiles, and with runs of both tuple widths in one fold."""
 import importlib
 
-import os
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+from _grid_trips import check_same, scan_ordered_image  # noqa: E402
 from test_gpu_scan import DevFile, small_spec  # noqa: E402
 
 TILE = 5120  # P0_TILE of csrc/grid_common.h
-
-
-def scan_ordered_image(oracle, seed, n, fmt, snap_step=512, snap_fraction=0.5):
-    """A LAST image whose points are sorted along x inside y strips (scan lines, boustrophedon), half of them snapped to a
-    coarse lattice — runs of identical positions with different attributes: equal distances, the first in file order must
-    win — and with the last point of every tile repeated as the first point of the next one (a tie across the boundary)."""
-    seed += int(os.environ.get("PCQ_TEST_SEED_BASE", "0"))  # a soak run: other seeds than the committed ones
-    spec = small_spec(seed, n, fmt=fmt)
-    image = oracle.synth_image(spec, transposed=True).copy()
-    hdr = oracle.parse_header(image[:400].tobytes())
-    otp = hdr.offset_to_point_data
-    xyz = image[otp:otp + 12 * n].view("<i4").reshape(n, 3).copy()
-    rng = np.random.default_rng(seed)
-    snap = rng.random(n) < snap_fraction
-    xyz[snap] = xyz[snap] // snap_step * snap_step
-    strip = xyz[:, 1] // 400
-    order = np.lexsort((np.where(strip % 2 == 0, xyz[:, 0], -xyz[:, 0]), strip))
-    xyz = xyz[order]
-    for k in range(TILE, n, TILE):
-        xyz[k] = xyz[k - 1]
-    image[otp:otp + 12 * n] = np.frombuffer(np.ascontiguousarray(xyz).tobytes(), dtype=np.uint8)
-    return image, hdr
-
-
-def check_same(gg, og):
-    assert gg.point_count() == og.point_count()
-    gp, gk = gg.points(), gg.grid_cells()
-    order = np.argsort(gk, kind="stable")
-    assert np.array_equal(gk[order], og.grid_cells())
-    assert gp[order].tobytes() == og.points().tobytes()  # per cell: the same winner, every byte
 
 
 @pytest.mark.parametrize("fmt", [1, 2])

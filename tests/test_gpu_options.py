@@ -29,6 +29,7 @@ RANGED = [
     ("grid_tuple16", "grid_tuple16", 0, 2),
     ("grid_stream", "grid_stream", 0, 1),
     ("grid_block_pad", "grid_block_pad", 0, 65536),
+    ("grid_p0_blocks", "grid_p0_blocks", 0, 65536),
     ("scratch_cap_words", "scratch_cap_words", 0, None),
 ]
 BOOLEAN = [("numa_local", "numa_local"), ("allreduce_single_rank", "allreduce_single_rank")]
