@@ -214,6 +214,7 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_time_hist_batch": (C.c_int, [vp, P(Columns), P(Predicate), C.c_size_t, P(C.c_double), C.c_size_t, vp, vp]),
         "pcq_scan_dev_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]),
         "pcq_scan_dev_zrange_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "pcq_scan_dev_zsum_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
         "pcq_scan_dev_count_batch_polygon": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_int32), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
@@ -512,6 +513,20 @@ class Context:
         wa = (C.c_uint32 * max(len(flat), 1))(*flat)
         _check(self.lib.pcq_scan_dev_zrange_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_zmin), C.c_void_p(d_zmax),
                                                          C.c_void_p(stream)))
+
+    def scan_dev_zsum_raster_batch(self, cols: Sequence[Columns], preds: Sequence[Predicate], cells, nx: int, ny: int, d_count: int,
+                                   d_zsum: int, stream: Optional[int] = None) -> None:
+        """The mean-height raster of a box (segments, predicates and cells as for scan_dev_raster_batch; at most PCQ_ZSUM_CELLS_MAX
+        cells) in ONE pass: for every point (X, Y, Z) inside its segment's box, += 1 into word ((Y - lmin[1]) // cell_y) * nx +
+        (X - lmin[0]) // cell_x of the nx * ny u64 words of d_count and += Z into that i64 word of d_zsum, both modulo 2^64."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        flat = [int(w) for c in cells for w in c]
+        assert len(flat) == 2 * n, "one (x, y) pair of cell widths per segment"
+        wa = (C.c_uint32 * max(len(flat), 1))(*flat)
+        _check(self.lib.pcq_scan_dev_zsum_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_count), C.c_void_p(d_zsum),
+                                                       C.c_void_p(stream)))
 
     def scan_dev_count_batch_polygon(self, cols: Sequence[Columns], preds: Sequence[Predicate], verts, d_total: int,
                                      stream: Optional[int] = None) -> None:

@@ -149,8 +149,8 @@ constexpr int PCQ_SEGMENTS_CLASS_HIST = 0x4348;  // ("CH") no pcq_predicate_kind
 // count and edges behind them, under a kind of its own: the same segments under PCQ_PRED_BOUNDS_TIME are another entry's table.
 constexpr int PCQ_SEGMENTS_TIME_HIST = 0x5448;  // ("TH") no pcq_predicate_kind
 
-// One segment of a density raster launch (scan_raster.hip) or a height raster launch (scan_zrange.hip: the same table under the
-// same kind, since both kernels read every field alike): DevSegment with the segment's cell widths in lattice units and the
+// One segment of a density raster launch (scan_raster.hip) or a height or mean-height raster launch (scan_zrange.hip, scan_zsum.hip: the
+// same table under the same kind, since the kernels read every field alike): DevSegment with the segment's cell widths in lattice units and the
 // magics of the division by them (raster_div.h).  At its own pitch in the same buffers, under a kind of its own: the widths are
 // part of the bytes the upload compares.
 struct DevRasterSegment {
@@ -375,6 +375,7 @@ struct pcq_ctx {
     int class_hist_copies = 0;    // ... and copies of the LDS histogram per wave, 1 / 2 / 4 / 8 / 16 (0 = the product's: CLASS_HIST_COPIES)
     int raster_waves_per_cu = 0;  // density raster (scan_raster.hip): workgroups per CU before the LDS limit (0 = the product's: RASTER_WAVES_PER_CU)
     int zrange_waves_per_cu = 0;  // height raster (scan_zrange.hip): workgroups per CU before the LDS limit (0 = the product's: ZRANGE_WAVES_PER_CU)
+    int zsum_waves_per_cu = 0;    // mean-height raster (scan_zsum.hip): workgroups per CU before the LDS limit (0 = the product's: ZSUM_WAVES_PER_CU)
     int polygon_waves_per_cu = 0; // box AND polygon count (scan_polygon.hip): workgroups per CU (0 = the product's: POLYGON_WAVES_PER_CU)
     int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif
@@ -443,6 +444,9 @@ int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d
 // scan_count_multi.hip: the finish of the height raster, k_finish_zrange on s — block c folds slice c (nblocks words: max z high, min z
 // low) of the context's partials with a signed min / max into d_zmin[c] / d_zmax[c]
 int pcq_launch_finish_zrange(pcq_ctx *ctx, int ncells, int nblocks, int32_t *d_zmin, int32_t *d_zmax, hipStream_t s);
+// scan_count_multi.hip: the finish of the mean-height raster, k_finish_counts on s twice — slice c (nblocks words) of the context's
+// partials += into d_count[c], slice ncells + c += into d_zsum[c], both modulo 2^64
+int pcq_launch_finish_zsum(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_count, int64_t *d_zsum, hipStream_t s);
 // scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)
 int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s);
 // scan_generic.hip

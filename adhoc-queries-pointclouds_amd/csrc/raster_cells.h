@@ -1,8 +1,8 @@
 // raster_cells.h — what the kernels that bin the points of a box into the cells of a 2-D raster over x and y share: the density
-// raster (scan_raster.hip: a count per cell) and the height raster (scan_zrange.hip: min and max z per cell).  The cursor kind of
+// raster (scan_raster.hip: a count per cell), the height raster (scan_zrange.hip: min and max z per cell) and the mean-height raster (scan_zsum.hip: count and z sum per cell).  The cursor kind of
 // seg_seek (scan_tiles.h) that carries a segment's origin, cell widths and division magics through SGPRs, the cell of a point,
 // the move of a value from the next lane, the gather of a load's points (slot_xy, for the polygon count of scan_polygon.hip), and
-// — host side — the one fill of a DevRasterSegment with every refusal of the two entries.
+// — host side — the one fill of a DevRasterSegment with every refusal of the three entries.
 #pragma once
 
 #include "pcq_internal.h"

@@ -243,6 +243,16 @@ int pcq_launch_finish_counts(pcq_ctx *ctx, int nslices, int nblocks, uint64_t *d
     return PCQ_OK;
 }
 
+// The finish of the mean-height raster (scan_zsum.hip): k_finish_counts twice, over the count slices into d_count and over the sum
+// slices behind them into d_zsum — the sums are two's complement words, so the unsigned add modulo 2^64 is the signed one.
+int pcq_launch_finish_zsum(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_count, int64_t *d_zsum, hipStream_t s) {
+    const uint64_t *sums = ctx->d_partials + (uint64_t)ncells * (uint64_t)nblocks;
+    hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)ncells), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_count);
+    hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)ncells), dim3(BLOCK), 0, s, sums, nblocks, reinterpret_cast<uint64_t *>(d_zsum));
+    PCQ_HIP(hipGetLastError());
+    return PCQ_OK;
+}
+
 int pcq_launch_finish_zrange(pcq_ctx *ctx, int ncells, int nblocks, int32_t *d_zmin, int32_t *d_zmax, hipStream_t s) {
     hipLaunchKernelGGL(k_finish_zrange, dim3((unsigned)ncells), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_zmin, d_zmax);
     PCQ_HIP(hipGetLastError());

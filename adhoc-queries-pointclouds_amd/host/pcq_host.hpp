@@ -393,6 +393,20 @@ public:
     // scale is not finite or not above 0.
     Status bounds_zrange_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, double *zlo, double *zhi,
                                 uint64_t *points_scanned = nullptr);
+    // the mean-height raster of a box: count[cy * nx + cx] is what the density raster counts in cell (cx, cy) and zmean[...] the mean
+    // world z of those points, NaN where it counts none.  ONE pass per batch of files of one z lattice (bitwise-equal scale[2] and
+    // offset[2], groups in the order of their first file; within a group the files in load order in batches of fewer than 2^32 points:
+    // zsum_plan.h) and block of PCQ_ZSUM_CELLS_MAX cells; a batch gives per cell the u64 count cnt and the i64 sum of the stored z.  The
+    // result is DEFINED as, per cell, over the batches in that order, in f64 with every product rounded before the add (no fused
+    // multiply-add: host/Makefile compiles with -ffp-contract=off), W and N starting at 0:
+    //
+    //     W += offset * (double)cnt + scale * (double)(int64_t)sum;   N += cnt;
+    //     count[c] = N;   zmean[c] = N ? W / (double)N : NaN
+    //
+    // The caller has checked nx, ny and cell_size.  bounds_zrange_raster's errors, and PCQ_ERR_UNSUPPORTED for a scanned file of 2^32
+    // points or more.  On any failure the outputs are left as they were.
+    Status bounds_zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count, double *zmean,
+                               uint64_t *points_scanned = nullptr);
     // box AND polygon, count only: the points with z in [zmin, zmax] inside the outline of nverts finite world vertices xy[nverts][2]
     // (even-odd, exact in each file's lattice: polygon_plan.h), from ONE pass.  The caller has checked nverts and the vertices.  A
     // scanned file the outline cannot be asked of (its x or y scale, a vertex outside its i32 lattice, a span above 2^31 - 1):
@@ -419,7 +433,7 @@ private:
     Status box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg);
     Status run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out);
     Status raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, Segments *seg,
-                           std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster
+                           std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster, bounds_zmean_raster
     Status count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     Status search_files(const AABB *bounds, pcq_predicate pred, ResultCollector &rc);  // search_*
@@ -428,7 +442,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster and of bounds_zrange_raster: two i32)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster and of bounds_zrange_raster: two i32; two per cell of bounds_zmean_raster)
     uint64_t points_ = 0;
 };
 

@@ -35,6 +35,10 @@
 // lattice, one pcq_scan_dev_zrange_raster_batch per group of files of one z lattice and block of PCQ_ZRANGE_CELLS_MAX cells, instead of
 // a search into a buffer collector whose records the host would have to reduce.
 //
+// The mean-height raster of a box (bounds_zmean_raster): the count and the mean world z of the points of every cell of the same
+// lattice, one pcq_scan_dev_zsum_raster_batch per batch of files of one z lattice (zsum_plan.h) and block of PCQ_ZSUM_CELLS_MAX
+// cells, the batches' counts and sums merged on the host in world space.
+//
 // Box AND polygon (count_polygon): the points inside a world outline, one pcq_scan_dev_count_batch_polygon over the surviving files
 // with the outline rounded into each file's lattice (polygon_plan.h).
 #include <algorithm>
@@ -43,6 +47,7 @@
 
 #include "pcq_host.hpp"
 #include "polygon_plan.h"
+#include "zsum_plan.h"
 
 namespace pcq {
 
@@ -348,7 +353,7 @@ Status ResidentDataset::count_polygon(size_t nverts, const double *xy, double zm
     return Status::Ok();
 }
 
-// The prologue of the two rasters of a box (count_bounds_raster, bounds_zrange_raster): the prologue of count_box with the world
+// The prologue of the three rasters of a box (count_bounds_raster, bounds_zrange_raster, bounds_zmean_raster): the prologue of count_box with the world
 // box of the whole raster, then per surviving file the cell as a whole number of that file's lattice steps (else
 // PCQ_ERR_UNSUPPORTED) and the file's box cut to full cells: lmin .. lmin + n k - 1 on x and y.  cells: [segment][2], the cell in
 // each segment's lattice steps.  z_lattice: a surviving file whose z scale is not finite or not above 0 is PCQ_ERR_UNSUPPORTED as
@@ -511,6 +516,83 @@ Status ResidentDataset::bounds_zrange_raster(const double bmin[3], double zmax, 
     }
     memcpy(zlo, lo.data(), words * sizeof(double));
     memcpy(zhi, hi.data(), words * sizeof(double));
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
+}
+
+// How high is this box on average, cell by cell: raster_segments (with the z lattice rule), the surviving files in groups of one z
+// lattice as for bounds_zrange_raster, and within a group the files, in load order, in batches of fewer than 2^32 points
+// (zsum_plan.h), so that a batch's i64 sums cannot wrap.  Per batch the dataset's counter holds nx * ny u64 counts and behind them
+// nx * ny i64 sums, zeroed; per block of at most PCQ_ZSUM_CELLS_MAX cells ONE pcq_scan_dev_zsum_raster_batch over the batch's files
+// on the context's stream; then one copy back.  The merge, per cell and in batch order (groups in the order of their first file):
+//
+//     W += offset * (double)cnt + scale * (double)(int64_t)sum;   N += cnt;
+//     count[c] = N;   zmean[c] = N ? W / (double)N : NaN
+//
+// every product rounded before the add: this file is compiled with -ffp-contract=off (host/Makefile), and the two products are
+// named values below.  `count`, `zmean` and `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::bounds_zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count,
+                                            double *zmean, uint64_t *points_scanned) {
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, &seg, &cells);
+    if (!st.ok()) return st;
+    const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZSUM_CELLS_MAX);
+    const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
+    std::vector<double> W(words, 0.0);
+    std::vector<uint64_t> N(words, 0), got(2 * words), cnt(words), sum(words);
+    std::vector<uint8_t> grouped(nseg, 0);
+    for (size_t first = 0; first < nseg; first++) {
+        if (grouped[first]) continue;
+        const double scale = seg.cols[first].scale[2], offset = seg.cols[first].offset[2];
+        std::vector<size_t> members;  // of seg, in load order
+        std::vector<uint64_t> points;
+        for (size_t i = first; i < nseg; i++) {
+            if (grouped[i] || memcmp(&seg.cols[i].scale[2], &scale, 8) || memcmp(&seg.cols[i].offset[2], &offset, 8)) continue;
+            grouped[i] = 1;
+            members.push_back(i);
+            points.push_back(seg.cols[i].n);
+        }
+        std::vector<zsum_plan::Batch> batches;
+        size_t refused = 0;
+        if (!zsum_plan::cut(points, zsum_plan::POINTS_LIMIT, &batches, &refused)) {
+            std::string path;  // (a file with points owns its positions block)
+            for (const auto &f : files_)
+                if (f.xyz == seg.cols[members[refused]].xyz) path = f.path;
+            return Status::Err(PCQ_ERR_UNSUPPORTED, "mean-height raster: 2^32 points or more in " + path);
+        }
+        for (const zsum_plan::Batch &batch : batches) {
+            Segments grp;
+            std::vector<uint32_t> gcells;
+            for (size_t m = batch.begin; m < batch.end; m++) {
+                const size_t i = members[m];
+                grp.cols.push_back(seg.cols[i]);
+                grp.preds.push_back(seg.preds[i]);
+                gcells.push_back(cells[2 * i]), gcells.push_back(cells[2 * i + 1]);
+            }
+            st = read_counts(2 * words, [&] {
+                int rc = PCQ_OK;
+                int64_t *const d_sum = reinterpret_cast<int64_t *>(counter_ + words);
+                std::vector<pcq_predicate> preds(grp.preds.size());
+                for (size_t b = 0; b < blocks.size() && !rc; b++) {
+                    for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(grp.preds[i], &gcells[2 * i], blocks[b]);
+                    rc = pcq_scan_dev_zsum_raster_batch(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(), (uint32_t)blocks[b].w,
+                                                        (uint32_t)blocks[b].h, counter_ + blocks[b].at, d_sum + blocks[b].at, nullptr);
+                }
+                return rc;
+            }, got.data());
+            if (!st.ok()) return st;
+            scatter_blocks(blocks, got.data(), nx, cnt.data());
+            scatter_blocks(blocks, got.data() + words, nx, sum.data());
+            for (size_t c = 0; c < words; c++) {
+                const double a = offset * (double)cnt[c], b = scale * (double)(int64_t)sum[c];
+                W[c] += a + b;
+                N[c] += cnt[c];
+            }
+        }
+    }
+    const double nan = std::nan("");
+    for (size_t c = 0; c < words; c++) count[c] = N[c], zmean[c] = N[c] ? W[c] / (double)N[c] : nan;
     if (points_scanned) *points_scanned = seg.scanned;
     return Status::Ok();
 }

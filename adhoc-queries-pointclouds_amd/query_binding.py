@@ -1,6 +1,6 @@
-"""ctypes view of include/pcq_query.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
+"""ctypes view of include/pcq_query.h and include/pcq_query_stats.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
 
-Plumbing only, in the style of binding.load_library(): ONE signature table for every function the header declares, so that no
+Plumbing only, in the style of binding.load_library(): ONE signature table per header for every function it declares, so that no
 caller writes an argtypes line of its own.  The conventions, chosen once:
 
   * three-vectors, edge tables and vertex arrays are POINTER(c_double) (d3(v) builds a three-vector; a float64 numpy array goes
@@ -91,7 +91,16 @@ def _signatures() -> dict:
     }
 
 
+def _stats_signatures() -> dict:
+    vp, u64, dbl = C.c_void_p, C.c_uint64, C.c_double
+    dd, pu64 = C.POINTER(dbl), C.POINTER(u64)
+    return {
+        "pcq_query_resident_bounds_zmean_raster": (C.c_int, [vp, dd, dbl, dbl, u64, u64, pu64, dd, pu64]),
+    }
+
+
 sig = _signatures()   # {name: (restype, argtypes)} for every function of include/pcq_query.h
+stats_sig = _stats_signatures()   # the same for include/pcq_query_stats.h (which says why it is a header of its own)
 _qlib = None
 
 
@@ -106,7 +115,7 @@ def load_query_library() -> C.CDLL:
         raise RuntimeError(f"{path} is missing: build the host layer first (make -C {_HERE}/host, or __graft_entry__.build()).")
     binding.load_library()
     lib = C.CDLL(path)
-    for name, (res, args) in sig.items():
+    for name, (res, args) in list(sig.items()) + list(stats_sig.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -329,6 +329,27 @@ int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_p
 #define PCQ_ZRANGE_CELLS_MAX 4096
 int pcq_scan_dev_zrange_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                                      size_t nsegments, uint32_t nx, uint32_t ny, int32_t *device_zmin, int32_t *device_zmax, void *stream);
+/* The mean-height raster of a box in ONE pass: "how high is this box on average, cell by cell?" — the count and the z sum a mean
+ * rests on.  Layout, predicate kind, `cell_xy`, the cell rule and the refusals are those of pcq_scan_dev_raster_batch, word for
+ * word; only the limit on nx * ny differs: PCQ_ZSUM_CELLS_MAX.  A point (X, Y, Z) of segment i inside the box of preds[i] lies in
+ * cell c = cy * nx + cx with cx = (X - lmin[0]) / cell_xy[2i] and cy = (Y - lmin[1]) / cell_xy[2i + 1], exact integer floor
+ * divisions.  The call ADDS: for every such point device_count[c] += 1 and device_zsum[c] += (int64_t)Z, Z the stored i32
+ * sign-extended, for every cell at once and from one read of the data.  Both are 64-bit adds MODULO 2^64 (two's complement for the
+ * sum): what the words hold afterwards is the sum of what they held and of every contribution, reduced modulo 2^64, in whatever
+ * order the adds happen.  The sums are exact outright while the true values fit i64, which fewer than 2^32 points into zeroed
+ * words guarantees (|Z| <= 2^31, so |sum| < 2^63).  device_count after a call from zeroed words is exactly what
+ * pcq_scan_dev_raster_batch gives.  Z is in the segment's OWN integer lattice: the sums of segments whose z scale or z offset
+ * differ do not add up, so a caller batches segments of one z lattice per call (pcq_query_resident_bounds_zmean_raster does).  No
+ * word at or beyond nx * ny of either array is touched.  A predicate that is empty matches nothing and its segment is not
+ * evaluated; a point that fails only the z test of its box contributes nothing.  nsegments == 0 is PCQ_OK after the argument
+ * checks.  A null argument (device_count and device_zsum among them), nx == 0, ny == 0 or nx * ny above PCQ_ZSUM_CELLS_MAX, any
+ * other predicate kind, any other layout, a cell width of 0 in a segment with points, a non-empty predicate whose lmin[0] or
+ * lmin[1] lies outside the i32 range, and a non-empty predicate whose box reaches beyond the raster — (min(lmax[a], INT32_MAX) -
+ * lmin[a]) / cell >= n for a = 0 or 1 — are refused (PCQ_ERR_ARG) before anything is uploaded or launched: both arrays are
+ * untouched.  lmax and lmin[2] may be anywhere. */
+#define PCQ_ZSUM_CELLS_MAX 2048
+int pcq_scan_dev_zsum_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                                   size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_count, int64_t *device_zsum, void *stream);
 /* Box AND polygon in ONE pass: "how many points of this box lie inside this outline?".  Every predicate is PCQ_PRED_BOUNDS and the
  * layout is that of pcq_scan_dev_count_batch_multi: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.
  * `verts_xy` is a HOST pointer to [nsegments][nverts][2] i32, in each segment's own lattice.  The rule, all in a segment's integer
