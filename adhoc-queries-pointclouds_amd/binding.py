@@ -215,6 +215,8 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp]),
         "pcq_scan_dev_zrange_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
         "pcq_scan_dev_zsum_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "pcq_scan_dev_zsum_raster_batch_classes": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                                             P(C.c_uint32), vp, vp, vp]),
         "pcq_scan_dev_count_batch_polygon": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_int32), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
@@ -277,6 +279,16 @@ def exported_symbols(path: str) -> set:
     import subprocess
     txt = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return {line.split()[-1] for line in txt.splitlines() if line.strip()}
+
+
+def class_set_words(classes) -> list:
+    """A set of class bytes as the eight words of pcq.h / pcq_query_classes.h: class c is bit (c & 31) of word c >> 5."""
+    words = [0] * 8
+    for c in classes:
+        c = int(c)
+        assert 0 <= c <= 255, "a class is a byte"
+        words[c >> 5] |= 1 << (c & 31)
+    return words
 
 
 def _check(rc: int) -> None:
@@ -527,6 +539,21 @@ class Context:
         wa = (C.c_uint32 * max(len(flat), 1))(*flat)
         _check(self.lib.pcq_scan_dev_zsum_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_count), C.c_void_p(d_zsum),
                                                        C.c_void_p(stream)))
+
+    def scan_dev_zsum_raster_batch_classes(self, cols: Sequence[Columns], preds: Sequence[Predicate], cells, nx: int, ny: int, classes,
+                                           d_count: int, d_zsum: int, stream: Optional[int] = None) -> None:
+        """The mean-height raster of the points of a set of classes (scan_dev_zsum_raster_batch restricted to them; segments laid
+        out as for scan_dev_count_batch_combined: cls beside xyz) in ONE pass.  classes: the class bytes of the set, an iterable of
+        0 .. 255 (class_set_words makes the eight words), or None for a null class_set."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        flat = [int(w) for c in cells for w in c]
+        assert len(flat) == 2 * n, "one (x, y) pair of cell widths per segment"
+        wa = (C.c_uint32 * max(len(flat), 1))(*flat)
+        sa = None if classes is None else (C.c_uint32 * 8)(*class_set_words(classes))
+        _check(self.lib.pcq_scan_dev_zsum_raster_batch_classes(self.handle, ca, pa, wa, n, nx, ny, sa, C.c_void_p(d_count),
+                                                               C.c_void_p(d_zsum), C.c_void_p(stream)))
 
     def scan_dev_count_batch_polygon(self, cols: Sequence[Columns], preds: Sequence[Predicate], verts, d_total: int,
                                      stream: Optional[int] = None) -> None:

@@ -167,6 +167,16 @@ struct DevRasterSegment {
 static_assert(sizeof(DevRasterSegment) == 72, "DevRasterSegment: DevSegment and four words");
 constexpr int PCQ_SEGMENTS_RASTER = 0x5253;  // ("RS") no pcq_predicate_kind
 
+// One segment of a class-filtered mean-height raster launch (scan_zsum_classes.hip): DevRasterSegment with the class block of the
+// same points beside it.  At its own pitch in the same buffers, under a kind of its own: the cached table of a raster launch is
+// never taken for this entry's, nor this one's for theirs.  The class SET of a launch is no part of the table (it travels as
+// kernel arguments), so two calls that differ in the set alone share one table.
+struct DevRasterClassSegment : DevRasterSegment {  // (so raster_segment_fill of raster_cells.h fills it, with every refusal)
+    const uint8_t *cls;    // classification block of the same points, any alignment
+};
+static_assert(sizeof(DevRasterClassSegment) == 80, "DevRasterClassSegment: DevRasterSegment and the class pointer");
+constexpr int PCQ_SEGMENTS_RASTER_CLASSES = 0x5243;  // ("RC") no pcq_predicate_kind
+
 // One segment of a box AND polygon count launch (scan_polygon.hip): DevSegment with the place of the segment's edges in the
 // trailer behind the table.  An edge is a DevPolygonEdge: the outline's edge with its lower end first; horizontal edges, which never
 // cross a point, do not travel.  At its own pitch in the same buffers, under a kind of its own; the edges are part of the bytes the
@@ -376,6 +386,7 @@ struct pcq_ctx {
     int raster_waves_per_cu = 0;  // density raster (scan_raster.hip): workgroups per CU before the LDS limit (0 = the product's: RASTER_WAVES_PER_CU)
     int zrange_waves_per_cu = 0;  // height raster (scan_zrange.hip): workgroups per CU before the LDS limit (0 = the product's: ZRANGE_WAVES_PER_CU)
     int zsum_waves_per_cu = 0;    // mean-height raster (scan_zsum.hip): workgroups per CU before the LDS limit (0 = the product's: ZSUM_WAVES_PER_CU)
+    int zsum_classes_waves_per_cu = 0;  // class-filtered mean-height raster (scan_zsum_classes.hip): the same (0 = the product's: ZSUM_CLASSES_WAVES_PER_CU)
     int polygon_waves_per_cu = 0; // box AND polygon count (scan_polygon.hip): workgroups per CU (0 = the product's: POLYGON_WAVES_PER_CU)
     int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif

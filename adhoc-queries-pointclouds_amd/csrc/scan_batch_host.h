@@ -26,6 +26,7 @@ struct K1Batch {
     bool null_refused;   // positions that are null with n > 0 are refused (the plain box kind never has)
     const void *trailer = nullptr;  // launch-level data behind the table in HBM (8-byte aligned there: every Seg is)
     size_t trailer_bytes = 0;
+    bool checks_only = false;       // every refusal of the table, then PCQ_OK: no upload, no launch, no finish (the class-filtered mean-height raster's empty set)
 };
 template <typename Seg, typename DP>
 void seg_box(Seg &g, const DP &dp) {
@@ -52,6 +53,7 @@ int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, siz
         g.tile_begin = steps;
         steps += cols[i].n / ((uint64_t)K1_TILES * TILE_POINTS);
     }
+    if (b.checks_only) return PCQ_OK;
     int rc = pcq_scratch_stream(ctx, s);
     if (rc) return rc;
     if (b.trailer_bytes) {

@@ -407,6 +407,12 @@ public:
     // points or more.  On any failure the outputs are left as they were.
     Status bounds_zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count, double *zmean,
                                uint64_t *points_scanned = nullptr);
+    // the mean-height raster of the points of a set of classes ("how high is the ground"): bounds_zmean_raster with cnt and sum taken
+    // over the points whose class byte is in the set — bit (c & 31) of class_set[c >> 5] — by pcq_scan_dev_zsum_raster_batch_classes:
+    // the same prologue, groups, batches, blocks and merge formula, the same errors, the same points_scanned.  All 256 bits set: bit
+    // for bit bounds_zmean_raster's result.  An empty set: every count 0 and every mean NaN without a launch, after every refusal.
+    Status bounds_zmean_raster_classes(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t class_set[8],
+                                       uint64_t *count, double *zmean, uint64_t *points_scanned = nullptr);
     // box AND polygon, count only: the points with z in [zmin, zmax] inside the outline of nverts finite world vertices xy[nverts][2]
     // (even-odd, exact in each file's lattice: polygon_plan.h), from ONE pass.  The caller has checked nverts and the vertices.  A
     // scanned file the outline cannot be asked of (its x or y scale, a vertex outside its i32 lattice, a span above 2^31 - 1):
@@ -432,8 +438,10 @@ private:
     Status read_counts(size_t words, Launch launch, uint64_t *out);  // (resident.cpp only)
     Status box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg);
     Status run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out);
-    Status raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, Segments *seg,
-                           std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster, bounds_zmean_raster
+    Status raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, int col_kind,
+                           Segments *seg, std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster, zmean_raster
+    Status zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t *class_set, uint64_t *count,
+                        double *zmean, uint64_t *points_scanned);  // bounds_zmean_raster (class_set null: every point), bounds_zmean_raster_classes
     Status count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
     Status scan(ResidentFile &f, const pcq_predicate &pred, ResultCollector &rc);
     Status search_files(const AABB *bounds, pcq_predicate pred, ResultCollector &rc);  // search_*

@@ -37,7 +37,8 @@
 //
 // The mean-height raster of a box (bounds_zmean_raster): the count and the mean world z of the points of every cell of the same
 // lattice, one pcq_scan_dev_zsum_raster_batch per batch of files of one z lattice (zsum_plan.h) and block of PCQ_ZSUM_CELLS_MAX
-// cells, the batches' counts and sums merged on the host in world space.
+// cells, the batches' counts and sums merged on the host in world space.  Of the points of a set of classes
+// (bounds_zmean_raster_classes): the same body with pcq_scan_dev_zsum_raster_batch_classes and the class blocks in the columns.
 //
 // Box AND polygon (count_polygon): the points inside a world outline, one pcq_scan_dev_count_batch_polygon over the surviving files
 // with the outline rounded into each file's lattice (polygon_plan.h).
@@ -358,7 +359,7 @@ Status ResidentDataset::count_polygon(size_t nverts, const double *xy, double zm
 // PCQ_ERR_UNSUPPORTED) and the file's box cut to full cells: lmin .. lmin + n k - 1 on x and y.  cells: [segment][2], the cell in
 // each segment's lattice steps.  z_lattice: a surviving file whose z scale is not finite or not above 0 is PCQ_ERR_UNSUPPORTED as
 // well (the height raster's conversion to world z has to be monotone).
-Status ResidentDataset::raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, Segments *seg,
+Status ResidentDataset::raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, int col_kind, Segments *seg,
                                         std::vector<uint32_t> *cells) {
     const double bmax[3] = {bmin[0] + (double)nx * cell_size, bmin[1] + (double)ny * cell_size, zmax};
     AABB bounds;
@@ -383,7 +384,7 @@ Status ResidentDataset::raster_segments(const double bmin[3], double zmax, doubl
         const double sz = f.header.scale[2];
         if (z_lattice && (!(sz > 0.0) || sz - sz != 0.0))
             return Status::Err(PCQ_ERR_UNSUPPORTED, "height raster: the z scale is not finite and above 0 in " + f.path);
-        seg->cols.push_back(file_columns(f, PCQ_PRED_BOUNDS));
+        seg->cols.push_back(file_columns(f, col_kind));
         seg->preds.push_back(pred);
         seg->scanned += f.header.number_of_points;
     }
@@ -438,7 +439,7 @@ Status ResidentDataset::count_bounds_raster(const double bmin[3], double zmax, d
                                             uint64_t *points_scanned) {
     Segments seg;
     std::vector<uint32_t> cells;  // [segment][2]
-    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/false, &seg, &cells);
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/false, PCQ_PRED_BOUNDS, &seg, &cells);
     if (!st.ok()) return st;
     const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_RASTER_CELLS_MAX);
     const size_t words = (size_t)(nx * ny);
@@ -471,7 +472,7 @@ Status ResidentDataset::bounds_zrange_raster(const double bmin[3], double zmax, 
                                              uint64_t *points_scanned) {
     Segments seg;
     std::vector<uint32_t> cells;  // [segment][2]
-    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, &seg, &cells);
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, PCQ_PRED_BOUNDS, &seg, &cells);
     if (!st.ok()) return st;
     const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZRANGE_CELLS_MAX);
     const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
@@ -531,12 +532,26 @@ Status ResidentDataset::bounds_zrange_raster(const double bmin[3], double zmax, 
 //
 // every product rounded before the add: this file is compiled with -ffp-contract=off (host/Makefile), and the two products are
 // named values below.  `count`, `zmean` and `points_scanned` are written only when everything has succeeded.
+//
+// class_set (null: every point) restricts cnt and sum to the points whose class byte is in the set: the columns then carry the class
+// blocks and the launch is pcq_scan_dev_zsum_raster_batch_classes; everything else is the same code.  An empty set makes every
+// refusal and no launch: cnt and sum are 0 in every batch.
 Status ResidentDataset::bounds_zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count,
                                             double *zmean, uint64_t *points_scanned) {
+    return zmean_raster(bmin, zmax, cell_size, nx, ny, nullptr, count, zmean, points_scanned);
+}
+Status ResidentDataset::bounds_zmean_raster_classes(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny,
+                                                    const uint32_t class_set[8], uint64_t *count, double *zmean, uint64_t *points_scanned) {
+    return zmean_raster(bmin, zmax, cell_size, nx, ny, class_set, count, zmean, points_scanned);
+}
+Status ResidentDataset::zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t *class_set,
+                                     uint64_t *count, double *zmean, uint64_t *points_scanned) {
     Segments seg;
     std::vector<uint32_t> cells;  // [segment][2]
-    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, &seg, &cells);
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, class_set ? PCQ_PRED_BOUNDS_CLASS : PCQ_PRED_BOUNDS, &seg, &cells);
     if (!st.ok()) return st;
+    bool none = class_set != nullptr;  // the empty set
+    for (int w = 0; class_set && w < 8; w++) none = none && class_set[w] == 0;
     const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZSUM_CELLS_MAX);
     const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
     std::vector<double> W(words, 0.0);
@@ -562,6 +577,7 @@ Status ResidentDataset::bounds_zmean_raster(const double bmin[3], double zmax, d
             return Status::Err(PCQ_ERR_UNSUPPORTED, "mean-height raster: 2^32 points or more in " + path);
         }
         for (const zsum_plan::Batch &batch : batches) {
+            if (none) break;  // (W and N stay 0)
             Segments grp;
             std::vector<uint32_t> gcells;
             for (size_t m = batch.begin; m < batch.end; m++) {
@@ -576,8 +592,12 @@ Status ResidentDataset::bounds_zmean_raster(const double bmin[3], double zmax, d
                 std::vector<pcq_predicate> preds(grp.preds.size());
                 for (size_t b = 0; b < blocks.size() && !rc; b++) {
                     for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(grp.preds[i], &gcells[2 * i], blocks[b]);
-                    rc = pcq_scan_dev_zsum_raster_batch(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(), (uint32_t)blocks[b].w,
-                                                        (uint32_t)blocks[b].h, counter_ + blocks[b].at, d_sum + blocks[b].at, nullptr);
+                    rc = class_set ? pcq_scan_dev_zsum_raster_batch_classes(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(),
+                                                                            (uint32_t)blocks[b].w, (uint32_t)blocks[b].h, class_set,
+                                                                            counter_ + blocks[b].at, d_sum + blocks[b].at, nullptr)
+                                   : pcq_scan_dev_zsum_raster_batch(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(),
+                                                                    (uint32_t)blocks[b].w, (uint32_t)blocks[b].h, counter_ + blocks[b].at,
+                                                                    d_sum + blocks[b].at, nullptr);
                 }
                 return rc;
             }, got.data());

@@ -1,4 +1,4 @@
-"""ctypes view of include/pcq_query.h and include/pcq_query_stats.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
+"""ctypes view of include/pcq_query.h, include/pcq_query_stats.h and include/pcq_query_classes.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
 
 Plumbing only, in the style of binding.load_library(): ONE signature table per header for every function it declares, so that no
 caller writes an argtypes line of its own.  The conventions, chosen once:
@@ -99,8 +99,17 @@ def _stats_signatures() -> dict:
     }
 
 
+def _classes_signatures() -> dict:
+    vp, u64, dbl = C.c_void_p, C.c_uint64, C.c_double
+    dd, pu64 = C.POINTER(dbl), C.POINTER(u64)
+    return {
+        "pcq_query_resident_bounds_zmean_raster_classes": (C.c_int, [vp, dd, dbl, dbl, u64, u64, C.POINTER(C.c_uint32), pu64, dd, pu64]),
+    }
+
+
 sig = _signatures()   # {name: (restype, argtypes)} for every function of include/pcq_query.h
 stats_sig = _stats_signatures()   # the same for include/pcq_query_stats.h (which says why it is a header of its own)
+classes_sig = _classes_signatures()   # the same for include/pcq_query_classes.h (a header of its own for the same reason)
 _qlib = None
 
 
@@ -115,7 +124,7 @@ def load_query_library() -> C.CDLL:
         raise RuntimeError(f"{path} is missing: build the host layer first (make -C {_HERE}/host, or __graft_entry__.build()).")
     binding.load_library()
     lib = C.CDLL(path)
-    for name, (res, args) in list(sig.items()) + list(stats_sig.items()):
+    for name, (res, args) in list(sig.items()) + list(stats_sig.items()) + list(classes_sig.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

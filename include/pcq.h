@@ -350,6 +350,19 @@ int pcq_scan_dev_zrange_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, cons
 #define PCQ_ZSUM_CELLS_MAX 2048
 int pcq_scan_dev_zsum_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                                    size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_count, int64_t *device_zsum, void *stream);
+/* The mean-height raster of the points of a SET of classes in ONE pass: "how high is the ground of this box, cell by cell?".
+ * pcq_scan_dev_zsum_raster_batch restricted to the points whose class byte is in the set: the same cells, the same two adds modulo
+ * 2^64 for every point inside the box of its segment AND of a class in the set, at most PCQ_ZSUM_CELLS_MAX cells, PCQ_PRED_BOUNDS
+ * predicates only, every refusal of that entry.  `class_set` is a HOST pointer to eight words: class c is in the set when bit
+ * (c & 31) of class_set[c >> 5] is set: the whole class byte, as the LAST class search compares it.  Segments are laid out as for
+ * pcq_scan_dev_count_batch_combined: beside the positions, cols[i].cls is the classification block of the same points (cls_stride
+ * 1, any alignment).  device_count after a call from zeroed words is the class-filtered density raster; with all 256 bits set both
+ * arrays receive exactly what pcq_scan_dev_zsum_raster_batch adds.  Refused besides (PCQ_ERR_ARG, both arrays untouched): a null
+ * class_set, a segment with points whose cls is null, a segment with points whose cls_stride is not 1.  An empty set (eight zero
+ * words) is PCQ_OK after every check: nothing is uploaded or launched and the words stay as they were. */
+int pcq_scan_dev_zsum_raster_batch_classes(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                                           size_t nsegments, uint32_t nx, uint32_t ny, const uint32_t class_set[8],
+                                           uint64_t *device_count, int64_t *device_zsum, void *stream);
 /* Box AND polygon in ONE pass: "how many points of this box lie inside this outline?".  Every predicate is PCQ_PRED_BOUNDS and the
  * layout is that of pcq_scan_dev_count_batch_multi: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.
  * `verts_xy` is a HOST pointer to [nsegments][nverts][2] i32, in each segment's own lattice.  The rule, all in a segment's integer

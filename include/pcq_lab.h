@@ -12,7 +12,8 @@
  * of the density raster of a box before its LDS limit and the form of its LDS add, 1 per lane or 2 wave-level
  * (profiles/raster_rate_sweep.log), and "zrange_waves_per_cu", the grid of the height raster of a box before its LDS limit
  * (profiles/zrange_raster_rate_sweep.log), and "zsum_waves_per_cu", the same of the mean-height raster of a box
- * (profiles/zsum_raster_rate_sweep.log), and "polygon_waves_per_cu", the grid of the box AND polygon count
+ * (profiles/zsum_raster_rate_sweep.log), and "zsum_classes_waves_per_cu", the same of the mean-height raster of a set of classes
+ * (profiles/zsum_classes_rate_sweep.log), and "polygon_waves_per_cu", the grid of the box AND polygon count
  * (profiles/polygon_rate_sweep.log).
  *
  * (Round 2's experimental shapes of the grid collector — option "grid_variant" — left with the kernels they varied:

@@ -1,0 +1,148 @@
+"""k_bounds_zsum_classes_pipe<2> (pcq_scan_dev_zsum_raster_batch_classes) beyond its pipeline's second step, on step-coded data,
+against numpy's count and sum of z per cell on int64.
+
+The plan, the schedule report and the step-coded data are those of tests/_pipeline_plan.py, as in test_gpu_pipeline_depth_zsum.py:
+the same Family (scan_zsum_classes.hip keeps the mean-height raster's launch rule: 4 workgroups per CU at the 64 x 32 cells used
+here), the deep run of seventeen segments sized from the device's compute units (depth 5 at least, both exits out of the steady
+state, both cursors seek, segments jumped over), the shallow run of 4g - 1 steps.  Here the class bytes of points_file travel too,
+class piece k at the plan's byte phase (all sixteen occur): in step s the m(s) planted points carry class classes[s mod 3], the rest
+of the box a class of other_classes, and the points outside the box a class of `classes` — so with the set `classes` exactly the
+planted points pass, m(s) of them in step s with m distinct along any workgroup's steps, and a class byte from the other register
+set, the neighbouring tile or another segment lets a background point through or drops a planted one.  The sets asked: `classes`,
+one class of them (a third of the steps), other_classes (the background alone) and all 256.
+"""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(__file__))
+import _pipeline_plan as pp  # noqa: E402
+from _zsum_classes import in_set  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+pkg = importlib.import_module("adhoc-queries-pointclouds_amd")
+binding = importlib.import_module("adhoc-queries-pointclouds_amd.binding")
+
+NX, NY = 64, 32
+LDS_LIMIT = 160 * 1024 // (16 * NX * NY)
+FAM = pp.Family("K1 zsum classes", min(16, LDS_LIMIT) & ~3, pp.K1.step)  # adhoc-queries-pointclouds_amd/csrc/scan_zsum_classes.hip: ZSUM_CLASSES_WAVES_PER_CU
+EMPTY = ([5, 5, 5], [4, 4, 4])
+assert FAM.waves_per_cu == 4 and NX * NY == 2048
+PRE_CNT = np.asarray([(0, 2**32 - 1, 2**40 + c)[c % 3] for c in range(NX * NY + 16)], dtype=np.int64)
+PRE_SUM = np.asarray([(0, -1, 2**62, -2**62 + c)[c % 4] for c in range(NX * NY + 16)], dtype=np.int64)
+
+
+def widths(k):
+    return 32 + k, 66 + 2 * k  # 64 cells of the one and 32 of the other cover the box's 2001 lattice steps
+
+
+class Run:
+    """Segments (steps, leftover points) in HBM, step-coded; `empty`: the segment whose box is empty."""
+
+    def __init__(self, ctx, cus, seg_steps, seg_rest, phases, empty, seed):
+        self.ctx, self.empty = ctx, empty
+        g = self.g = pp.full_grid(FAM, cus)
+        assert all(r < FAM.step for r in seg_rest)
+        ns = self.ns = [FAM.step * s + r for s, r in zip(seg_steps, seg_rest)]
+        self.report = pp.depth_report(pp.schedule(pp.batch_grid(FAM, cus, sum(seg_steps), len(ns)), sum(seg_steps), seg_steps, ns))
+        poff, psize = pp.carve(ns, [0] * len(ns), 12)
+        coff, csize = pp.carve(ns, phases, 1)
+        self.blocks = [ctx.alloc(psize + 64), ctx.alloc(csize + 64), ctx.alloc(8 * len(PRE_CNT)), ctx.alloc(8 * len(PRE_SUM))]
+        d_pos, d_cls, self.d_cnt, self.d_sum = self.blocks
+        assert d_pos % 16 == 0 and d_cls % 16 == 0 and all(o % 16 == 0 for o in poff)
+        begin = pp.tile_begin(seg_steps)
+        rng = np.random.default_rng(seed)
+        pos_img, cls_img = np.zeros(psize, dtype=np.uint8), np.full(csize + 64, 2, dtype=np.uint8)  # (between the pieces: a class of the set)
+        self.cols, self.q, self.xyz, self.cls = [], [], [], []
+        for k, (steps, rest) in enumerate(zip(seg_steps, seg_rest)):
+            q = pp.PointQueries(10_000 * k)
+            xyz, cls, _ = pp.points_file(rng, g, steps, 0, rest, q, int(begin[k]))
+            pos_img[poff[k]:poff[k] + 12 * ns[k]] = xyz.view(np.uint8).reshape(-1)
+            cls_img[coff[k]:coff[k] + ns[k]] = cls
+            self.cols.append(binding.make_columns(xyz=d_pos + poff[k], cls=d_cls + coff[k], n=ns[k]))
+            self.q.append(q), self.xyz.append(xyz), self.cls.append(cls)
+        self.misalignments = {(d_cls + o) % 4 for o, n in zip(coff, ns) if n >= FAM.step}
+        ctx.to_device(d_pos, pos_img)
+        ctx.to_device(d_cls, cls_img)
+
+    def check(self, classes):
+        """One call with q.box of every live segment, from preset words; numpy's adds over the live segments.  Returns the points
+        per cell and the z sums per cell."""
+        boxes = [EMPTY if k == self.empty else q.box for k, q in enumerate(self.q)]
+        cws = [widths(k) for k in range(len(boxes))]
+        cnt, zsum = PRE_CNT.copy(), PRE_SUM.copy()
+        for k, (lo, hi) in enumerate(boxes):
+            if k != self.empty:
+                p = self.xyz[k][pp.in_box(self.xyz[k], lo, hi) & in_set(self.cls[k], classes)].astype(np.int64)
+                cell = ((p[:, 1] - lo[1]) // cws[k][1]) * NX + (p[:, 0] - lo[0]) // cws[k][0]
+                assert not len(cell) or (0 <= cell.min() and cell.max() < NX * NY)
+                np.add.at(cnt, cell, 1)
+                np.add.at(zsum, cell, p[:, 2])
+        self.ctx.to_device(self.d_cnt, PRE_CNT)
+        self.ctx.to_device(self.d_sum, PRE_SUM)
+        self.ctx.scan_dev_zsum_raster_batch_classes(self.cols, [pkg.Predicate.bounds(lo, hi) for lo, hi in boxes], cws, NX, NY, classes, self.d_cnt,
+                                                    self.d_sum)
+        for name, d, want in (("count", self.d_cnt, cnt), ("sum", self.d_sum, zsum)):
+            got = np.zeros(len(want), dtype=np.int64)
+            self.ctx.to_host(got, d)  # (waits for the context's stream)
+            bad = np.flatnonzero(got != want)
+            assert len(bad) == 0, (f"g={self.g}, set {sorted(classes)[:8]}: {name} (cell, got, want) = "
+                                   f"{[(int(c), int(got[c]), int(want[c])) for c in bad[:12]]} ({len(bad)} words)")
+        return (cnt - PRE_CNT)[:NX * NY], (zsum - PRE_SUM)[:NX * NY]
+
+    def free(self):
+        for p in self.blocks:
+            self.ctx.free(p)
+
+
+@pytest.fixture(scope="module")
+def cus(gpu_ctx):
+    return gpu_ctx.device_info()["compute_units"]
+
+
+@pytest.fixture(scope="module")
+def deep(gpu_ctx, cus):
+    g = pp.full_grid(FAM, cus)
+    plan = pp.batch_plan(g)
+    ns = [pp.point_segment_points(s) for s in plan]
+    steps = [n // FAM.step for n in ns]
+    assert steps == [s.steps for s in plan] and len(plan) == 17
+    r = Run(gpu_ctx, cus, steps, [n % FAM.step for n in ns], [s.phase for s in plan], pp.EMPTY_BOX_SEGMENT, 1831)
+    yield r
+    r.free()
+
+
+def test_deep_plan_reaches_depths_five_and_six_through_both_cursors(deep):
+    rep = deep.report
+    assert sum(n // FAM.step for n in deep.ns) >= pp.deep_steps(deep.g)
+    assert min(rep["depths"]) >= 5 and rep["both_exits_deep"], rep["depths"]
+    assert rep["cross_into_a"] and rep["cross_into_b"] and rep["skips_stepped"] and rep["skips_zero_step"] and rep["skips_empty"], rep
+    assert deep.empty in rep["skipped"] and deep.ns[deep.empty] // FAM.step > 0
+    assert deep.misalignments == {0, 1, 2, 3}  # of the class blocks that have whole steps
+
+
+def test_zsum_classes_deep(deep):
+    q = deep.q[0]
+    live = sum(n for k, n in enumerate(deep.ns) if k != deep.empty)
+    planted = deep.check(q.classes)[0].sum()
+    one = deep.check(q.classes[:1])[0].sum()
+    background = deep.check(q.other_classes)[0].sum()
+    every = deep.check(tuple(range(256)))[0].sum()
+    assert 0 < one < planted < background and planted + background == every and live // 3 < every < live
+
+
+def test_zsum_classes_shallow(gpu_ctx, cus):
+    g = pp.full_grid(FAM, cus)
+    steps = [g + g // 3 + 1, 3, 0]
+    steps[2] = pp.shallow_steps(g) - steps[0] - steps[1]
+    r = Run(gpu_ctx, cus, steps, [277, 77, 53], [1, 2, 3], 1, 1832)
+    try:
+        assert set(r.report["depths"]) == {3, 4} and r.report["cross_into_a"] and r.report["cross_into_b"], r.report
+        q = r.q[0]
+        assert 0 < r.check(q.classes)[0].sum() < r.check(q.other_classes)[0].sum()
+    finally:
+        r.free()
