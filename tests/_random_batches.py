@@ -1,4 +1,4 @@
-"""Seeded random cases for the ten batched entries: a segment set, one query per segment and entry, and numpy's answers.
+"""Seeded random cases for eleven batched entries: a segment set, one query per segment and entry, and numpy's answers.
 
 draw(seed) is a pure function of BASE + PCQ_TEST_SEED_BASE + seed (test_gpu_random.py's soak switch).  Nothing here touches a
 GPU or the library: test_random_batches_plan.py proves on the CPU that the committed seeds satisfy every precondition of every
@@ -22,11 +22,16 @@ What is drawn jointly, per case (include/pcq.h names what every entry accepts; o
              intersect themselves), the hull of box and outline at most 2^31 - 1 wide.
 
 Answers restate include/pcq.h on int64 / f64 host arrays: inclusive integer compares for boxes, IEEE compares for ranges and bins
-(bin = #{edges <= t} - 1), floor division on int64 for cells, np.minimum.at / np.maximum.at for the height raster, and
+(bin = #{edges <= t} - 1), floor division on int64 for cells, np.minimum.at / np.maximum.at for the height raster, np.add.at of 1
+and of z on int64 for the mean-height raster (no sum of CAP i32 values leaves the i64 range), and
 _polygon_rule.inside_exact (Python integers) for the outlines: for every boxed point where that takes at most EXACT_BUDGET
 edge tests per segment, else _polygon_rule.inside (the same rule in int64, exact inside the entry's bound: every product is below
 2^62) with inside_exact on a sample of EXACT_SAMPLE of them.  Every answer is kept per segment ([S, words]): a launch's answer is the sum
 (height raster: the fold) over the segments.
+
+The mean-height raster ("zsum") came after the other ten had committed seeds: everything it draws comes from a generator of its
+own, seeded from (BASE + PCQ_TEST_SEED_BASE + seed, ZSUM_TAG), behind everything else, so that the ten draw what they always drew
+(test_random_batches_plan.py pins a digest of that).
 """
 import functools
 import os
@@ -43,8 +48,10 @@ BASE = 52000
 SEED_BASE = int(os.environ.get("PCQ_TEST_SEED_BASE", "0"))  # a soak run: other seeds than the committed ones
 SEEDS = range(48)
 
-ENTRIES = ("box", "class", "box_class", "box_time", "multi", "class_hist", "time_hist", "raster", "zrange", "polygon")
-COUNTS_WITH_STEPS = ("box", "box_class", "box_time", "multi", "polygon")
+FIRST_TEN = ("box", "class", "box_class", "box_time", "multi", "class_hist", "time_hist", "raster", "zrange", "polygon")
+ENTRIES = FIRST_TEN + ("zsum",)
+COUNTS_WITH_STEPS = ("box", "box_class", "box_time", "multi", "polygon", "zsum")
+ZSUM_TAG = 0x7a73756d  # ("zsum") the second word of the seed of the entry's own generator
 N_LIST = (0, 1, 2, 63, 64, 65, 85, 86, 170, 171, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 1535)
 N_UNIFORM_MAX = 4500
 S_MAX = 24
@@ -57,8 +64,10 @@ CELL_WIDTHS = (1, 2, 3, 7, 641, 2**24)
 I32_MIN, I32_MAX = -2**31, 2**31 - 1
 SPAN_MAX = 2**31 - 1          # include/pcq.h: the polygon entry's exactness bound
 MULTI_BOX_MAX, CLASS_BINS, TIME_BINS_MAX, RASTER_CELLS_MAX, ZRANGE_CELLS_MAX, POLYGON_VERTS_MAX = 8, 256, 1024, 8192, 4096, 256
+ZSUM_CELLS_MAX = 2048
 EXACT_BUDGET, EXACT_SAMPLE = 40000, 96
 RASTER_SHAPES = ((1, 1), (8, 8), (3, 5), (1, 37), (64, 64), (91, 45), (4096, 1), (1, 4096), (2, 2048))
+ZSUM_SHAPES = ((2048, 1), (1, 2048), (64, 32), (3, 5), (1, 1), (8, 8), (1, 37))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -309,10 +318,36 @@ def draw(seed):
     c.zrange = [draw_raster_box(rng, P[k], c.zrange_dims) for k in range(S)]
     c.polygon = [draw_outline(rng, P[k], c.nverts) for k in range(S)]
     answers(c, P, rng)
+    draw_zsum(c, P, np.random.default_rng([BASE + SEED_BASE + seed, ZSUM_TAG]))
     return c
 
 
+def draw_zsum(c, P, rng):
+    """The mean-height raster's shape, boxes, cell widths and answers, from a generator of its own: c.zsum_dims, c.zsum, and
+    c.share["zsum"] = (counts, z sums), each [S, cells] int64; c.mask["zsum"][k]: the counted points of segment k"""
+    if rng.random() < 0.75:
+        nx, ny = ZSUM_SHAPES[int(rng.integers(0, len(ZSUM_SHAPES)))]
+    else:
+        nx = int(rng.integers(1, 200))
+        ny = int(rng.integers(1, max(2, min(200, ZSUM_CELLS_MAX // nx + 1))))
+    assert nx * ny <= ZSUM_CELLS_MAX
+    c.zsum_dims = (nx, ny)
+    c.zsum = [draw_raster_box(rng, P[k], c.zsum_dims) for k in range(c.S)]
+    cnt, zsum = np.zeros((c.S, nx * ny), dtype=np.int64), np.zeros((c.S, nx * ny), dtype=np.int64)
+    c.mask["zsum"] = []
+    for k in range(c.S):
+        lo, hi, cw = c.zsum[k]
+        sel = pp.in_box(P[k], lo, hi)
+        cell = cells_of(P[k], sel, lo, cw, nx, ny)
+        np.add.at(cnt[k], cell, 1)
+        np.add.at(zsum[k], cell, P[k][sel, 2])
+        c.mask["zsum"].append(sel)
+    c.share["zsum"] = (cnt, zsum)
+
+
 def words_of(c, entry):
+    if entry == "zsum":
+        return c.zsum_dims[0] * c.zsum_dims[1]
     return {"multi": c.nq, "class_hist": CLASS_BINS, "time_hist": len(c.edges) - 1, "raster": c.raster_dims[0] * c.raster_dims[1],
             "zrange": c.zrange_dims[0] * c.zrange_dims[1]}.get(entry, 1)
 
@@ -323,7 +358,7 @@ def boxes_of(c, entry, k):
         return []
     if entry == "multi":
         return c.multi[k]
-    if entry in ("raster", "zrange", "polygon"):
+    if entry in ("raster", "zrange", "polygon", "zsum"):
         return [getattr(c, entry)[k][:2]]
     return [c.box[entry][k]]
 
@@ -333,10 +368,10 @@ def answers(c, P, rng):
     INT32_MAX and INT32_MIN where a segment has no point in a cell); c.mask[entry][k]: the counted points of segment k (multi: of
     any box), for the entries of COUNTS_WITH_STEPS; c.passing: the boxed points of the box entry"""
     S = c.S
-    c.share = {e: np.zeros((S, words_of(c, e)), dtype=np.int64) for e in ENTRIES if e != "zrange"}
+    c.share = {e: np.zeros((S, words_of(c, e)), dtype=np.int64) for e in FIRST_TEN if e != "zrange"}
     cells = words_of(c, "zrange")
     zmin, zmax = np.full((S, cells), I32_MAX, dtype=np.int64), np.full((S, cells), I32_MIN, dtype=np.int64)
-    c.mask = {e: [] for e in COUNTS_WITH_STEPS}
+    c.mask = {e: [] for e in COUNTS_WITH_STEPS if e in FIRST_TEN}
     c.passing = []
     nbins = len(c.edges) - 1
     for k in range(S):
@@ -383,6 +418,9 @@ def answer(c, entry):
     if entry == "zrange":
         zmin, zmax = c.share[entry]
         return zmin.min(axis=0), zmax.max(axis=0)
+    if entry == "zsum":
+        cnt, zsum = c.share[entry]
+        return cnt.sum(axis=0), zsum.sum(axis=0)
     return c.share[entry].sum(axis=0)
 
 
@@ -390,6 +428,8 @@ def live(c, entry):
     """Per segment: it gives something to the answer"""
     if entry == "zrange":
         return (c.share[entry][0] != I32_MAX).any(axis=1)
+    if entry == "zsum":
+        return c.share[entry][0].any(axis=1)
     return c.share[entry].any(axis=1)
 
 

@@ -21,6 +21,7 @@ from _batch_all_kinds import KINDS, NAMES, SMALL
 
 pytestmark = pytest.mark.gpu
 
+ROTATION = 3 * len(KINDS)  # calls of the rotation, and a closing one behind them
 FILLER_WORDS, FILLER_ADDS = 1 << 28, 256  # a chain of additions in place over 1 GiB of f32 (2 GiB of traffic each): about ninety milliseconds
 
 
@@ -35,10 +36,18 @@ def test_a_held_launch_on_a_callers_stream_survives_the_next_call(kind):
     began = time.perf_counter()
     first, changed = ak.query(kind, SMALL, 0), ak.query(kind, SMALL, 1)
     ak.check_not_vacuous(first), ak.check_not_vacuous(changed)
-    # what the held launch would add if it read the changed call's table: the first call's launch-level parameters over the
-    # changed predicates.  Every word of it differs from the right answer where the kind has one word per query, some word elsewhere.
+    # what the held launch would add if it read the changed call's table: the first call's launch-level parameters (nqueries,
+    # edges, the raster's shape, the class set, which travels in the kernel's arguments; the polygon count's boxes) over the changed
+    # predicates (the polygon count's outlines).  Every word of it differs from the right answer where the kind has one word per
+    # query, some word elsewhere.
     misread = ak.query(kind, SMALL, first.visit, changed.visit)
     assert misread.words == first.words and (misread.want != first.want).any()
+    if kind in (ak.ZRANGE, ak.ZSUM, ak.ZSUM_CLASSES):
+        assert misread.args[2:] == first.args[2:] and [bytes(p) for p in misread.args[0]] == [bytes(p) for p in changed.args[0]]
+    if kind == ak.ZSUM_CLASSES:  # (the changed call changes the set and the table)
+        assert set(changed.args[4]) != set(first.args[4]) and [bytes(p) for p in changed.args[0]] != [bytes(p) for p in first.args[0]]
+    if kind == ak.POLYGON:
+        assert [bytes(p) for p in misread.args[0]] == [bytes(p) for p in first.args[0]] and misread.args[1] == changed.args[1] != first.args[1]
     if first.words <= 8:
         assert (misread.want != first.want).all(), (misread.want, first.want)
     if kind == ak.MULTI:  # (the rows of the changed call hold the same boxes in the slots the held instantiation reads)
@@ -46,8 +55,10 @@ def test_a_held_launch_on_a_callers_stream_survives_the_next_call(kind):
     A0, A, B, C, D = range(5)
     ctx = ak.pkg.Context(0)
     try:
-        dev = ak.Dev(ctx, 5)
+        dev = ak.Dev(ctx, [first, first, changed, first, changed])
         try:
+            # (a fold hides a wrong z behind a preset beyond it: the misread answer is another one in the held call's region too)
+            assert (ak.expected(misread, dev.before(A)) != ak.expected(first, dev.before(A))).any()
             ts = torch.cuda.Stream()
             with torch.cuda.stream(ts):
                 x = torch.zeros(FILLER_WORDS, device="cuda")
@@ -87,26 +98,26 @@ def test_a_held_launch_on_a_callers_stream_survives_the_next_call(kind):
 
 
 def test_two_callers_streams_and_the_contexts_in_rotation():
-    """24 calls, each kind once on each of two caller's streams and on the context's stream, a stream after another; nothing
+    """36 calls, each kind once on each of two caller's streams and on the context's stream, a stream after another; nothing
     is read or synchronised by the test before the end"""
     import torch
     began = time.perf_counter()
     visits, queries = [0] * len(KINDS), []
-    for call in range(24):
-        kind = (call // 3 + call % 3) % 8
+    for call in range(ROTATION):
+        kind = (call // 3 + call % 3) % len(KINDS)
         queries.append(ak.query(kind, call % 2, visits[kind]))
         visits[kind] += 1
     queries.append(ak.query(ak.BOX, SMALL, visits[ak.BOX]))  # (the last call of a test is on the context's own stream)
-    assert all({queries[c].kind for c in range(r, 24, 3)} == set(KINDS) for r in range(3))
+    assert all({queries[c].kind for c in range(r, ROTATION, 3)} == set(KINDS) for r in range(3))
     for q in queries:
         ak.check_not_vacuous(q)
     ctx = ak.pkg.Context(0)
     try:
-        dev = ak.Dev(ctx, len(queries))
+        dev = ak.Dev(ctx, queries)
         try:
             streams = [torch.cuda.Stream(), torch.cuda.Stream(), None]
             for call, q in enumerate(queries):
-                s = streams[call % 3] if call < 24 else None
+                s = streams[call % 3] if call < ROTATION else None
                 dev.launch(q, call, s.cuda_stream if s is not None else None)
             streams[0].synchronize(), streams[1].synchronize()
             words = dev.regions()
@@ -114,7 +125,7 @@ def test_two_callers_streams_and_the_contexts_in_rotation():
             for call, q in enumerate(queries):
                 bad = dev.wrong(words[call], q, call)
                 if bad is not None:
-                    on = ("the first caller's stream", "the second caller's stream", "the context's stream")[call % 3 if call < 24 else 2]
+                    on = ("the first caller's stream", "the second caller's stream", "the context's stream")[call % 3 if call < ROTATION else 2]
                     failures.append(f"call {call}: kind {NAMES[q.kind]} after kind {NAMES[queries[call - 1].kind] if call else None}, "
                                     f"visit {q.visit}, set {('small', 'large')[q.set]}, on {on}: {bad}")
             assert not failures, f"{len(failures)} of {len(queries)} calls wrong, the first: {failures[0]}"

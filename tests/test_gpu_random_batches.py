@@ -1,12 +1,14 @@
-"""Seeded random parity of the ten batched entries with numpy (_random_batches.py; its seeds are proven on the CPU by
+"""Seeded random parity of eleven batched entries with numpy (_random_batches.py; its seeds are proven on the CPU by
 test_random_batches_plan.py).  PCQ_TEST_SEED_BASE moves the whole seed range for a soak run.
 
-Per seed: the case is uploaded once, all ten entries run through binding.Context on the session's context — consecutive seeds
+Per seed: the case is uploaded once, all the entries run through binding.Context on the session's context — consecutive seeds
 bring unrelated shapes, so the segment table and the partials are reused, outgrown and regrown across them — and every output
 word is compared with numpy's, exactly.  The outputs lie in one device buffer, each between two runs of guard words, all of it
 preset to distinct non-zero words: the counts have to be ADDED to what was there, the height raster FOLDED onto it (its words
 are preset to values among the data's own, to INT32_MAX / INT32_MIN "nothing yet", and to the limits that no z can beat), and
-no guard word may change.  A mismatch names the seed, the entry, the first words with got - want, and the segments whose
+no guard word may change.  The mean-height raster, which joined the ten later (the test keeps its name), adds its counts and its
+z sums into two arrays behind the others' outputs; test_the_mean_height_raster_against_numpy asks for it alone, from a table and
+partials that the previous seed's call left.  A mismatch names the seed, the entry, the first words with got - want, and the segments whose
 shares (numpy's, per segment) make up those words: rerun draw(seed) and cut the case down to them.
 """
 import importlib
@@ -40,8 +42,8 @@ def layout(c):
     """Per output its first u64 word and its length in u64 words (the height raster: two arrays of i32 words, two to a u64 word,
     an odd cell count rounded up: the half word behind it is a guard as well); the buffer's length"""
     at, q = {}, GUARD
-    for name in rb.ENTRIES[:-2] + ("polygon", "zmin", "zmax"):
-        words = (rb.words_of(c, "zrange") + 1) // 2 if name in ("zmin", "zmax") else rb.words_of(c, name)
+    for name in rb.FIRST_TEN[:-2] + ("polygon", "zmin", "zmax", "zcount", "zsum"):
+        words = (rb.words_of(c, "zrange") + 1) // 2 if name in ("zmin", "zmax") else rb.words_of(c, "zsum" if name == "zcount" else name)
         at[name] = (q, words)
         q += words + GUARD
     return at, q
@@ -61,10 +63,14 @@ def preset_words(c, total, at):
     return pre
 
 
-def expected(c, pre, at):
+def expected(c, pre, at, entries=rb.ENTRIES):
     exp = pre.copy()
-    for e in rb.ENTRIES:
-        if e == "zrange":
+    for e in entries:
+        if e == "zsum":  # (modulo 2^64: the presets are large)
+            for name, words in zip(("zcount", "zsum"), rb.answer(c, e)):
+                first, n = at[name]
+                exp[first:first + n] += words.view(np.uint64)
+        elif e == "zrange":
             zmin, zmax = rb.answer(c, e)
             cells = len(zmin)
             w32 = exp.view(np.int32)
@@ -77,7 +83,7 @@ def expected(c, pre, at):
     return exp
 
 
-def launch_all(ctx, c, base, d_out, at, stream=None):
+def launch_all(ctx, c, base, d_out, at, stream=None, entries=rb.ENTRIES):
     d_pos, d_cls, d_t = base
     S = c.S
     pos = [d_pos + c.poff[k] for k in range(S)]
@@ -93,6 +99,10 @@ def launch_all(ctx, c, base, d_out, at, stream=None):
     def bounds(rows):
         return [P.bounds(r[0], r[1]) for r in rows]
 
+    if "zsum" in entries and len(entries) == 1:
+        ctx.scan_dev_zsum_raster_batch(plain, bounds(c.zsum), [r[2] for r in c.zsum], *c.zsum_dims, out["zcount"], out["zsum"], stream=stream)
+        return
+    assert tuple(entries) == rb.ENTRIES
     ctx.scan_dev_count_batch(plain, bounds(c.box["box"]), out["box"], stream=stream)
     ctx.scan_dev_count_batch(only_class, [P.classification(v) for v in c.cclass], out["class"], stream=stream)
     ctx.scan_dev_count_batch_combined(with_class, [P.bounds_class(lo, hi, v) for (lo, hi), v in zip(c.box["box_class"], c.qclass)],
@@ -106,9 +116,12 @@ def launch_all(ctx, c, base, d_out, at, stream=None):
     ctx.scan_dev_zrange_raster_batch(plain, bounds(c.zrange), [r[2] for r in c.zrange], *c.zrange_dims, out["zmin"], out["zmax"],
                                      stream=stream)
     ctx.scan_dev_count_batch_polygon(plain, bounds(c.polygon), [r[2] for r in c.polygon], out["polygon"], stream=stream)
+    ctx.scan_dev_zsum_raster_batch(plain, bounds(c.zsum), [r[2] for r in c.zsum], *c.zsum_dims, out["zcount"], out["zsum"], stream=stream)
 
 
 def contributors(c, entry, word):
+    if entry == "zsum":
+        return np.flatnonzero(c.share[entry][0][:, word]).tolist()
     if entry == "zrange":
         zmin, zmax = c.share[entry]
         return np.flatnonzero(zmin[:, word] != I32_MAX).tolist()
@@ -120,6 +133,16 @@ def describe(c, got, exp, at):
     out = []
     covered = np.zeros(len(exp), dtype=bool)
     for e in rb.ENTRIES:
+        if e == "zsum":
+            for name in ("zcount", "zsum"):
+                first, words = at[name]
+                covered[first:first + words] = True
+                g, w = got[first:first + words].view(np.int64), exp[first:first + words].view(np.int64)
+                bad = np.flatnonzero(g != w)
+                if len(bad):
+                    out.append(f"zsum {name}: {len(bad)} of {words} words wrong, (word, got - want, segments) "
+                               f"{[(int(b), int(g[b]) - int(w[b]), contributors(c, e, b)) for b in bad[:4]]}")
+            continue
         if e == "zrange":
             cells = rb.words_of(c, e)
             for name in ("zmin", "zmax"):
@@ -150,11 +173,11 @@ def describe(c, got, exp, at):
     return out
 
 
-def run_case(ctx, seed, stream=None, sync=None):
+def run_case(ctx, seed, stream=None, sync=None, entries=rb.ENTRIES):
     c = rb.case(seed)
     at, total = layout(c)
     pre = preset_words(c, total, at)
-    exp = expected(c, pre, at)
+    exp = expected(c, pre, at, entries)
     blocks = [ctx.alloc(size + 64) for size in (c.psize, c.csize, c.tsize, 8 * total)]
     try:
         assert all(b % 16 == 0 for b in blocks)
@@ -162,7 +185,7 @@ def run_case(ctx, seed, stream=None, sync=None):
         ctx.to_device(blocks[1], image(c.csize, c.coff, c.cls, 1))
         ctx.to_device(blocks[2], image(c.tsize, c.toff, c.t, 8))
         ctx.to_device(blocks[3], pre)
-        launch_all(ctx, c, blocks[:3], blocks[3], at, stream)
+        launch_all(ctx, c, blocks[:3], blocks[3], at, stream, entries)
         if sync is not None:
             sync()
         got = np.zeros(total, dtype=np.uint64)
@@ -179,6 +202,13 @@ def run_case(ctx, seed, stream=None, sync=None):
 @pytest.mark.parametrize("seed", rb.SEEDS)
 def test_all_ten_entries_against_numpy(gpu_ctx, seed):
     run_case(gpu_ctx, seed)
+
+
+@pytest.mark.parametrize("seed", rb.SEEDS)
+@pytest.mark.parametrize("entry", ["zsum"])
+def test_the_mean_height_raster_against_numpy(gpu_ctx, entry, seed):
+    """The entry that joined later, alone: counts and z sums as int64 bit patterns, every other word of the buffer as it was"""
+    run_case(gpu_ctx, seed, entries=(entry,))
 
 
 def test_on_a_callers_stream(gpu_ctx):

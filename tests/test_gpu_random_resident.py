@@ -2,10 +2,11 @@
 the CPU by test_random_batches_plan.py).  PCQ_TEST_SEED_BASE moves the whole seed range for a soak run.
 
 Per seed: 2 .. 6 LAST files are written and loaded with their time blocks (pcq_query_resident_load_with), and each of the ten
-count entries of include/pcq_query.h is asked once with a world-space query drawn around the files' own points.  Every call
+count entries of include/pcq_query.h and the two mean-height rasters of pcq_query_stats.h and pcq_query_classes.h is asked once with a world-space query drawn around the files' own points.  Every call
 has to return 0 (the generator draws only what the entries accept) and every output word has to be numpy's: the matches, the
 histograms, every raster cell — both rasters have more cells than one launch holds, in some seeds rows longer than a launch —
-the world z of the height raster bit for bit with NaN where no point lies, and points_scanned / points_read.
+the world z of the height raster bit for bit with NaN where no point lies, the mean-height rasters' counts as integers and their
+means as f64 bit patterns (NaN is an answer), and points_scanned / points_read.
 """
 import ctypes as C
 import importlib
@@ -86,10 +87,21 @@ def ask(q, r, entry, qu):
         rc = lib.pcq_query_resident_bounds_zrange_raster(r, d3(qu.bmin), qu.zmax, qu.cell, qu.nx, qu.ny, zlo.ctypes.data_as(dd), zhi.ctypes.data_as(dd),
                                                          C.byref(s))
         out["zlo"], out["zhi"] = zlo, zhi
+    elif entry in ("zmean", "zmean_classes"):
+        count, pc = u64s(qu.nx * qu.ny)
+        zmean = np.full(qu.nx * qu.ny, -0.25)
+        pm = zmean.ctypes.data_as(C.POINTER(C.c_double))
+        if entry == "zmean":
+            rc = lib.pcq_query_resident_bounds_zmean_raster(r, d3(qu.bmin), qu.zmax, qu.cell, qu.nx, qu.ny, pc, pm, C.byref(s))
+        else:
+            words = [sum(1 << (v % 32) for v in qu.classes if v // 32 == w) for w in range(8)]
+            rc = lib.pcq_query_resident_bounds_zmean_raster_classes(r, d3(qu.bmin), qu.zmax, qu.cell, qu.nx, qu.ny, (C.c_uint32 * 8)(*words), pc, pm,
+                                                                    C.byref(s))
+        out["count"], out["zmean"] = count.astype(np.int64), zmean
     else:
         flat = [float(v) for p in qu.xy for v in p]
         rc = lib.pcq_query_resident_count_polygon(r, len(qu.xy), (C.c_double * len(flat))(*flat), qu.zmin, qu.zmax, C.byref(m), C.byref(s))
-    if "hist" not in out and "raster" not in out and "zlo" not in out:
+    if "hist" not in out and "raster" not in out and "zlo" not in out and "count" not in out:
         out["matches"] = m.value
     out["scanned"] = s.value
     return rc, out
@@ -110,9 +122,41 @@ def differences(got, want):
     return bad
 
 
+def load(q, tmp_path, c):
+    paths = []
+    for k, f in enumerate(c.files):
+        p = str(tmp_path / f"s{c.seed}_f{k}_{f.fmt}_{f.n}.last")
+        rr.image(f).tofile(p)
+        paths.append(p)
+    arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+    r = C.c_void_p()
+    assert q.lib.pcq_query_resident_load_with(0, arr, len(paths), PCQ_RESIDENT_TIME, C.byref(r)) == 0, q.err()
+    return r
+
+
+@pytest.mark.parametrize("seed", rr.SEEDS)
+@pytest.mark.parametrize("entry", ["zmean", "zmean_classes"])
+def test_the_mean_height_rasters_against_numpy(q, tmp_path, entry, seed):
+    """The two entries that joined later, each alone on a freshly loaded dataset and asked twice: the second call meets the first
+    call's tables and partials, and has to give the same words"""
+    c = rr.case(seed)
+    r = load(q, tmp_path, c)
+    wrong = []
+    try:
+        for visit in range(2):
+            rc, got = ask(q, r, entry, c.q[entry])
+            assert rc == 0, f"seed {seed}, {entry}: refused with {rc}: {q.err()}"
+            wrong += [f"{entry}, call {visit}: {d}" for d in differences(got, c.answer[entry])]
+    finally:
+        q.lib.pcq_query_resident_free(r)
+    what = [(f.fmt, f.n, f.scale, f.offset, "lying" if f.lying else "") for f in c.files]
+    assert not wrong, (f"seed {seed} (PCQ_TEST_SEED_BASE {rr.SEED_BASE}), files (format, n, scale, offset) {what}, classes "
+                       f"{getattr(c.q[entry], 'classes', None)}: " + "; ".join(wrong))
+
+
 @pytest.mark.parametrize("seed", rr.SEEDS)
 def test_every_count_entry_against_numpy(q, tmp_path, seed):
-    c = rr.draw(seed)
+    c = rr.case(seed)
     paths = []
     for k, f in enumerate(c.files):
         p = str(tmp_path / f"s{seed}_f{k}_{f.fmt}_{f.n}.last")

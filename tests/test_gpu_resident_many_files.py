@@ -262,6 +262,49 @@ def test_height_raster(q, dataset):
     assert np.array_equal(zlo.view(np.uint64), lo.view(np.uint64)) and np.array_equal(zhi.view(np.uint64), hi.view(np.uint64))
 
 
+def mean_height(q, r, held, classes):
+    """The mean-height raster of RASTER (classes None: the unfiltered entry) against the header comment's definition, restated for one
+    z lattice (every file shares its z scale and offset, so there is one group and one batch): per cell cnt and the i64 sum of the
+    stored z over all files, W = offset * (double)cnt + scale * (double)sum with both products rounded before the add, W / N."""
+    bmin, zmax, cell, nx, ny = RASTER
+    count, mean = np.full(nx * ny, 77, dtype=np.uint64), np.full(nx * ny, -77.25)
+    s = C.c_uint64(7)
+    out = (count.ctypes.data_as(C.POINTER(C.c_uint64)), mean.ctypes.data_as(C.POINTER(C.c_double)), C.byref(s))
+    if classes is None:
+        rc = q.lib.pcq_query_resident_bounds_zmean_raster(r, d3(bmin), zmax, cell, nx, ny, *out)
+    else:
+        words = [sum(1 << (c % 32) for c in classes if c // 32 == w) for w in range(8)]
+        rc = q.lib.pcq_query_resident_bounds_zmean_raster_classes(r, d3(bmin), zmax, cell, nx, ny, (C.c_uint32 * 8)(*words), *out)
+    assert rc == 0, q.err()
+    sel, cells = raster_cells(held)
+    keep = np.ones(len(cells), dtype=bool) if classes is None else np.isin(held.cls[sel], list(classes))
+    cnt = np.bincount(cells[keep], minlength=nx * ny).astype(np.int64)
+    zsum = np.zeros(nx * ny, dtype=np.int64)
+    np.add.at(zsum, cells[keep], held.xyz[sel, 2][keep].astype(np.int64))
+    a = np.float64(Z_OFFSET) * cnt.astype(np.float64)   # (each product an array of rounded f64 before the add: numpy fuses nothing)
+    b = np.float64(SCALES[0][2]) * zsum.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        want = np.where(cnt > 0, (a + b) / cnt.astype(np.float64), np.nan)
+    assert s.value == len(held.xyz) and np.array_equal(count.astype(np.int64), cnt) and cnt.min() > 0
+    assert np.array_equal(mean.view(np.uint64), want.view(np.uint64))
+    assert (held.xyz[sel, 2][keep] < 0).any() and (held.xyz[sel, 2][keep] > 0).any()  # (a z that lost its sign is another mean)
+    return cnt
+
+
+def test_mean_height_raster(q, dataset):
+    r, held = dataset
+    cnt = mean_height(q, r, held, None)
+    assert np.array_equal(cnt, np.bincount(raster_cells(held)[1], minlength=len(cnt)))  # (the density raster's counts)
+
+
+def test_mean_height_raster_classes(q, dataset):
+    """The set {2, 6} of the files' classes 1, 2 and 6: every cell keeps some of its points and loses some"""
+    r, held = dataset
+    cnt = mean_height(q, r, held, (CLASS, 6))
+    every = np.bincount(raster_cells(held)[1], minlength=len(cnt))
+    assert (cnt < every).all()
+
+
 def test_polygon(q, dataset):
     r, held = dataset
     xy, zmin, zmax = OUTLINE

@@ -4,6 +4,7 @@ refusal on the GPU is then a failure, not a skipped seed — and the seed ranges
 generator that loses one fails here.
 """
 import functools
+import hashlib
 
 import numpy as np
 import pytest
@@ -13,9 +14,60 @@ import _random_resident as rr
 from _random_batches import I32_MAX, I32_MIN
 
 
+# What the first ten entries of each module drew at commit c1949bf ("Ground-only mean-height raster: a class set in the z-sum raster
+# pass"), the last one before the mean-height entries joined them: SHA-256 over every seed's data, queries and answers
+# (batches_digest, resident_digest), computed there with these two functions.  The later entries draw from generators of their own.
+BATCHES_DIGEST_AT_C1949BF = "ca415a8ab0ae9fdf23a5e3e7765e5e0d878217b1999cffae0fdd6c9dae32da37"
+RESIDENT_DIGEST_AT_C1949BF = "0c829a68dbc6e09a800276862e4c2bb039a443d5d098f66bdf5473de95aef589"
+BATCHES_TEN = ("box", "class", "box_class", "box_time", "multi", "class_hist", "time_hist", "raster", "zrange", "polygon")
+RESIDENT_TEN = ("bounds", "class", "bounds_class", "bounds_time", "many", "by_class", "by_time", "raster", "zrange", "polygon")
+
+
+def _put(h, *things):
+    """Arrays as their dtype, shape and bytes; everything else (integers, floats, strings, nested lists of them) as its repr"""
+    for x in things:
+        if isinstance(x, np.ndarray):
+            h.update(repr((x.dtype.str, x.shape)).encode() + np.ascontiguousarray(x).tobytes())
+        elif isinstance(x, (list, tuple)) and any(isinstance(v, np.ndarray) for v in x):
+            _put(h, len(x), *x)
+        else:
+            h.update(repr(x).encode())
+
+
+def batches_digest(cs):
+    h = hashlib.sha256()
+    for c in cs:
+        _put(h, c.seed + rb.SEED_BASE, c.n, c.S, c.cphase, c.tphase, c.poff, c.psize, c.coff, c.csize, c.toff, c.tsize, c.dist, c.xyz, c.class_values, c.cls,
+             c.edges, c.nq, c.raster_dims, c.zrange_dims, c.nverts, c.t, c.ranges, c.qclass, c.cclass, sorted(c.box.items()), c.multi, c.raster,
+             c.zrange, c.polygon, c.passing)
+        for e in BATCHES_TEN:
+            _put(h, e, c.share[e], c.mask.get(e, ()))
+    return h.hexdigest()
+
+
+def resident_digest(cs):
+    h = hashlib.sha256()
+    for c in cs:
+        _put(h, c.seed + rr.SEED_BASE, len(c.files))
+        for f in c.files:
+            _put(h, f.fmt, f.n, f.scale, f.offset, f.xyz, f.cls, f.t, f.world, f.hmin, f.hmax, f.hidden, f.lying)
+        for e in RESIDENT_TEN:
+            _put(h, e, sorted((k, v) for k, v in vars(c.q[e]).items() if not isinstance(v, np.ndarray)),
+                 [v for k, v in sorted(vars(c.q[e]).items()) if isinstance(v, np.ndarray)])
+            _put(h, [k for k, v in sorted(c.answer[e].items())], [np.asarray(v) for k, v in sorted(c.answer[e].items())])
+        _put(h, [e for e in c.lie_decides if e in RESIDENT_TEN])
+    return h.hexdigest()
+
+
 @functools.lru_cache(maxsize=None)
 def cases():
     return [rb.draw(seed) for seed in rb.SEEDS]
+
+
+def test_the_first_ten_entries_draw_what_they_drew_before_the_mean_height_raster():
+    """(the committed seeds, also in a soak run, which moves every other test to other seeds)"""
+    cs = cases() if rb.SEED_BASE == 0 else [rb.draw(seed - rb.SEED_BASE) for seed in rb.SEEDS]
+    assert batches_digest(cs) == BATCHES_DIGEST_AT_C1949BF
 
 
 def test_a_draw_is_a_function_of_its_seed():
@@ -62,6 +114,7 @@ def test_every_precondition_of_every_entry(seed):
     assert 1 <= len(e) - 1 <= rb.TIME_BINS_MAX and not np.isnan(e).any() and np.all(e[:-1] <= e[1:])
     check_raster(c.raster, c.raster_dims, rb.RASTER_CELLS_MAX)
     check_raster(c.zrange, c.zrange_dims, rb.ZRANGE_CELLS_MAX)
+    check_raster(c.zsum, c.zsum_dims, rb.ZSUM_CELLS_MAX)
     assert 3 <= c.nverts <= rb.POLYGON_VERTS_MAX
     for lo, hi, verts in c.polygon:
         assert len(verts) == c.nverts and all(I32_MIN <= v <= I32_MAX for xy in verts for v in xy)
@@ -112,9 +165,12 @@ def test_the_planted_times_decide_answers():
 def test_the_answers_are_worth_asking_for(entry):
     cs = cases()
     zero = sum(not rb.live(c, entry).any() for c in cs)
-    assert 10 * zero <= len(cs), f"{zero} of {len(cs)} cases leave the answer untouched"
+    cap = 10 if entry in rb.FIRST_TEN else 4  # (an entry that joined later: at most a quarter of its seeds)
+    assert cap * zero <= len(cs), f"{zero} of {len(cs)} cases leave the answer untouched"
     if entry == "zrange":
         more = sum(int((c.share[entry][0] != I32_MAX).sum()) > 1 for c in cs)
+    elif entry == "zsum":
+        more = sum(int(rb.answer(c, entry)[0].sum()) > 1 for c in cs)
     else:
         more = sum(int(rb.answer(c, entry).sum()) > 1 for c in cs)
     assert 2 * more >= len(cs), f"only {more} of {len(cs)} cases have more than a single match"
@@ -138,12 +194,41 @@ def test_matches_from_whole_steps_and_from_leftovers(entry):
     assert both >= 1
 
 
+def test_the_mean_height_raster_reaches_what_it_is_for():
+    """The entry that joined later, over its 48 seeds: the shapes at the limit and the small ones, sums of both signs and beyond 32
+    bits (the "wide" positions plant INT32_MIN / INT32_MAX on z), a cell that a whole wave adds into, matches from whole steps and
+    from leftovers, and at most a quarter of the seeds with nothing to add"""
+    cs = cases()
+    shapes = {c.zsum_dims for c in cs}
+    assert {(2048, 1), (1, 2048), (64, 32), (3, 5), (1, 1)} <= shapes and any(d not in rb.ZSUM_SHAPES for d in shapes)
+    assert any(any(w not in rb.CELL_WIDTHS for _, _, cw in c.zsum for w in cw) for c in cs)
+    negative = wide = crowded = both = zero = 0
+    for c in cs:
+        cnt, zsum = rb.answer(c, "zsum")
+        assert cnt.dtype == zsum.dtype == np.int64 and not zsum[cnt == 0].any()
+        assert abs(int(np.abs(c.share["zsum"][1]).sum())) < 2**62  # (numpy's int64 is the exact value)
+        zero += not cnt.any()
+        negative += bool((zsum[cnt > 0] < 0).any())
+        wide += bool((np.abs(zsum) > 2**32).any())
+        crowded += bool((cnt >= 64).any())
+        tiles = sum(int(m[:c.n[k] // rb.K1_STEP * rb.K1_STEP].sum()) for k, m in enumerate(c.mask["zsum"]))
+        left = sum(int(m[c.n[k] // rb.K1_STEP * rb.K1_STEP:].sum()) for k, m in enumerate(c.mask["zsum"]))
+        both += tiles > 0 and left > 0
+    assert 4 * zero <= len(cs), f"{zero} of {len(cs)} seeds add nothing"
+    assert negative >= 1 and wide >= 1 and crowded >= 1 and both >= 1, (negative, wide, crowded, both)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the twin for the resident queries (_random_resident.py)
 # ---------------------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def resident_cases():
-    return [rr.draw(seed) for seed in rr.SEEDS]
+    return [rr.case(seed) for seed in rr.SEEDS]
+
+
+def test_resident_first_ten_entries_draw_what_they_drew_before_the_mean_height_rasters():
+    cs = resident_cases() if rr.SEED_BASE == 0 else [rr.draw(seed - rr.SEED_BASE) for seed in rr.SEEDS]
+    assert resident_digest(cs) == RESIDENT_DIGEST_AT_C1949BF
 
 
 @pytest.mark.parametrize("seed", rr.SEEDS)
@@ -159,11 +244,14 @@ def test_resident_no_call_is_refused(seed):
     for e in rr.ENTRIES:
         assert rr.refusal(c.files, e, c.q[e]) is None, e
     assert 1 <= len(c.q["many"].bmin) <= 20 and 3 <= len(c.q["polygon"].xy) <= rr.POLYGON_VERTS_MAX
-    for e, limit in (("raster", rr.RASTER_CELLS_MAX), ("zrange", rr.ZRANGE_CELLS_MAX)):  # more cells than a launch holds
+    assert all(0 <= v < 256 for v in c.q["zmean_classes"].classes) and len(set(c.q["zmean_classes"].classes)) == len(c.q["zmean_classes"].classes)
+    for e, limit in (("raster", rr.RASTER_CELLS_MAX), ("zrange", rr.ZRANGE_CELLS_MAX), ("zmean", rr.ZSUM_CELLS_MAX),
+                     ("zmean_classes", rr.ZSUM_CELLS_MAX)):  # more cells than a launch holds
         assert limit < c.q[e].nx * c.q[e].ny <= rr.QUERY_RASTER_CELLS_MAX
         for f, lmin, lmax in rr.survivors(c.files, *rr.raster_world_box(c.q[e])):  # a whole multiple of every surviving file's steps
             assert all(rr.steps_of(c.q[e].cell, f.scale[a]) is not None for a in range(2))
             assert all(I32_MIN <= lmin[a] <= I32_MAX for a in range(2))
+            assert np.isfinite(f.scale[2]) and f.scale[2] > 0 and f.n < 2**32
 
 
 def test_resident_seeds_reach_what_they_are_for():
@@ -185,4 +273,43 @@ def test_resident_seeds_reach_what_they_are_for():
 def test_resident_answers_are_worth_asking_for(entry):
     cs = resident_cases()
     zero = sum(rr.total(c.answer[entry]) == 0 for c in cs)
-    assert 10 * zero <= len(cs), f"{zero} of {len(cs)} cases leave the answer empty"
+    cap = 10 if entry in rr.FIRST_TEN else 4  # (the later entries: at most a quarter — the empty class set is drawn on purpose)
+    assert cap * zero <= len(cs), f"{zero} of {len(cs)} cases leave the answer empty"
+
+
+@pytest.mark.parametrize("entry", ["zmean", "zmean_classes"])
+def test_resident_mean_height_seeds_reach_what_they_are_for(entry):
+    """Some seed merges at least three z lattices, some seed has a cell that two groups reach (there the order of the merge and the
+    rounding of the two products decide the bits), some seed a NaN cell next to a reached one; rows longer than a launch occur; with
+    a class set: every kind of set occurs, and some set removes some but not all points of a reached cell"""
+    cs = resident_cases()
+    lattices = shared = nan_beside = long_rows = partly = reordered = fused = 0
+    for c in cs:
+        qu = c.q[entry]
+        classes = qu.classes if entry == "zmean_classes" else None
+        count, zmean, scanned, per_group = rr.zmean_answer(c.files, qu, classes)
+        # two mutants of the merge, exact in rationals: the groups in the reverse order, and scale * sum contracted into the add
+        # (one rounding of scale * sum + a instead of two; offset * cnt is exact for these offsets, so the other contraction is none)
+        groups, _ = rr.zmean_groups(c.files, qu, classes)
+        order, contracted = rr.zmean_mutants(groups, len(count))
+        reordered += order > 0
+        fused += contracted > 0
+        assert np.array_equal(np.isnan(zmean), count == 0) and np.array_equal(count, c.answer[entry]["count"])
+        assert np.array_equal(zmean.view(np.uint64), c.answer[entry]["zmean"].view(np.uint64))
+        lattices += len(per_group) >= 3
+        shared += bool(len(per_group) >= 2 and (np.sum([g > 0 for g in per_group], axis=0) >= 2).any())
+        grid = (count > 0).reshape(qu.ny, qu.nx)
+        nan_beside += bool((grid[:, 1:] != grid[:, :-1]).any() or (grid[1:] != grid[:-1]).any())
+        long_rows += qu.nx > rr.ZSUM_CELLS_MAX
+        if classes is not None:
+            every = rr.zmean_answer(c.files, qu, None)[0]
+            partly += bool(((count > 0) & (count < every)).any())
+            assert (count <= every).all() and (len(classes) < 256 or np.array_equal(count, every)) and (len(classes) or not count.any())
+    assert lattices >= 1 and shared >= 1 and nan_beside >= 1 and long_rows >= 1, (lattices, shared, nan_beside, long_rows)
+    # (the class-filtered entry runs the same merge; its sets leave fewer lattices in a cell, and no committed seed of its own
+    # has a mean that the order decides)
+    assert fused >= 2 and (reordered >= 2 or entry == "zmean_classes"), \
+        f"the merge's order decides a mean in {reordered} seeds, the rounding of scale * sum in {fused}"
+    if entry == "zmean_classes":
+        assert partly >= 1
+        assert {c.q[entry].kind for c in cs} == set(rr.SET_KINDS)
