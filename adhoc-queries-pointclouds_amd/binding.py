@@ -217,6 +217,8 @@ def load_library() -> C.CDLL:
         "pcq_scan_dev_zsum_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
         "pcq_scan_dev_zsum_raster_batch_classes": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
                                                              P(C.c_uint32), vp, vp, vp]),
+        "pcq_scan_dev_zmoments_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                                         vp, vp, vp, vp, vp]),
         "pcq_scan_dev_count_batch_polygon": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_int32), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
@@ -554,6 +556,21 @@ class Context:
         sa = None if classes is None else (C.c_uint32 * 8)(*class_set_words(classes))
         _check(self.lib.pcq_scan_dev_zsum_raster_batch_classes(self.handle, ca, pa, wa, n, nx, ny, sa, C.c_void_p(d_count),
                                                                C.c_void_p(d_zsum), C.c_void_p(stream)))
+
+    def scan_dev_zmoments_raster_batch(self, cols: Sequence[Columns], preds: Sequence[Predicate], cells, nx: int, ny: int, d_count: int,
+                                       d_zsum: int, d_zsq_lo: int, d_zsq_hi: int, stream: Optional[int] = None) -> None:
+        """The height-spread raster of a box (segments, predicates and cells as for scan_dev_raster_batch; at most
+        PCQ_ZMOMENTS_CELLS_MAX cells) in ONE pass: for every point (X, Y, Z) inside its segment's box, into the word of its cell of
+        each of four arrays of nx * ny words, += 1 (d_count), += Z (d_zsum, i64), += (Z * Z) & 0xffffffff (d_zsq_lo) and
+        += (Z * Z) >> 32 (d_zsq_hi), all modulo 2^64."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        flat = [int(w) for c in cells for w in c]
+        assert len(flat) == 2 * n, "one (x, y) pair of cell widths per segment"
+        wa = (C.c_uint32 * max(len(flat), 1))(*flat)
+        _check(self.lib.pcq_scan_dev_zmoments_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_count), C.c_void_p(d_zsum),
+                                                           C.c_void_p(d_zsq_lo), C.c_void_p(d_zsq_hi), C.c_void_p(stream)))
 
     def scan_dev_count_batch_polygon(self, cols: Sequence[Columns], preds: Sequence[Predicate], verts, d_total: int,
                                      stream: Optional[int] = None) -> None:

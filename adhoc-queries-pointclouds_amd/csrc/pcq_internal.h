@@ -149,7 +149,7 @@ constexpr int PCQ_SEGMENTS_CLASS_HIST = 0x4348;  // ("CH") no pcq_predicate_kind
 // count and edges behind them, under a kind of its own: the same segments under PCQ_PRED_BOUNDS_TIME are another entry's table.
 constexpr int PCQ_SEGMENTS_TIME_HIST = 0x5448;  // ("TH") no pcq_predicate_kind
 
-// One segment of a density raster launch (scan_raster.hip) or a height or mean-height raster launch (scan_zrange.hip, scan_zsum.hip: the
+// One segment of a density raster launch (scan_raster.hip) or a height, mean-height or height-spread raster launch (scan_zrange.hip, scan_zsum.hip, scan_zmoments.hip: the
 // same table under the same kind, since the kernels read every field alike): DevSegment with the segment's cell widths in lattice units and the
 // magics of the division by them (raster_div.h).  At its own pitch in the same buffers, under a kind of its own: the widths are
 // part of the bytes the upload compares.
@@ -387,6 +387,7 @@ struct pcq_ctx {
     int zrange_waves_per_cu = 0;  // height raster (scan_zrange.hip): workgroups per CU before the LDS limit (0 = the product's: ZRANGE_WAVES_PER_CU)
     int zsum_waves_per_cu = 0;    // mean-height raster (scan_zsum.hip): workgroups per CU before the LDS limit (0 = the product's: ZSUM_WAVES_PER_CU)
     int zsum_classes_waves_per_cu = 0;  // class-filtered mean-height raster (scan_zsum_classes.hip): the same (0 = the product's: ZSUM_CLASSES_WAVES_PER_CU)
+    int zmoments_waves_per_cu = 0;  // height-spread raster (scan_zmoments.hip): the same (0 = the product's: ZMOMENTS_WAVES_PER_CU)
     int polygon_waves_per_cu = 0; // box AND polygon count (scan_polygon.hip): workgroups per CU (0 = the product's: POLYGON_WAVES_PER_CU)
     int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif
@@ -458,6 +459,10 @@ int pcq_launch_finish_zrange(pcq_ctx *ctx, int ncells, int nblocks, int32_t *d_z
 // scan_count_multi.hip: the finish of the mean-height raster, k_finish_counts on s twice — slice c (nblocks words) of the context's
 // partials += into d_count[c], slice ncells + c += into d_zsum[c], both modulo 2^64
 int pcq_launch_finish_zsum(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_count, int64_t *d_zsum, hipStream_t s);
+// scan_count_multi.hip: the finish of the height-spread raster, k_finish_counts on s four times — slices a * ncells + c (a = 0 .. 3) of
+// the context's partials += into d_count[c], d_zsum[c], d_zsq_lo[c], d_zsq_hi[c], all modulo 2^64
+int pcq_launch_finish_zmoments(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_count, int64_t *d_zsum, uint64_t *d_zsq_lo, uint64_t *d_zsq_hi,
+                               hipStream_t s);
 // scan_time.hip: K3 over a packed, 8-byte aligned f64 time column (+= into *d_count)
 int pcq_launch_time_count_f64(pcq_ctx *ctx, const void *d_t, uint64_t n, const DevPred &pred, uint64_t *d_count, hipStream_t s);
 // scan_generic.hip

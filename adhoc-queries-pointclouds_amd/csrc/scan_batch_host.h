@@ -1,5 +1,5 @@
 // scan_batch_host.h — the host side of the K1-family batched launches (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip,
-// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_zsum.hip, scan_polygon.hip): host code only; the kernels and their constants are in scan_tiles.h.
+// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_zsum.hip, scan_zsum_classes.hip, scan_zmoments.hip, scan_polygon.hip): host code only; the kernels and their constants are in scan_tiles.h.
 #pragma once
 
 #include <vector>
@@ -16,7 +16,7 @@ namespace {
 // predicates, or their refusal); xyz, n and tile_begin are filled here.  launch(workgroups, steps) enqueues the kernel, or refuses.
 // A trailer (the time histogram's edges, the polygon count's outlines) travels behind the table in the same upload, under the same compare of all bytes.
 // finish(workgroups) enqueues the fold of the partials into the caller's words: pcq_launch_finish_counts (`folded` slices added into
-// d_out) for every count; the height and mean-height rasters bring their own (pcq_launch_finish_zrange, _zsum).
+// d_out) for every count; the height, mean-height and height-spread rasters bring their own (pcq_launch_finish_zrange, _zsum, _zmoments).
 struct K1Batch {
     const char *prefix;  // of a refusal's text
     int table_kind;      // the key of the table in HBM (pcq_upload_segment_table)

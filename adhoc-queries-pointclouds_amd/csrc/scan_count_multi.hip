@@ -253,6 +253,18 @@ int pcq_launch_finish_zsum(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_co
     return PCQ_OK;
 }
 
+// The finish of the height-spread raster (scan_zmoments.hip): k_finish_counts once per array, over the four quarters of the partials
+// in the kernel's order — counts, sums, the low and the high words of the squares — each += into its array modulo 2^64.
+int pcq_launch_finish_zmoments(pcq_ctx *ctx, int ncells, int nblocks, uint64_t *d_count, int64_t *d_zsum, uint64_t *d_zsq_lo, uint64_t *d_zsq_hi,
+                               hipStream_t s) {
+    const uint64_t quarter = (uint64_t)ncells * (uint64_t)nblocks;
+    uint64_t *const out[4] = {d_count, reinterpret_cast<uint64_t *>(d_zsum), d_zsq_lo, d_zsq_hi};
+    for (int a = 0; a < 4; a++)
+        hipLaunchKernelGGL(k_finish_counts, dim3((unsigned)ncells), dim3(BLOCK), 0, s, ctx->d_partials + a * quarter, nblocks, out[a]);
+    PCQ_HIP(hipGetLastError());
+    return PCQ_OK;
+}
+
 int pcq_launch_finish_zrange(pcq_ctx *ctx, int ncells, int nblocks, int32_t *d_zmin, int32_t *d_zmax, hipStream_t s) {
     hipLaunchKernelGGL(k_finish_zrange, dim3((unsigned)ncells), dim3(BLOCK), 0, s, ctx->d_partials, nblocks, d_zmin, d_zmax);
     PCQ_HIP(hipGetLastError());

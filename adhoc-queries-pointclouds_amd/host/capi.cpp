@@ -1,4 +1,5 @@
-// capi.cpp — extern "C" view of the host layer (include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h).
+// capi.cpp — extern "C" view of the host layer (include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h,
+// include/pcq_query_moments.h).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -7,6 +8,7 @@
 #include "pcq_host.hpp"
 #include "pcq_query.h"
 #include "pcq_query_classes.h"
+#include "pcq_query_moments.h"
 #include "pcq_query_stats.h"
 
 using namespace pcq;
@@ -435,6 +437,17 @@ extern "C" int pcq_query_resident_bounds_zmean_raster_classes(pcq_host_resident 
     if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
         return done(Status::Err(PCQ_ERR_ARG, "mean-height raster of classes: cell_size must be finite and above 0"));
     return done(r->ds->bounds_zmean_raster_classes(bmin, zmax, cell_size, nx, ny, class_set, count, zmean, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
+}
+extern "C" int pcq_query_resident_bounds_zstd_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
+                                                     uint64_t ny, uint64_t *count, double *zmean, double *zstd, uint64_t *points_scanned) {
+    if (!r || !bmin || !count || !zmean || !zstd) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nx == 0 || ny == 0) return PCQ_OK;
+    if (nx > PCQ_QUERY_RASTER_CELLS_MAX || ny > PCQ_QUERY_RASTER_CELLS_MAX || nx * ny > PCQ_QUERY_RASTER_CELLS_MAX)  // (neither r nor a device is touched before these)
+        return done(Status::Err(PCQ_ERR_ARG, "height-spread raster: " + std::to_string(nx) + " x " + std::to_string(ny) + " cells (at most " +
+                                                 std::to_string(PCQ_QUERY_RASTER_CELLS_MAX) + ")"));
+    if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
+        return done(Status::Err(PCQ_ERR_ARG, "height-spread raster: cell_size must be finite and above 0"));
+    return done(r->ds->bounds_zstd_raster(bmin, zmax, cell_size, nx, ny, count, zmean, zstd, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
 }
 extern "C" int pcq_query_resident_count_polygon(pcq_host_resident *r, size_t nverts, const double *xy, double zmin, double zmax, uint64_t *matches,
                                                 uint64_t *points_scanned) {

@@ -413,6 +413,14 @@ public:
     // for bit bounds_zmean_raster's result.  An empty set: every count 0 and every mean NaN without a launch, after every refusal.
     Status bounds_zmean_raster_classes(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t class_set[8],
                                        uint64_t *count, double *zmean, uint64_t *points_scanned = nullptr);
+    // the height-spread raster of a box: count and zmean as bounds_zmean_raster gives them, bit for bit, and zstd[cy * nx + cx] the
+    // population standard deviation of the world z of the cell's points, NaN where it counts none.  ONE pass per batch (the groups and
+    // batches of bounds_zmean_raster) and block of PCQ_ZMOMENTS_CELLS_MAX cells; a batch gives per cell cnt, the i64 sum of the stored
+    // z and the two u64 halves of the sum of their squares (pcq_scan_dev_zmoments_raster_batch), and zmoments_merge.h, which states the
+    // formula, makes the floats from those exact integers.  The caller has checked nx, ny and cell_size.  bounds_zmean_raster's
+    // errors.  On any failure the outputs are left as they were.
+    Status bounds_zstd_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count, double *zmean,
+                              double *zstd, uint64_t *points_scanned = nullptr);
     // box AND polygon, count only: the points with z in [zmin, zmax] inside the outline of nverts finite world vertices xy[nverts][2]
     // (even-odd, exact in each file's lattice: polygon_plan.h), from ONE pass.  The caller has checked nverts and the vertices.  A
     // scanned file the outline cannot be asked of (its x or y scale, a vertex outside its i32 lattice, a span above 2^31 - 1):
@@ -439,7 +447,7 @@ private:
     Status box_segments(const AABB &bounds, pcq_predicate pred, int col_kind, Segments *seg);
     Status run(BatchEntry entry, size_t words, const Segments &seg, uint64_t *out);
     Status raster_segments(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, bool z_lattice, int col_kind,
-                           Segments *seg, std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster, zmean_raster
+                           Segments *seg, std::vector<uint32_t> *cells);  // count_bounds_raster, bounds_zrange_raster, zmean_raster, bounds_zstd_raster
     Status zmean_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t *class_set, uint64_t *count,
                         double *zmean, uint64_t *points_scanned);  // bounds_zmean_raster (class_set null: every point), bounds_zmean_raster_classes
     Status count_box(const AABB &bounds, const pcq_predicate &pred, uint64_t *matches, uint64_t *points_scanned);  // count_bounds*
@@ -450,7 +458,7 @@ private:
     std::vector<pcq_index *> last_indices_;  // the indices the last search_* scanned through
     std::vector<ResidentFile> files_;
     uint64_t *counter_ = nullptr;
-    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster and of bounds_zrange_raster: two i32; two per cell of bounds_zmean_raster)
+    size_t counter_words_ = 2;  // (ensure_counter: a word per box of count_bounds_many, per class of count_bounds_by_class, per bin of count_bounds_by_time, per cell of count_bounds_raster and of bounds_zrange_raster: two i32; two per cell of bounds_zmean_raster; four per cell of bounds_zstd_raster)
     uint64_t points_ = 0;
 };
 

@@ -40,6 +40,10 @@
 // cells, the batches' counts and sums merged on the host in world space.  Of the points of a set of classes
 // (bounds_zmean_raster_classes): the same body with pcq_scan_dev_zsum_raster_batch_classes and the class blocks in the columns.
 //
+// The height-spread raster of a box (bounds_zstd_raster): count, mean and population standard deviation of the world z of the points
+// of every cell, one pcq_scan_dev_zmoments_raster_batch per batch of the mean-height raster and block of PCQ_ZMOMENTS_CELLS_MAX
+// cells, the batches' exact integer words merged on the host (zmoments_merge.h).
+//
 // Box AND polygon (count_polygon): the points inside a world outline, one pcq_scan_dev_count_batch_polygon over the surviving files
 // with the outline rounded into each file's lattice (polygon_plan.h).
 #include <algorithm>
@@ -48,6 +52,7 @@
 
 #include "pcq_host.hpp"
 #include "polygon_plan.h"
+#include "zmoments_merge.h"
 #include "zsum_plan.h"
 
 namespace pcq {
@@ -613,6 +618,75 @@ Status ResidentDataset::zmean_raster(const double bmin[3], double zmax, double c
     }
     const double nan = std::nan("");
     for (size_t c = 0; c < words; c++) count[c] = N[c], zmean[c] = N[c] ? W[c] / (double)N[c] : nan;
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
+}
+
+// How rough is this box, cell by cell: the prologue, the groups of one z lattice and the batches of fewer than 2^32 points of
+// zmean_raster (without a class set), so that neither a batch's i64 sums nor the two u64 halves of its sums of squares can wrap.  Per
+// batch the dataset's counter holds four arrays of nx * ny words, zeroed — counts, sums, the low and the high halves of the sums of
+// squares; per block of at most PCQ_ZMOMENTS_CELLS_MAX cells ONE pcq_scan_dev_zmoments_raster_batch over the batch's files on the
+// context's stream; then one copy back.  The merge, per cell and in batch order, is zmoments_merge.h's, which states the formula.
+// `count`, `zmean`, `zstd` and `points_scanned` are written only when everything has succeeded.
+Status ResidentDataset::bounds_zstd_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count,
+                                           double *zmean, double *zstd, uint64_t *points_scanned) {
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, PCQ_PRED_BOUNDS, &seg, &cells);
+    if (!st.ok()) return st;
+    const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZMOMENTS_CELLS_MAX);
+    const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
+    std::vector<zmoments_merge::Cell> acc(words);
+    std::vector<uint64_t> got(4 * words), part[4];
+    for (auto &p : part) p.resize(words);
+    std::vector<uint8_t> grouped(nseg, 0);
+    for (size_t first = 0; first < nseg; first++) {
+        if (grouped[first]) continue;
+        const double scale = seg.cols[first].scale[2], offset = seg.cols[first].offset[2];
+        std::vector<size_t> members;  // of seg, in load order
+        std::vector<uint64_t> points;
+        for (size_t i = first; i < nseg; i++) {
+            if (grouped[i] || memcmp(&seg.cols[i].scale[2], &scale, 8) || memcmp(&seg.cols[i].offset[2], &offset, 8)) continue;
+            grouped[i] = 1;
+            members.push_back(i);
+            points.push_back(seg.cols[i].n);
+        }
+        std::vector<zsum_plan::Batch> batches;
+        size_t refused = 0;
+        if (!zsum_plan::cut(points, zsum_plan::POINTS_LIMIT, &batches, &refused)) {
+            std::string path;  // (a file with points owns its positions block)
+            for (const auto &f : files_)
+                if (f.xyz == seg.cols[members[refused]].xyz) path = f.path;
+            return Status::Err(PCQ_ERR_UNSUPPORTED, "height-spread raster: 2^32 points or more in " + path);
+        }
+        for (const zsum_plan::Batch &batch : batches) {
+            Segments grp;
+            std::vector<uint32_t> gcells;
+            for (size_t m = batch.begin; m < batch.end; m++) {
+                const size_t i = members[m];
+                grp.cols.push_back(seg.cols[i]);
+                grp.preds.push_back(seg.preds[i]);
+                gcells.push_back(cells[2 * i]), gcells.push_back(cells[2 * i + 1]);
+            }
+            st = read_counts(4 * words, [&] {
+                int rc = PCQ_OK;
+                std::vector<pcq_predicate> preds(grp.preds.size());
+                for (size_t b = 0; b < blocks.size() && !rc; b++) {
+                    for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(grp.preds[i], &gcells[2 * i], blocks[b]);
+                    uint64_t *const at = counter_ + blocks[b].at;
+                    rc = pcq_scan_dev_zmoments_raster_batch(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(), (uint32_t)blocks[b].w,
+                                                            (uint32_t)blocks[b].h, at, reinterpret_cast<int64_t *>(at + words), at + 2 * words,
+                                                            at + 3 * words, nullptr);
+                }
+                return rc;
+            }, got.data());
+            if (!st.ok()) return st;
+            for (int a = 0; a < 4; a++) scatter_blocks(blocks, got.data() + a * words, nx, part[a].data());
+            for (size_t c = 0; c < words; c++)
+                zmoments_merge::add(acc[c], scale, offset, part[0][c], (int64_t)part[1][c], part[2][c], part[3][c]);
+        }
+    }
+    for (size_t c = 0; c < words; c++) count[c] = acc[c].N, zmean[c] = zmoments_merge::zmean(acc[c]), zstd[c] = zmoments_merge::zstd(acc[c]);
     if (points_scanned) *points_scanned = seg.scanned;
     return Status::Ok();
 }

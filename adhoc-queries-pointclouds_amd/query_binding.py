@@ -1,4 +1,4 @@
-"""ctypes view of include/pcq_query.h, include/pcq_query_stats.h and include/pcq_query_classes.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
+"""ctypes view of include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h and include/pcq_query_moments.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
 
 Plumbing only, in the style of binding.load_library(): ONE signature table per header for every function it declares, so that no
 caller writes an argtypes line of its own.  The conventions, chosen once:
@@ -107,9 +107,18 @@ def _classes_signatures() -> dict:
     }
 
 
+def _moments_signatures() -> dict:
+    vp, u64, dbl = C.c_void_p, C.c_uint64, C.c_double
+    dd, pu64 = C.POINTER(dbl), C.POINTER(u64)
+    return {
+        "pcq_query_resident_bounds_zstd_raster": (C.c_int, [vp, dd, dbl, dbl, u64, u64, pu64, dd, dd, pu64]),
+    }
+
+
 sig = _signatures()   # {name: (restype, argtypes)} for every function of include/pcq_query.h
 stats_sig = _stats_signatures()   # the same for include/pcq_query_stats.h (which says why it is a header of its own)
 classes_sig = _classes_signatures()   # the same for include/pcq_query_classes.h (a header of its own for the same reason)
+moments_sig = _moments_signatures()   # the same for include/pcq_query_moments.h (likewise)
 _qlib = None
 
 
@@ -124,7 +133,7 @@ def load_query_library() -> C.CDLL:
         raise RuntimeError(f"{path} is missing: build the host layer first (make -C {_HERE}/host, or __graft_entry__.build()).")
     binding.load_library()
     lib = C.CDLL(path)
-    for name, (res, args) in list(sig.items()) + list(stats_sig.items()) + list(classes_sig.items()):
+    for name, (res, args) in list(sig.items()) + list(stats_sig.items()) + list(classes_sig.items()) + list(moments_sig.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

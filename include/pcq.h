@@ -363,6 +363,28 @@ int pcq_scan_dev_zsum_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const 
 int pcq_scan_dev_zsum_raster_batch_classes(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                                            size_t nsegments, uint32_t nx, uint32_t ny, const uint32_t class_set[8],
                                            uint64_t *device_count, int64_t *device_zsum, void *stream);
+/* The height-spread raster of a box in ONE pass: "how rough is this box, cell by cell?" — the count, the z sum and the sum of z
+ * squared that a mean and a standard deviation rest on.  The cells, the boxes, `cell_xy`, the refusals and their order are those of
+ * pcq_scan_dev_zsum_raster_batch, word for word; only the limit on nx * ny differs: PCQ_ZMOMENTS_CELLS_MAX.  The call ADDS, every
+ * add a 64-bit add MODULO 2^64: for every point (X, Y, Z) of segment i inside the box of preds[i], in cell c,
+ *
+ *     device_count[c]  += 1;
+ *     device_zsum[c]   += Z;                        (the stored i32 sign-extended, two's complement)
+ *     device_zsq_lo[c] += (Z * Z) & 0xffffffff;     (Z * Z formed in 64 bits: at most 2^62, Z = INT32_MIN)
+ *     device_zsq_hi[c] += (Z * Z) >> 32;
+ *
+ * device_count and device_zsum receive exactly what pcq_scan_dev_zsum_raster_batch adds.  The square is split so that no word needs
+ * more than 64 bits: while a call reads fewer than 2^32 points into words that were 0, neither half can wrap and the sum of Z * Z
+ * over the cell is device_zsq_hi[c] * 2^32 + device_zsq_lo[c] exactly (below 2^94); no carry is moved from the low word into the
+ * high one.  Z is in the segment's OWN integer lattice, as there: a caller batches segments of one z lattice per call
+ * (pcq_query_resident_bounds_zstd_raster does).  No word at or beyond nx * ny of any of the four arrays is touched.  nsegments == 0
+ * is PCQ_OK after the argument checks, with nothing written.  A null argument (any of the four arrays among them: "null argument"),
+ * nx == 0, ny == 0 or nx * ny above PCQ_ZMOMENTS_CELLS_MAX, and every refusal of pcq_scan_dev_zsum_raster_batch are PCQ_ERR_ARG
+ * before anything is uploaded or launched: the four arrays are untouched. */
+#define PCQ_ZMOMENTS_CELLS_MAX 1024
+int pcq_scan_dev_zmoments_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                                       size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_count, int64_t *device_zsum,
+                                       uint64_t *device_zsq_lo, uint64_t *device_zsq_hi, void *stream);
 /* Box AND polygon in ONE pass: "how many points of this box lie inside this outline?".  Every predicate is PCQ_PRED_BOUNDS and the
  * layout is that of pcq_scan_dev_count_batch_multi: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.
  * `verts_xy` is a HOST pointer to [nsegments][nverts][2] i32, in each segment's own lattice.  The rule, all in a segment's integer
