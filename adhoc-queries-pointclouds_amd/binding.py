@@ -219,6 +219,8 @@ def load_library() -> C.CDLL:
                                                              P(C.c_uint32), vp, vp, vp]),
         "pcq_scan_dev_zmoments_raster_batch": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
                                                          vp, vp, vp, vp, vp]),
+        "pcq_scan_dev_zrange_raster_batch_classes": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_uint32), C.c_size_t, C.c_uint32, C.c_uint32,
+                                                               P(C.c_uint32), P(C.c_uint32), vp, vp, vp]),
         "pcq_scan_dev_count_batch_polygon": (C.c_int, [vp, P(Columns), P(Predicate), P(C.c_int32), C.c_size_t, C.c_size_t, vp, vp]),
         "pcq_allreduce_sum_u64": (C.c_int, [P(vp), P(vp), P(vp), C.c_int]),
         "pcq_allreduce_prepare": (C.c_int, [P(C.c_int), C.c_int]),
@@ -571,6 +573,23 @@ class Context:
         wa = (C.c_uint32 * max(len(flat), 1))(*flat)
         _check(self.lib.pcq_scan_dev_zmoments_raster_batch(self.handle, ca, pa, wa, n, nx, ny, C.c_void_p(d_count), C.c_void_p(d_zsum),
                                                            C.c_void_p(d_zsq_lo), C.c_void_p(d_zsq_hi), C.c_void_p(stream)))
+
+    def scan_dev_zrange_raster_batch_classes(self, cols: Sequence[Columns], preds: Sequence[Predicate], cells, nx: int, ny: int, low, high,
+                                             d_zmin: int, d_zmax: int, stream: Optional[int] = None) -> None:
+        """The canopy-height raster of a box (segments laid out as for scan_dev_zsum_raster_batch_classes: cls beside xyz; at most
+        PCQ_ZRANGE_CLASSES_CELLS_MAX cells) in ONE pass: for every point inside its segment's box, d_zmin[cell] = min(itself, Z) when
+        the point's class byte is in `low` and d_zmax[cell] = max(itself, Z) when it is in `high`, signed i32.  low, high: the class
+        bytes of each set, iterables of 0 .. 255 (class_set_words makes the eight words), or None for a null pointer."""
+        n = len(cols)
+        ca = (Columns * n)(*cols)
+        pa = (Predicate * n)(*preds)
+        flat = [int(w) for c in cells for w in c]
+        assert len(flat) == 2 * n, "one (x, y) pair of cell widths per segment"
+        wa = (C.c_uint32 * max(len(flat), 1))(*flat)
+        la = None if low is None else (C.c_uint32 * 8)(*class_set_words(low))
+        ha = None if high is None else (C.c_uint32 * 8)(*class_set_words(high))
+        _check(self.lib.pcq_scan_dev_zrange_raster_batch_classes(self.handle, ca, pa, wa, n, nx, ny, la, ha, C.c_void_p(d_zmin),
+                                                                 C.c_void_p(d_zmax), C.c_void_p(stream)))
 
     def scan_dev_count_batch_polygon(self, cols: Sequence[Columns], preds: Sequence[Predicate], verts, d_total: int,
                                      stream: Optional[int] = None) -> None:

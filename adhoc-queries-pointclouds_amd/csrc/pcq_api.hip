@@ -350,6 +350,7 @@ static const Option k_options[] = {
     {"zsum_waves_per_cu", &pcq_ctx::zsum_waves_per_cu, 0, 32, OPT_SET},
     {"zsum_classes_waves_per_cu", &pcq_ctx::zsum_classes_waves_per_cu, 0, 32, OPT_SET},
     {"zmoments_waves_per_cu", &pcq_ctx::zmoments_waves_per_cu, 0, 32, OPT_SET},
+    {"zrange_classes_waves_per_cu", &pcq_ctx::zrange_classes_waves_per_cu, 0, 32, OPT_SET},
     {"polygon_waves_per_cu", &pcq_ctx::polygon_waves_per_cu, 0, 32, OPT_SET},
     {"raster_add", &pcq_ctx::raster_add, 0, 2, OPT_SET},  // 0 the product's, 1 per lane, 2 wave-level (scan_raster.hip)
     {"class_hist_copies", &pcq_ctx::class_hist_copies, 0, 16, OPT_SET},  // (only 0, 1, 2, 4, 8 and 16: scan_class_hist.hip)

@@ -388,6 +388,7 @@ struct pcq_ctx {
     int zsum_waves_per_cu = 0;    // mean-height raster (scan_zsum.hip): workgroups per CU before the LDS limit (0 = the product's: ZSUM_WAVES_PER_CU)
     int zsum_classes_waves_per_cu = 0;  // class-filtered mean-height raster (scan_zsum_classes.hip): the same (0 = the product's: ZSUM_CLASSES_WAVES_PER_CU)
     int zmoments_waves_per_cu = 0;  // height-spread raster (scan_zmoments.hip): the same (0 = the product's: ZMOMENTS_WAVES_PER_CU)
+    int zrange_classes_waves_per_cu = 0;  // canopy-height raster (scan_zrange_classes.hip): the same (0 = the product's: ZRANGE_CLASSES_WAVES_PER_CU)
     int polygon_waves_per_cu = 0; // box AND polygon count (scan_polygon.hip): workgroups per CU (0 = the product's: POLYGON_WAVES_PER_CU)
     int raster_add = 0;           // ... and the form of its LDS add: 1 = per lane, 2 = the wave-level shortcut (0 = the product's: RASTER_WAVE_ADD)
 #endif

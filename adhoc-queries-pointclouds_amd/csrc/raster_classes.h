@@ -1,6 +1,7 @@
 // raster_classes.h — a class SET as a second test of the raster kernels (raster_cells.h): what a kernel needs to keep, of the points
 // that pass the box, those whose class byte is in a set of the 256 classes.  Instantiated by the class-filtered mean-height raster
-// (scan_zsum_classes.hip) only; the density and height rasters could include it for entries of their own.
+// (scan_zsum_classes.hip) and, with two sets at once, by the canopy-height raster (scan_zrange_classes.hip); the density raster could
+// include it for an entry of its own.
 //
 //   the set       eight dwords, class c in the set when bit (c & 31) of word c >> 5 is set.  They are kernel arguments (uniform), not
 //                 part of the segment table: the table cache is keyed on columns, predicates and kind, and a set stored in the table
@@ -62,6 +63,43 @@ __device__ __forceinline__ void class_slot_masks(const Col2Regs<COL_U8> &r, uint
     for (int k = 0; k < 3; k++) {
         va[k] = __ballot(verdict_at(V, lanes.addr_a[k], lanes.bit_a[k]));
         vb[k] = __ballot(verdict_at(V, lanes.addr_b[k], lanes.bit_b[k]));
+    }
+}
+
+// TWO sets at once (scan_zrange_classes.hip: the lowest z of a `low` set and the highest z of a `high` set from one pass).  One
+// table: bit 0 of byte c says that class c is in the low set, bit 1 that it is in the high set, so a class byte still costs one
+// ds_read_u8.  One verdict word: byte i of the lane's word has its low verdict at bit 8i + 6 and its high verdict at bit 8i + 7
+// (vbit<COL_U8> and the bit below it), so one ds_bpermute per slot brings both verdicts of a point to its lane and a shift by
+// bit - 1 leaves them in bits 0 and 1; a ballot per set makes the masks.  Six ds_bpermute per tile, as for one set, and twelve
+// ballots.  (The other form, two verdict words and twelve ds_bpermute, was compiled beside it: DESIGN.md §4 "How high above the
+// ground is this box" has the counts.)
+__device__ __forceinline__ uint32_t class_nibble(const ClassSet &s, int lane) {  // classes 4l .. 4l + 3 of the set: bits 0 .. 3
+    const uint32_t a0 = (lane & 8) ? s.w[1] : s.w[0], a1 = (lane & 8) ? s.w[3] : s.w[2];
+    const uint32_t a2 = (lane & 8) ? s.w[5] : s.w[4], a3 = (lane & 8) ? s.w[7] : s.w[6];
+    const uint32_t b0 = (lane & 16) ? a1 : a0, b1 = (lane & 16) ? a3 : a2;
+    return (((lane & 32) ? b1 : b0) >> (4 * (lane & 7))) & 0xfu;
+}
+__device__ __forceinline__ uint32_t nibble_bytes(uint32_t nib) { return (nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21; }
+constexpr uint32_t CLASS_LOW = 1u, CLASS_HIGH = 2u;  // the bits of a byte of the two-set table
+__device__ __forceinline__ void class_table_fill2(uint32_t *table, const ClassSet &low, const ClassSet &high, int lane) {
+    table[lane] = nibble_bytes(class_nibble(low, lane)) | nibble_bytes(class_nibble(high, lane)) << 1;
+}
+// Class byte c against both sets: CLASS_LOW | CLASS_HIGH, either or 0.
+__device__ __forceinline__ uint32_t class_in_sets(const uint32_t *table, uint32_t c) { return reinterpret_cast<const uint8_t *>(table)[c]; }
+__device__ __forceinline__ uint32_t class_verdict_word2(uint32_t bytes, const uint32_t *table) {
+    return class_in_sets(table, bytes & 0xffu) << 6 | class_in_sets(table, (bytes >> 8) & 0xffu) << 14 |
+           class_in_sets(table, (bytes >> 16) & 0xffu) << 22 | class_in_sets(table, bytes >> 24) << 30;
+}
+// The twelve class masks of a tile: class_slot_masks for the low set (la, lb) and the high set (ha, hb).
+__device__ __forceinline__ void class_slot_masks2(const Col2Regs<COL_U8> &r, uint32_t shift, const Col2<COL_U8> &lanes, const uint32_t *table,
+                                                  uint64_t (&la)[3], uint64_t (&lb)[3], uint64_t (&ha)[3], uint64_t (&hb)[3]) {
+    const uint32_t V = class_verdict_word2(__builtin_amdgcn_alignbit((uint32_t)r.hi, (uint32_t)r.lo, shift), table);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((int)lanes.addr_a[k], (int)V) >> (lanes.bit_a[k] - 1);
+        const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)lanes.addr_b[k], (int)V) >> (lanes.bit_b[k] - 1);
+        la[k] = __ballot((a & CLASS_LOW) != 0), ha[k] = __ballot((a & CLASS_HIGH) != 0);
+        lb[k] = __ballot((b & CLASS_LOW) != 0), hb[k] = __ballot((b & CLASS_HIGH) != 0);
     }
 }
 

@@ -1,5 +1,5 @@
 // scan_batch_host.h — the host side of the K1-family batched launches (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip,
-// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_zsum.hip, scan_zsum_classes.hip, scan_zmoments.hip, scan_polygon.hip): host code only; the kernels and their constants are in scan_tiles.h.
+// scan_class_hist.hip, scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_zsum.hip, scan_zsum_classes.hip, scan_zrange_classes.hip, scan_zmoments.hip, scan_polygon.hip): host code only; the kernels and their constants are in scan_tiles.h.
 #pragma once
 
 #include <vector>

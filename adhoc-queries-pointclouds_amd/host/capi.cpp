@@ -1,5 +1,5 @@
 // capi.cpp — extern "C" view of the host layer (include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h,
-// include/pcq_query_moments.h).
+// include/pcq_query_moments.h, include/pcq_query_canopy.h).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -7,6 +7,7 @@
 #include "lz4_frame.hpp"
 #include "pcq_host.hpp"
 #include "pcq_query.h"
+#include "pcq_query_canopy.h"
 #include "pcq_query_classes.h"
 #include "pcq_query_moments.h"
 #include "pcq_query_stats.h"
@@ -448,6 +449,19 @@ extern "C" int pcq_query_resident_bounds_zstd_raster(pcq_host_resident *r, const
     if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
         return done(Status::Err(PCQ_ERR_ARG, "height-spread raster: cell_size must be finite and above 0"));
     return done(r->ds->bounds_zstd_raster(bmin, zmax, cell_size, nx, ny, count, zmean, zstd, points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
+}
+extern "C" int pcq_query_resident_bounds_canopy_raster(pcq_host_resident *r, const double bmin[3], double zmax, double cell_size, uint64_t nx,
+                                                       uint64_t ny, const uint32_t ground_set[8], const uint32_t surface_set[8],
+                                                       double *zground, double *zsurface, double *height, uint64_t *points_scanned) {
+    if (!r || !bmin || !ground_set || !surface_set || !zground || !zsurface) return done(Status::Err(PCQ_ERR_ARG, "null argument"));
+    if (nx == 0 || ny == 0) return PCQ_OK;
+    if (nx > PCQ_QUERY_RASTER_CELLS_MAX || ny > PCQ_QUERY_RASTER_CELLS_MAX || nx * ny > PCQ_QUERY_RASTER_CELLS_MAX)  // (neither r nor a device is touched before these)
+        return done(Status::Err(PCQ_ERR_ARG, "canopy-height raster: " + std::to_string(nx) + " x " + std::to_string(ny) + " cells (at most " +
+                                                 std::to_string(PCQ_QUERY_RASTER_CELLS_MAX) + ")"));
+    if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
+        return done(Status::Err(PCQ_ERR_ARG, "canopy-height raster: cell_size must be finite and above 0"));
+    return done(r->ds->bounds_canopy_raster(bmin, zmax, cell_size, nx, ny, ground_set, surface_set, zground, zsurface, height,
+                                            points_scanned));  // bmin[2] > zmax: PCQ_ERR_PANIC
 }
 extern "C" int pcq_query_resident_count_polygon(pcq_host_resident *r, size_t nverts, const double *xy, double zmin, double zmax, uint64_t *matches,
                                                 uint64_t *points_scanned) {

@@ -421,6 +421,16 @@ public:
     // errors.  On any failure the outputs are left as they were.
     Status bounds_zstd_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, uint64_t *count, double *zmean,
                               double *zstd, uint64_t *points_scanned = nullptr);
+    // the canopy-height raster of a box ("how high above the ground"): zground[cy * nx + cx] is the lowest world z of the cell's points
+    // whose class byte is in ground_set, zsurface[...] the highest world z of those whose class byte is in surface_set — bit (c & 31)
+    // of word c >> 5 — and height[...] (may be null) their difference; NaN where a group's word stayed at its sentinel INT32_MAX /
+    // INT32_MIN in every group, so a ground point stored at INT32_MAX and a surface point stored at INT32_MIN read as no point
+    // (include/pcq_query_canopy.h states the definition).  bounds_zrange_raster's prologue, groups, blocks and errors; ONE
+    // pcq_scan_dev_zrange_raster_batch_classes per group and block of PCQ_ZRANGE_CLASSES_CELLS_MAX cells.  Both sets empty: every output
+    // NaN without a launch, after every refusal.  On any failure the outputs are left as they were.
+    Status bounds_canopy_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny, const uint32_t ground_set[8],
+                                const uint32_t surface_set[8], double *zground, double *zsurface, double *height,
+                                uint64_t *points_scanned = nullptr);
     // box AND polygon, count only: the points with z in [zmin, zmax] inside the outline of nverts finite world vertices xy[nverts][2]
     // (even-odd, exact in each file's lattice: polygon_plan.h), from ONE pass.  The caller has checked nverts and the vertices.  A
     // scanned file the outline cannot be asked of (its x or y scale, a vertex outside its i32 lattice, a span above 2^31 - 1):

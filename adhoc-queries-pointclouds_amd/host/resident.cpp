@@ -526,6 +526,76 @@ Status ResidentDataset::bounds_zrange_raster(const double bmin[3], double zmax, 
     return Status::Ok();
 }
 
+// How high above the ground is this box, cell by cell: the body of bounds_zrange_raster, spelt out beside it so that that entry
+// compiles as it did — the same prologue (with the class blocks in the columns), groups, presets, blocks and copy back — with ONE
+// pcq_scan_dev_zrange_raster_batch_classes per group and block of at most PCQ_ZRANGE_CLASSES_CELLS_MAX cells.  The two arrays are
+// independent: a minimum that left INT32_MAX becomes a world value whatever the maximum holds, and the reverse, so a ground point
+// stored at INT32_MAX and a surface point stored at INT32_MIN read as no point (include/pcq_query_canopy.h: the sentinel rule).
+// height = zsurface - zground in f64, NaN where either is.  Both sets empty: the prologue's refusals, then NaN everywhere without a
+// launch.  The outputs are written only when everything has succeeded.
+Status ResidentDataset::bounds_canopy_raster(const double bmin[3], double zmax, double cell_size, uint64_t nx, uint64_t ny,
+                                             const uint32_t ground_set[8], const uint32_t surface_set[8], double *zground, double *zsurface,
+                                             double *height, uint64_t *points_scanned) {
+    Segments seg;
+    std::vector<uint32_t> cells;  // [segment][2]
+    Status st = raster_segments(bmin, zmax, cell_size, nx, ny, /*z_lattice=*/true, PCQ_PRED_BOUNDS_CLASS, &seg, &cells);
+    if (!st.ok()) return st;
+    uint32_t any = 0;
+    for (int w = 0; w < 8; w++) any |= ground_set[w] | surface_set[w];
+    const std::vector<RasterBlock> blocks = raster_blocks(nx, ny, PCQ_ZRANGE_CLASSES_CELLS_MAX);
+    const size_t words = (size_t)(nx * ny), nseg = seg.cols.size();
+    const double nan = std::nan("");
+    std::vector<double> lo(words, nan), hi(words, nan);
+    std::vector<int32_t> preset(2 * words), got(2 * words), zmin(words), zmax_i(words);
+    std::fill(preset.begin(), preset.begin() + words, INT32_MAX);
+    std::fill(preset.begin() + words, preset.end(), INT32_MIN);
+    std::vector<uint8_t> grouped(nseg, 0);
+    for (size_t first = 0; first < nseg && any; first++) {
+        if (grouped[first]) continue;
+        const double scale = seg.cols[first].scale[2], offset = seg.cols[first].offset[2];
+        Segments grp;
+        std::vector<uint32_t> gcells;
+        for (size_t i = first; i < nseg; i++) {
+            if (grouped[i] || memcmp(&seg.cols[i].scale[2], &scale, 8) || memcmp(&seg.cols[i].offset[2], &offset, 8)) continue;
+            grouped[i] = 1;
+            grp.cols.push_back(seg.cols[i]);
+            grp.preds.push_back(seg.preds[i]);
+            gcells.push_back(cells[2 * i]), gcells.push_back(cells[2 * i + 1]);
+        }
+        int rc = ensure_counter(words);  // (2 x words i32)
+        if (!rc) rc = pcq_ctx_synchronize(ctx_);  // (a call that failed may have left launches that write the counter)
+        if (!rc) rc = pcq_copy_to_device(ctx_, counter_, preset.data(), 2 * words * sizeof(int32_t));
+        int32_t *const d_zmin = reinterpret_cast<int32_t *>(counter_), *const d_zmax = d_zmin + words;
+        std::vector<pcq_predicate> preds(grp.preds.size());
+        for (size_t b = 0; b < blocks.size() && !rc; b++) {
+            for (size_t i = 0; i < preds.size(); i++) preds[i] = block_predicate(grp.preds[i], &gcells[2 * i], blocks[b]);
+            rc = pcq_scan_dev_zrange_raster_batch_classes(ctx_, grp.cols.data(), preds.data(), gcells.data(), preds.size(), (uint32_t)blocks[b].w,
+                                                          (uint32_t)blocks[b].h, ground_set, surface_set, d_zmin + blocks[b].at,
+                                                          d_zmax + blocks[b].at, nullptr);
+        }
+        if (!rc) rc = pcq_copy_to_host(ctx_, got.data(), counter_, 2 * words * sizeof(int32_t));
+        if (rc) return Status::FromLib(rc);
+        scatter_blocks(blocks, got.data(), nx, zmin.data());
+        scatter_blocks(blocks, got.data() + words, nx, zmax_i.data());
+        for (size_t c = 0; c < words; c++) {
+            if (zmin[c] != INT32_MAX) {  // (the sentinel: no ground point of this group)
+                const double a = ((double)zmin[c] * scale) + offset;
+                if (!(lo[c] <= a)) lo[c] = a;  // (NaN: nothing yet)
+            }
+            if (zmax_i[c] != INT32_MIN) {
+                const double b = ((double)zmax_i[c] * scale) + offset;
+                if (!(hi[c] >= b)) hi[c] = b;
+            }
+        }
+    }
+    memcpy(zground, lo.data(), words * sizeof(double));
+    memcpy(zsurface, hi.data(), words * sizeof(double));
+    if (height)
+        for (size_t c = 0; c < words; c++) height[c] = hi[c] - lo[c];  // (NaN where either is)
+    if (points_scanned) *points_scanned = seg.scanned;
+    return Status::Ok();
+}
+
 // How high is this box on average, cell by cell: raster_segments (with the z lattice rule), the surviving files in groups of one z
 // lattice as for bounds_zrange_raster, and within a group the files, in load order, in batches of fewer than 2^32 points
 // (zsum_plan.h), so that a batch's i64 sums cannot wrap.  Per batch the dataset's counter holds nx * ny u64 counts and behind them

@@ -1,4 +1,4 @@
-"""ctypes view of include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h and include/pcq_query_moments.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
+"""ctypes view of include/pcq_query.h, include/pcq_query_stats.h, include/pcq_query_classes.h, include/pcq_query_moments.h and include/pcq_query_canopy.h (libpcq_query.so): the C++ host layer and the resident-dataset API.
 
 Plumbing only, in the style of binding.load_library(): ONE signature table per header for every function it declares, so that no
 caller writes an argtypes line of its own.  The conventions, chosen once:
@@ -115,10 +115,19 @@ def _moments_signatures() -> dict:
     }
 
 
+def _canopy_signatures() -> dict:
+    vp, u64, dbl = C.c_void_p, C.c_uint64, C.c_double
+    dd, pu64, pu32 = C.POINTER(dbl), C.POINTER(u64), C.POINTER(C.c_uint32)
+    return {
+        "pcq_query_resident_bounds_canopy_raster": (C.c_int, [vp, dd, dbl, dbl, u64, u64, pu32, pu32, dd, dd, dd, pu64]),
+    }
+
+
 sig = _signatures()   # {name: (restype, argtypes)} for every function of include/pcq_query.h
 stats_sig = _stats_signatures()   # the same for include/pcq_query_stats.h (which says why it is a header of its own)
 classes_sig = _classes_signatures()   # the same for include/pcq_query_classes.h (a header of its own for the same reason)
 moments_sig = _moments_signatures()   # the same for include/pcq_query_moments.h (likewise)
+canopy_sig = _canopy_signatures()   # the same for include/pcq_query_canopy.h (likewise)
 _qlib = None
 
 
@@ -133,7 +142,8 @@ def load_query_library() -> C.CDLL:
         raise RuntimeError(f"{path} is missing: build the host layer first (make -C {_HERE}/host, or __graft_entry__.build()).")
     binding.load_library()
     lib = C.CDLL(path)
-    for name, (res, args) in list(sig.items()) + list(stats_sig.items()) + list(classes_sig.items()) + list(moments_sig.items()):
+    for name, (res, args) in list(sig.items()) + list(stats_sig.items()) + list(classes_sig.items()) + list(moments_sig.items()) + \
+            list(canopy_sig.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -385,6 +385,33 @@ int pcq_scan_dev_zsum_raster_batch_classes(pcq_ctx *ctx, const pcq_columns *cols
 int pcq_scan_dev_zmoments_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
                                        size_t nsegments, uint32_t nx, uint32_t ny, uint64_t *device_count, int64_t *device_zsum,
                                        uint64_t *device_zsq_lo, uint64_t *device_zsq_hi, void *stream);
+/* The canopy-height raster of a box in ONE pass: "how high above the ground is this box, cell by cell?" — the lowest z of the
+ * points of a LOW set of classes and the highest z of the points of a HIGH set, per cell, from one read of positions and class
+ * bytes.  Layout, predicate kind, `cell_xy`, the cell rule and every refusal are those of pcq_scan_dev_zsum_raster_batch_classes:
+ * PCQ_PRED_BOUNDS only, cols[i].cls the classification block of the same points (cls_stride 1, not null, any byte alignment), and a
+ * null set is a null argument; the limit on nx * ny is PCQ_ZRANGE_CLASSES_CELLS_MAX.  `low_set` and `high_set` are HOST pointers to
+ * eight words each: class c is in a set when bit (c & 31) of its word c >> 5 is set.  The call is a FOLD, as
+ * pcq_scan_dev_zrange_raster_batch is.  After it, for every cell c,
+ *
+ *     device_zmin[c] = min(before, Z of every point inside the box of its segment whose class byte is in low_set);
+ *     device_zmax[c] = max(before, Z of every point inside the box of its segment whose class byte is in high_set);
+ *
+ * signed i32 compares; a point in both sets counts for both, a point in neither for nothing, and a point that fails only the z
+ * test of its box contributes nothing.  A caller presets INT32_MAX / INT32_MIN and reads those values back as "no such point".  Z is
+ * in the segment's OWN integer lattice: a caller batches segments of one z lattice per call.  No word at or beyond nx * ny of either
+ * array is touched.  On any refusal (PCQ_ERR_ARG) both arrays are untouched.  Consequences:
+ *   (a) both sets with all 256 bits give, word for word, what pcq_scan_dev_zrange_raster_batch gives from the same presets;
+ *   (b) with low_set == high_set == S, on words preset to INT32_MAX / INT32_MIN and data without a stored Z of INT32_MAX,
+ *       device_zmin[c] != INT32_MAX exactly where pcq_scan_dev_zsum_raster_batch_classes counts a point of S in c; the same holds
+ *       for INT32_MIN, device_zmax and its sentinel;
+ *   (c) an empty low set leaves device_zmin as it was while device_zmax is still folded, and the reverse;
+ *   (d) with BOTH sets empty every check of the table is made, then nothing is uploaded or launched: PCQ_OK, the words as they were.
+ * The segment table travels under the kind of pcq_scan_dev_zsum_raster_batch_classes (the sets are kernel arguments, never part
+ * of it), so a table uploaded by either entry serves the other. */
+#define PCQ_ZRANGE_CLASSES_CELLS_MAX 4096 /* 256 + 32 KiB of LDS per wave: four workgroups per CU at the limit */
+int pcq_scan_dev_zrange_raster_batch_classes(pcq_ctx *ctx, const pcq_columns *cols, const pcq_predicate *preds, const uint32_t *cell_xy,
+                                             size_t nsegments, uint32_t nx, uint32_t ny, const uint32_t low_set[8],
+                                             const uint32_t high_set[8], int32_t *device_zmin, int32_t *device_zmax, void *stream);
 /* Box AND polygon in ONE pass: "how many points of this box lie inside this outline?".  Every predicate is PCQ_PRED_BOUNDS and the
  * layout is that of pcq_scan_dev_count_batch_multi: xyz_stride 12, 16-byte aligned, non-null when n > 0; cls is not read.
  * `verts_xy` is a HOST pointer to [nsegments][nverts][2] i32, in each segment's own lattice.  The rule, all in a segment's integer

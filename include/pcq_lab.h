@@ -14,7 +14,8 @@
  * (profiles/zrange_raster_rate_sweep.log), and "zsum_waves_per_cu", the same of the mean-height raster of a box
  * (profiles/zsum_raster_rate_sweep.log), and "zsum_classes_waves_per_cu", the same of the mean-height raster of a set of classes
  * (profiles/zsum_classes_rate_sweep.log), and "zmoments_waves_per_cu", the same of the height-spread raster of a box
- * (profiles/zmoments_rate_sweep.log), and "polygon_waves_per_cu", the grid of the box AND polygon count
+ * (profiles/zmoments_rate_sweep.log), and "zrange_classes_waves_per_cu", the same of the canopy-height raster of a box
+ * (profiles/zrange_classes_rate_sweep.log), and "polygon_waves_per_cu", the grid of the box AND polygon count
  * (profiles/polygon_rate_sweep.log).
  *
  * (Round 2's experimental shapes of the grid collector — option "grid_variant" — left with the kernels they varied:
