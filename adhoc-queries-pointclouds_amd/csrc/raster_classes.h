@@ -1,7 +1,7 @@
 // raster_classes.h — a class SET as a second test of the raster kernels (raster_cells.h): what a kernel needs to keep, of the points
 // that pass the box, those whose class byte is in a set of the 256 classes.  Instantiated by the class-filtered mean-height raster
 // (scan_zsum_classes.hip) and, with two sets at once, by the canopy-height raster (scan_zrange_classes.hip); the density raster could
-// include it for an entry of its own.
+// include it for an entry of its own.  The fill of a segment with the class column stands at the end.
 //
 //   the set       eight dwords, class c in the set when bit (c & 31) of word c >> 5 is set.  They are kernel arguments (uniform), not
 //                 part of the segment table: the table cache is keyed on columns, predicates and kind, and a set stored in the table
@@ -134,6 +134,19 @@ __device__ __forceinline__ Col2<COL_U8> col2_of(Col2<COL_U8> lanes, const Raster
     lanes.off_hi = c.off_hi;
     lanes.shift = c.shift;
     return lanes;
+}
+template <>
+struct PipeCol<COL_RASTER_U8> {
+    static constexpr int value = COL_U8;
+};
+
+// raster_segment_fill for a table with the class column: its refusal first, then the pointer and the raster's fill.
+inline int raster_segment_fill(const char *prefix, DevRasterClassSegment &g, const pcq_predicate &pred, const pcq_columns &col, const uint32_t *cw,
+                               uint32_t nx, uint32_t ny, size_t i) {
+    if (col.n && (col.cls_stride != 1 || !col.cls))
+        return pcq_fail(PCQ_ERR_ARG, "%s: LAST classification blocks only (stride 1, not null), segment %zu", prefix, i);
+    g.cls = (const uint8_t *)col.cls;
+    return raster_segment_fill(prefix, static_cast<DevRasterSegment &>(g), pred, col, cw, nx, ny, i);
 }
 
 }  // namespace

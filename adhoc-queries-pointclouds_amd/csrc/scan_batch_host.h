@@ -33,6 +33,11 @@ void seg_box(Seg &g, const DP &dp) {
     for (int a = 0; a < 3; a++) g.lo[a] = dp.lo[a], g.width[a] = dp.width[a];
     g.empty = dp.empty;
 }
+// admit(i) of the entries that take a box and nothing else
+inline int admit_bounds_only(const char *prefix, const pcq_predicate &pred, size_t i) {
+    return pred.kind != PCQ_PRED_BOUNDS ? pcq_fail(PCQ_ERR_ARG, "%s: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", prefix, pred.kind, i)
+                                        : (int)PCQ_OK;
+}
 template <typename Seg, typename Admit, typename Fill, typename Launch, typename Finish>
 int k1_batch_launch(pcq_ctx *ctx, const K1Batch &b, const pcq_columns *cols, size_t nsegments, hipStream_t s, Admit admit, Fill fill, Launch launch,
                     Finish finish) {

@@ -93,41 +93,14 @@ __global__ __launch_bounds__(64) void k_bounds_class_hist_pipe(const DevCombined
     static_assert(R >= 1 && R <= 16 && (R & (R - 1)) == 0, "copies of the histogram: a power of two");
     constexpr int COL = COL_U8;
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = TILES * (3 + col2_loads(COL));  // per register set
     __shared__ uint32_t hist[PCQ_CLASS_BINS * R];
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     for (int i = lane; i < PCQ_CLASS_BINS * R; i += 64) hist[i] = 0;
     __syncthreads();
-    if (blockIdx.x < total_steps) {
-        Col2<COL> lanes{};
-        lanes.off_lo = 4 * lane;
-        const HistLanes hl = hist_lanes(lane);
-        PipeRegs<TILES, COL> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES, COL>(A, ca.base, u - ca.begin, lane, col2_of(lanes, ca.col));
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) hist_eval<TILES, R>(A, ca, hl, hist, lane);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) hist_eval<TILES, R>(B, cb, hl, hist, lane);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
+    const HistLanes hl = hist_lanes(lane);
+    pipe_scan<TILES, COL>(segs, nseg, total_steps, lane, [&](const PipeRegs<TILES, COL> &P, const SegCursor<COL> &c, const Col2<COL> &) {
+        hist_eval<TILES, R>(P, c, hl, hist, lane);
+    });
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const DevCombinedSegment &g = segs[i];
         if (g.empty) continue;
@@ -171,12 +144,7 @@ extern "C" int pcq_scan_dev_class_hist_batch(pcq_ctx *ctx, const pcq_columns *co
 #endif
     const K1Batch b = {"class_hist_batch", PCQ_SEGMENTS_CLASS_HIST, waves, PCQ_CLASS_BINS, PCQ_CLASS_BINS, /*null_refused=*/true};
     return k1_batch_launch<DevCombinedSegment>(
-        ctx, b, cols, nsegments, device_hist, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "class_hist_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
+        ctx, b, cols, nsegments, device_hist, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
         [&](DevCombinedSegment &g, size_t i) {
             if (cols[i].cls_stride != 1 || (!cols[i].cls && cols[i].n))
                 return pcq_fail(PCQ_ERR_ARG, "class_hist_batch: LAST classification blocks only (stride 1), segment %zu", i);

@@ -24,10 +24,13 @@
 //    tile's 256 class bytes (one dword per lane) or 256 times (two dwordx4 per lane) are tested per lane into a verdict word;
 //    one ds_bpermute per (load, start phase) brings each point's verdict to the lane that holds its first dword, where it is
 //    ANDed into the mask algebra before the popcount.  13 / 20 B per point.
-// The loop of the software pipeline is written out in every kernel: a shared driver with the kernels as its stages compiled to
-//    the same vector code, but its other scalar code measured slower than this form in alternated runs ("The
-//    software pipeline").  The register sets, their loads and their counted waits are shared (scan_tiles.h: PipeRegs, VecRegs).
-// The batched K1 (k_bounds_count_batch_pipe<TILES, Col...>, the same loop written out) and the host side of its launch
+// The loop of the software pipeline is written out in the kernels of this file, in the multi-box count and in three rasters: a
+//    shared driver with every kernel as a stage object compiled to the same vector code, but its other scalar code measured slower
+//    than this form in alternated runs ("The software pipeline").  Nine kernels that walk a segment table with seg_seek
+//    share pipe_scan (scan_tiles.h), which takes only the eval as a callable, came out of the compiler structurally as the loops it
+//    replaced and measured as fast ("One pipeline driver for the batched scans"); three rasters did not and keep their
+//    loops.  The register sets, their loads and their counted waits are shared (scan_tiles.h: PipeRegs, VecRegs).
+// The batched K1 (k_bounds_count_batch_pipe<TILES, Col...>, on pipe_scan) and the host side of its launch
 //    (k1_batch_launch, scan_batch_host.h) live in headers: pcq_scan_dev_count_batch below launches the box kind, scan_count_batch.hip the two
 //    kinds with a second column.  The batched K2 and the per-file kernels are here; the finish reduction of every count is
 //    pcq_launch_finish_counts (scan_count_multi.hip).

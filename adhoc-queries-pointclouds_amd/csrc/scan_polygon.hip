@@ -56,6 +56,10 @@ template <>
 struct SegCol<COL_POLYGON> {
     uint32_t edge_begin, nedges;  // (uniform)
 };
+template <>
+struct PipeCol<COL_POLYGON> {
+    static constexpr int value = COL_NONE;
+};
 // through SGPRs like the box (seg_seek says why)
 __device__ __forceinline__ void segcol_seek(SegCol<COL_POLYGON> &c, const DevPolygonSegment &g, int) {
     uint32_t eb = g.edge_begin, ne = g.nedges;
@@ -127,36 +131,11 @@ __global__ __launch_bounds__(64) void k_bounds_polygon_pipe(const DevPolygonSegm
                                                            const DevPolygonEdge *__restrict__ edges, uint64_t *__restrict__ partials) {
     constexpr int COL = COL_POLYGON;
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = PipeRegs<TILES>::LOADS;  // per register set
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     uint64_t total = 0;
-    if (blockIdx.x < total_steps) {
-        PipeRegs<TILES> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES>(A, ca.base, u - ca.begin, lane);
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane);  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) total += polygon_eval<TILES>(A, ca, edges, lane);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane);
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) total += polygon_eval<TILES>(B, cb, edges, lane);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
+    pipe_scan<TILES, COL>(segs, nseg, total_steps, lane, [&](const PipeRegs<TILES> &P, const SegCursor<COL> &c, const Col2<COL_NONE> &) {
+        total += polygon_eval<TILES>(P, c, edges, lane);
+    });
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const DevPolygonSegment &g = segs[i];
         if (g.empty) continue;
@@ -214,12 +193,7 @@ extern "C" int pcq_scan_dev_count_batch_polygon(pcq_ctx *ctx, const pcq_columns 
     const K1Batch b = {"count_batch_polygon", PCQ_SEGMENTS_POLYGON, waves, 1, 1, /*null_refused=*/true,
                        edges.data(), edges.size() * sizeof(DevPolygonEdge)};
     return k1_batch_launch<DevPolygonSegment>(
-        ctx, b, cols, nsegments, device_total, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "count_batch_polygon: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
+        ctx, b, cols, nsegments, device_total, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
         [&](DevPolygonSegment &g, size_t i) {
             DevPred dp;
             const int prc = pcq_make_dev_pred(&preds[i], &dp);

@@ -2,11 +2,13 @@
 // pass (pcq_scan_dev_raster_batch).
 //
 // The box count (scan_tiles.h: k_bounds_count_batch_pipe<2>) answers one cell per read of the 12 B/point, the multi-box count
-// eight.  k_bounds_raster_pipe<TILES, WAVE> keeps the shape of the box count — one wave per workgroup, TILES tiles per step, two
-// register sets, 2 x 3 loads per set behind the counted s_waitcnt, steps numbered across segments, the cursor refreshed through
-// SGPRs at a seek (seg_seek<TILES, COL_RASTER>: the origin, the cell widths and their magics travel like the box), the clamped
-// tail prefetch — and, instead of popcounting the start bits, brings the x and y of every passing point into one lane, divides
-// both by the segment's cell widths and adds 1 to the cell's word of a raster in LDS:
+// eight.  k_bounds_raster_pipe<TILES, WAVE> runs the box count's software pipeline (pipe_scan of scan_tiles.h: one wave per workgroup,
+// TILES tiles per step, two register sets, 2 x 3 loads per set behind the counted s_waitcnt, steps numbered across segments, the
+// cursor refreshed through SGPRs at a seek — COL_RASTER: the origin, the cell widths and their magics travel like the box — the
+// clamped tail prefetch) and the rasters' leftover loop (raster_leftovers of raster_cells.h), and, instead of popcounting the start
+// bits, brings the x and y of every passing point into one lane, divides both by the segment's cell widths and adds 1 to the cell's
+// word of a raster in LDS.  The tile is this file's own (tile_raster: one value moves across lanes, not the two of the z-carrying tiles, and
+// raster_cells.h has what a helper did to it):
 //
 //   values     in load k lane l starts one point among j = 0..2, at j0 = (3 - (k + l) % 3) % 3: x = v[k][j0], y = v[k][j0 + 1],
 //              both its own; the verdict is bit l of s012 (tile_count_regs).  Where j0 == 0 a second point starts at j = 3: x =
@@ -42,12 +44,12 @@
 namespace {
 
 // Workgroups (of one wave) per CU: the smaller of this constant and what a CU's LDS holds at the launch's raster size
-// (RASTER_LDS_PER_CU / (4 nx ny): 5 at PCQ_RASTER_CELLS_MAX, 40 at 32 x 32), rounded down to a multiple of four from four on: the
+// (RASTER_LDS_PER_CU / (4 nx ny): 5 at PCQ_RASTER_CELLS_MAX, 40 at 32 x 32), rounded down to a multiple of four from four on
+// (raster_waves_per_cu of raster_cells.h): the
 // steps are dealt out evenly, the pass waits for instruction latency rather than for HBM, and a fifth wave makes one SIMD of a CU
 // carry two (5 per CU is slower than 4, 10 slower than 8).  DESIGN.md §4 "Where in this box are the points" has the sweep
 // (profiles/raster_rate_sweep.log, option raster_waves_per_cu of the lab library).
 constexpr int RASTER_WAVES_PER_CU = 16;
-constexpr uint32_t RASTER_LDS_PER_CU = 160 * 1024;
 // The form of the LDS add that ships: the wave-level shortcut (true) or the plain per-lane ds_add_u32 (false).  Measured (16 files x
 // 163 M points, every point inside the box, the best grid of each, ms, generator order / scan-strip order): 8 x 8 cells: plain 5.2 /
 // 8.4, shortcut 5.7 / 5.7; 64 x 64: plain 6.6 / 8.8, shortcut 8.5 / 8.7; 128 x 64: plain 9.3 / 9.3, shortcut 13.2 / 13.2.  The
@@ -59,6 +61,9 @@ constexpr bool RASTER_WAVE_ADD = false;
 
 // One slot: the points of the lanes in `pass` (uniform) into their cells, without a branch.  WAVE: when every passing lane has the
 // cell of the first one, that lane alone adds their number; a slot without a passing lane has no first lane and adds nothing.
+// (A function, adapted by a lambda where raster_leftovers wants a fold: as a functor that holds `ras`, like the z folds, the kernel came out of the
+// compiler with 79 VGPRs for 80 and 1407 instructions for 1427 in the pipeline, which tools/count_kernels_asm_compare.py does not
+// pass as the same kernel.)
 template <bool WAVE>
 __device__ __forceinline__ void raster_add(uint32_t *ras, uint64_t pass, uint32_t cell, int lane) {
     bool add = (pass >> lane) & 1ull;
@@ -102,65 +107,18 @@ __device__ __forceinline__ void tile_raster(const v4i (&v)[3], const LaneBox &lb
 }
 
 template <int TILES, bool WAVE>
-__device__ __forceinline__ void raster_eval(const PipeRegs<TILES> &P, const SegCursor<COL_RASTER> &c, uint32_t nx, uint32_t *ras, int lane) {
-#pragma unroll
-    for (int t = 0; t < TILES; t++) tile_raster<WAVE>(P.r[t], c.lb, c.col, nx, ras, lane);
-}
-
-template <int TILES, bool WAVE>
 __global__ __launch_bounds__(64) void k_bounds_raster_pipe(const DevRasterSegment *__restrict__ segs, int nseg, uint64_t total_steps, uint32_t nx,
                                                           uint32_t cells, uint64_t *__restrict__ partials) {
     constexpr int COL = COL_RASTER;
-    constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = PipeRegs<TILES>::LOADS;  // per register set
-    extern __shared__ uint32_t ras[];              // `cells` words: the launch's dynamic shared memory
+    extern __shared__ uint32_t ras[];  // `cells` words: the launch's dynamic shared memory
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     for (uint32_t i = lane; i < cells; i += 64) ras[i] = 0;
     __syncthreads();
-    if (blockIdx.x < total_steps) {
-        PipeRegs<TILES> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES>(A, ca.base, u - ca.begin, lane);
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane);  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) raster_eval<TILES, WAVE>(A, ca, nx, ras, lane);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane);
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) raster_eval<TILES, WAVE>(B, cb, nx, ras, lane);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
-    for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
-        const DevRasterSegment &g = segs[i];
-        if (g.empty) continue;
-        const uint64_t n = g.n;
-        const int *q0 = reinterpret_cast<const int *>(g.xyz);
-        const RasterCol c = {g.lo[0], g.lo[1], g.cw[0], g.cw[1], g.magic[0], g.magic[1]};
-        for (uint64_t p = (n / STEP_POINTS) * STEP_POINTS + lane; p < ((n + 63) & ~63ull); p += 64) {  // (whole waves: the slot's masks are the wave's)
-            bool pass = false;
-            int x = 0, y = 0;
-            if (p < n) {
-                const int *q = q0 + 3 * p;
-                x = q[0], y = q[1];
-                pass = ((uint32_t)(x - g.lo[0]) <= g.width[0]) & ((uint32_t)(y - g.lo[1]) <= g.width[1]) & ((uint32_t)(q[2] - g.lo[2]) <= g.width[2]);
-            }
-            raster_add<WAVE>(ras, __ballot(pass), cell_of(x, y, c, nx), lane);
-        }
-    }
+    pipe_scan<TILES, COL>(segs, nseg, total_steps, lane, [&](const PipeRegs<TILES> &P, const SegCursor<COL> &c, const Col2<COL_NONE> &) {
+#pragma unroll
+        for (int t = 0; t < TILES; t++) tile_raster<WAVE>(P.r[t], c.lb, c.col, nx, ras, lane);
+    });
+    raster_leftovers<TILES>(segs, nseg, nx, lane, BoxOnly{}, [&](uint64_t pass, uint32_t cell, int, int l) { raster_add<WAVE>(ras, pass, cell, l); });
     __syncthreads();
     for (uint32_t i = lane; i < cells; i += 64) partials[(uint64_t)i * gridDim.x + blockIdx.x] = ras[i];
 }
@@ -183,31 +141,16 @@ extern "C" int pcq_scan_dev_raster_batch(pcq_ctx *ctx, const pcq_columns *cols, 
     if (nsegments == 0) return PCQ_OK;
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const uint32_t cells = nx * ny;
-    int waves = RASTER_WAVES_PER_CU;
+    int lab_waves = 0;
 #ifdef PCQ_LAB  // (tools/resident_raster_rate.py sweeps both)
-    if (ctx->raster_waves_per_cu) waves = ctx->raster_waves_per_cu;
+    lab_waves = ctx->raster_waves_per_cu;
     const bool other_add = ctx->raster_add && (ctx->raster_add == 2) != RASTER_WAVE_ADD;
 #endif
-    const int by_lds = (int)(RASTER_LDS_PER_CU / (cells * sizeof(uint32_t)));  // (>= 5: cells <= PCQ_RASTER_CELLS_MAX)
-    if (waves > by_lds) waves = by_lds;
-    bool whole_simds = true;
-#ifdef PCQ_LAB
-    whole_simds = ctx->raster_waves_per_cu == 0;  // (the sweep sees 5 and 6 as they are)
-#endif
-    if (whole_simds && waves > 4) waves &= ~3;
+    const int waves = raster_waves_per_cu(RASTER_WAVES_PER_CU, cells * sizeof(uint32_t), lab_waves);
     const K1Batch b = {"raster_batch", PCQ_SEGMENTS_RASTER, waves, (int)cells, (int)cells, /*null_refused=*/true};
     return k1_batch_launch<DevRasterSegment>(
-        ctx, b, cols, nsegments, device_raster, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "raster_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
-        [&](DevRasterSegment &g, size_t i) {
-            const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
-            const uint32_t dim[2] = {nx, ny};
-            return raster_segment_fill("raster_batch", g, preds[i], cols[i], cw, dim, i);
-        },
+        ctx, b, cols, nsegments, device_raster, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
+        [&](DevRasterSegment &g, size_t i) { return raster_segment_fill(b.prefix, g, preds[i], cols[i], cell_xy + 2 * i, nx, ny, i); },
         [&](unsigned g, uint64_t steps) {
 #ifdef PCQ_LAB
             if (other_add) launch_raster<!RASTER_WAVE_ADD>(ctx, g, (int)nsegments, steps, nx, cells, s);

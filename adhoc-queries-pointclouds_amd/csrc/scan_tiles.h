@@ -1,8 +1,10 @@
 // scan_tiles.h — what the count kernels (scan_count.hip, scan_count_batch.hip, scan_count_multi.hip, scan_class_hist.hip,
 // scan_time_hist.hip, scan_raster.hip, scan_zrange.hip, scan_polygon.hip, scan_time.hip) and the chunk index (chunk_index.hip) share: the mask algebra of a 768-dword tile of packed LAST positions,
 // K1's second column (class bytes or GPS times), the register sets of the software pipeline with their loads and counted waits
-// (PipeRegs for the K1 family, VecRegs for the one-column kernels K2 and K3; the loop itself is written in each kernel: see
-// scan_count.hip) and the batched K1 (k_bounds_count_batch_pipe: one template for the box, box AND class and box AND time
+// (PipeRegs for the K1 family, VecRegs for the one-column kernels K2 and K3), the software pipeline of every kernel that walks a
+// segment table with seg_seek (pipe_scan: the batched K1, the class and time histograms, the polygon count and the density, height and
+// canopy-height rasters call it with their own eval; the one-file kernels, the multi-box count, whose cursor carries eight boxes and
+// no `empty`, and the three rasters that add 64-bit words write their loop out: see scan_count.hip and those rasters' files) and the batched K1 (k_bounds_count_batch_pipe: one template for the box, box AND class and box AND time
 // kinds).  The host side of a K1-family batched launch is k1_batch_launch (scan_batch_host.h); the finish reduction of every
 // count is pcq_launch_finish_counts (scan_count_multi.hip).  See scan_count.hip for the design.
 #pragma once
@@ -485,6 +487,66 @@ __device__ __forceinline__ bool seg_point(const SegTail<COL_F64> &c, uint64_t p)
     return (t >= c.t0) & (t < c.t1);
 }
 
+// What a cursor kind loads beside the positions: the count kinds their own column; a kind that only carries constants of its segment
+// (COL_RASTER of raster_cells.h, COL_POLYGON of scan_polygon.hip) names COL_NONE here, COL_RASTER_U8 (raster_classes.h) COL_U8.
+template <int COL>
+struct PipeCol {
+    static constexpr int value = COL;
+};
+// the loads of step `step` of the cursor's segment
+template <int TILES, int COL>
+__device__ __forceinline__ void cursor_load(PipeRegs<TILES, PipeCol<COL>::value> &R, const SegCursor<COL> &c, uint64_t step, int lane,
+                                            const Col2<PipeCol<COL>::value> &lanes) {
+    if constexpr (PipeCol<COL>::value == COL_NONE) pipe_load<TILES>(R, c.base, step, lane);
+    else pipe_load<TILES, PipeCol<COL>::value>(R, c.base, step, lane, col2_of(lanes, c.col));
+}
+
+// THE software pipeline of the batched K1 family (every kernel that walks a segment table with seg_seek): the steps blockIdx.x,
+// blockIdx.x + gridDim.x, ... of the launch through two register sets.  While the tiles of step u are evaluated the loads of step
+// u + stride are in flight; a counted wait leaves exactly those in flight.  Each register set remembers the segment its step came
+// from (its cursor); behind the last step the prefetch is clamped to a step already read, and both sets are landed before the registers
+// die.  eval(P, cursor, lanes) is called once for every step of a segment that is not empty: P the step's registers, lanes the
+// lane constants of the second column (col2_lanes; of them a kernel pays only for what it reads).
+// `segs` is not __restrict__ here, unlike seg_seek's and the kernels' own: with it the skip loop of seg_seek read tile_begin with a
+// scalar load in six kernels (no drain of the prefetched tiles there) — better, perhaps, but another kernel than the one that was
+// measured, so a change of its own.
+template <int TILES, int COL, typename Eval>
+__device__ __forceinline__ void pipe_scan(const typename BatchSeg<COL>::type *segs, int nseg, uint64_t total_steps, int lane,
+                                          const Eval &eval) {
+    constexpr int LD = PipeCol<COL>::value;
+    constexpr int LOADS = PipeRegs<TILES, LD>::LOADS;  // per register set
+    const uint64_t stride = gridDim.x;
+    if (blockIdx.x < total_steps) {
+        Col2<LD> lanes{};
+        if constexpr (LD == COL_U8) lanes.off_lo = 4 * lane;
+        if constexpr (LD != COL_NONE) col2_lanes<LD>(lanes, lane);
+        PipeRegs<TILES, LD> A, B;
+        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
+        uint64_t u = blockIdx.x;
+        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
+        cursor_load<TILES, COL>(A, ca, u - ca.begin, lane, lanes);
+        for (;;) {
+            const uint64_t u1 = u + stride;
+            cb = ca;
+            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
+            cursor_load<TILES, COL>(B, cb, (u1 < total_steps ? u1 : u) - cb.begin, lane, lanes);  // clamped at the tail: an L2 hit
+            pipe_wait<LOADS>(A);
+            if (!ca.empty) eval(A, ca, lanes);
+            if (u1 >= total_steps) break;
+            const uint64_t u2 = u1 + stride;
+            ca = cb;
+            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
+            cursor_load<TILES, COL>(A, ca, (u2 < total_steps ? u2 : u1) - ca.begin, lane, lanes);
+            pipe_wait<LOADS>(B);
+            if (!cb.empty) eval(B, cb, lanes);
+            if (u2 >= total_steps) break;
+            u = u2;
+        }
+        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
+        pipe_wait<0>(B);
+    }
+}
+
 template <int TILES, typename... Col>
 __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment *__restrict__ raw, int nseg, uint64_t total_steps,
                                                                uint64_t *__restrict__ partials) {
@@ -492,40 +554,12 @@ __global__ __launch_bounds__(64) void k_bounds_count_batch_pipe(const DevSegment
     static_assert(sizeof...(Col) <= 1, "one second column at most");
     typedef typename BatchSeg<COL>::type Seg;
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = PipeRegs<TILES, COL>::LOADS;  // per register set
     const Seg *__restrict__ segs = reinterpret_cast<const Seg *>(raw);
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     uint64_t total = 0;
-    if (blockIdx.x < total_steps) {
-        Col2<COL> lanes{};
-        if constexpr (COL == COL_U8) lanes.off_lo = 4 * lane;
-        if constexpr (COL != COL_NONE) col2_lanes<COL>(lanes, lane);
-        PipeRegs<TILES, COL> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES, COL>(A, ca.base, u - ca.begin, lane, col2_of(lanes, ca.col));
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) total += pipe_eval<TILES, COL>(A, ca.lb, col2_of(lanes, ca.col));
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) total += pipe_eval<TILES, COL>(B, cb.lb, col2_of(lanes, cb.col));
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
+    pipe_scan<TILES, COL>(segs, nseg, total_steps, lane, [&](const PipeRegs<TILES, COL> &P, const SegCursor<COL> &c, const Col2<COL> &lanes) {
+        total += pipe_eval<TILES, COL>(P, c.lb, col2_of(lanes, c.col));
+    });
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const Seg &g = segs[i];
         if (g.empty) continue;

@@ -145,11 +145,9 @@ __global__ __launch_bounds__(64) void k_bounds_time_hist_pipe(const DevBoundsTim
                                                              uint64_t *__restrict__ partials) {
     constexpr int COL = COL_F64;
     constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = TILES * (3 + col2_loads(COL));  // per register set
     __shared__ double tab[PCQ_TIME_BINS_MAX];
     __shared__ uint32_t hist[PCQ_TIME_BINS_MAX];
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     const uint32_t slots = half ? 2 * half : 1;  // P (<= PCQ_TIME_BINS_MAX: the entry has checked nbins)
     for (uint32_t i = lane; i < slots; i += 64) {
         tab[i] = i + 1 < (uint32_t)nbins ? edges[i + 1] : __longlong_as_double(0x7ff0000000000000ll);
@@ -157,34 +155,10 @@ __global__ __launch_bounds__(64) void k_bounds_time_hist_pipe(const DevBoundsTim
     }
     const EdgeTable E = {tab, half, edges[0], edges[nbins]};
     __syncthreads();
-    if (blockIdx.x < total_steps) {
-        Col2<COL> lanes{};
-        const TimeLanes hl = time_lanes(lane);
-        PipeRegs<TILES, COL> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES, COL>(A, ca.base, u - ca.begin, lane, col2_of(lanes, ca.col));
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES, COL>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) hist_eval<TILES>(A, ca.lb, hl, E, hist);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES, COL>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) hist_eval<TILES>(B, cb.lb, hl, E, hist);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
+    const TimeLanes hl = time_lanes(lane);
+    pipe_scan<TILES, COL>(segs, nseg, total_steps, lane, [&](const PipeRegs<TILES, COL> &P, const SegCursor<COL> &c, const Col2<COL> &) {
+        hist_eval<TILES>(P, c.lb, hl, E, hist);
+    });
     for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
         const DevBoundsTimeSegment &g = segs[i];
         if (g.empty) continue;
@@ -235,12 +209,7 @@ extern "C" int pcq_scan_dev_time_hist_batch(pcq_ctx *ctx, const pcq_columns *col
     const K1Batch b = {"time_hist_batch", PCQ_SEGMENTS_TIME_HIST, waves, (int)nbins, (int)nbins, /*null_refused=*/true,
                        trailer.data(), trailer.size() * sizeof(uint64_t)};
     return k1_batch_launch<DevBoundsTimeSegment>(
-        ctx, b, cols, nsegments, device_hist, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "time_hist_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
+        ctx, b, cols, nsegments, device_hist, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
         [&](DevBoundsTimeSegment &g, size_t i) {
             if (cols[i].cls_stride != 8 || ((uintptr_t)cols[i].cls & 7) != 0 || (!cols[i].cls && cols[i].n))
                 return pcq_fail(PCQ_ERR_ARG, "time_hist_batch: LAST time blocks only (stride 8, 8-byte aligned), segment %zu", i);

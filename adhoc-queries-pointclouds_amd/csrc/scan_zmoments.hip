@@ -20,6 +20,11 @@
 // At exit the wave writes four u64 per cell to partials[slice * gridDim.x + blockIdx.x]: slice `cell` the count, `cells + cell` the
 // sum, `2 cells + cell` the low and `3 cells + cell` the high word; pcq_launch_finish_zmoments (scan_count_multi.hip: k_finish_counts
 // per array) adds each quarter into its array, modulo 2^64.
+// This kernel keeps its own text of the pipeline loop, the tile and the leftover loop.  On pipe_scan (scan_tiles.h), a tile shared
+// with the height raster and raster_leftovers (raster_cells.h) it compiled to a kernel structurally equal to this one (equal VGPRs, occupancy,
+// waits, loads, LDS operations and compares) that ran 0.76 % slower (9.530 against 9.458 ms, the parent's spread 0.030) at the largest raster, where
+// the LDS leaves one wave per SIMD, and inside the parent's spread at 8 x 8 cells (profiles/raster_frame_rate.log): outside the rule
+// of that change, so the copy stays.
 #include "pcq_internal.h"
 #include "raster_cells.h"
 #include "raster_div.h"
@@ -29,7 +34,7 @@
 namespace {
 
 // Workgroups (of one wave) per CU: the mean-height raster's rule with twice its LDS per cell — the smaller of this constant and what
-// a CU's LDS holds at the launch's raster size (ZMOMENTS_LDS_PER_CU / (32 nx ny): 5 at PCQ_ZMOMENTS_CELLS_MAX, 80 at 8 x 8), rounded
+// a CU's LDS holds at the launch's raster size (RASTER_LDS_PER_CU / (32 nx ny): 5 at PCQ_ZMOMENTS_CELLS_MAX, 80 at 8 x 8), rounded
 // down to a multiple of four from four on, so that no SIMD of a CU carries a wave more than another.  Measured (16 files x 163 M
 // points, every point inside the box, generator order, ms by workgroups per CU): 8 x 8 cells: 4: 13.8, 8: 13.7, 12: 13.7, 16: 13.6;
 // 1024 cells: 4: 9.5, 5 (the LDS limit): 16.7.  The pass follows its LDS adds, four per point: 1.94 times the mean-height pass at
@@ -37,7 +42,6 @@ namespace {
 // has the sweep (profiles/zmoments_rate_sweep.log, option zmoments_waves_per_cu of the lab library, which takes the value
 // as given up to the LDS limit).
 constexpr int ZMOMENTS_WAVES_PER_CU = 16;
-constexpr uint32_t ZMOMENTS_LDS_PER_CU = 160 * 1024;
 
 // The four arrays of a wave's raster in its shared memory.
 struct MomentWords {
@@ -170,28 +174,16 @@ extern "C" int pcq_scan_dev_zmoments_raster_batch(pcq_ctx *ctx, const pcq_column
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const uint32_t cells = nx * ny;
     const size_t lds = 4 * cells * sizeof(uint64_t);
-    int waves = ZMOMENTS_WAVES_PER_CU;
-    bool whole_simds = true;
-#ifdef PCQ_LAB  // (tools/resident_zmoments_rate.py sweeps it; the sweep sees 5 and 6 as they are)
-    if (ctx->zmoments_waves_per_cu) waves = ctx->zmoments_waves_per_cu, whole_simds = false;
+    int lab_waves = 0;
+#ifdef PCQ_LAB  // (tools/resident_zmoments_rate.py sweeps it)
+    lab_waves = ctx->zmoments_waves_per_cu;
 #endif
-    const int by_lds = (int)(ZMOMENTS_LDS_PER_CU / lds);  // (>= 5: cells <= PCQ_ZMOMENTS_CELLS_MAX)
-    if (waves > by_lds) waves = by_lds;
-    if (whole_simds && waves > 4) waves &= ~3;
+    const int waves = raster_waves_per_cu(ZMOMENTS_WAVES_PER_CU, lds, lab_waves);
     // (the density raster's table under its kind: the four kernels read it alike)
     const K1Batch b = {"zmoments_raster_batch", PCQ_SEGMENTS_RASTER, waves, 4 * (int)cells, 4 * (int)cells, /*null_refused=*/true};
     return k1_batch_launch<DevRasterSegment>(
-        ctx, b, cols, nsegments, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "zmoments_raster_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
-        [&](DevRasterSegment &g, size_t i) {
-            const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
-            const uint32_t dim[2] = {nx, ny};
-            return raster_segment_fill("zmoments_raster_batch", g, preds[i], cols[i], cw, dim, i);
-        },
+        ctx, b, cols, nsegments, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
+        [&](DevRasterSegment &g, size_t i) { return raster_segment_fill(b.prefix, g, preds[i], cols[i], cell_xy + 2 * i, nx, ny, i); },
         [&](unsigned g, uint64_t steps) {
             hipLaunchKernelGGL((k_bounds_zmoments_pipe<K1_TILES>), dim3(g), dim3(64), lds, s,
                                reinterpret_cast<const DevRasterSegment *>(ctx->d_segments), (int)nsegments, steps, nx, cells, ctx->d_partials);

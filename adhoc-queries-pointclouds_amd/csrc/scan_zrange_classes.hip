@@ -4,27 +4,24 @@
 // Ground {2} and surface "everything but 7 and 18" give the canopy-height (or building-height) model; both sets equal give the
 // class-filtered height raster; both sets full give the unfiltered height raster word for word.
 //
-// k_bounds_zrange_classes_pipe<TILES> is the height raster's kernel (scan_zrange.hip: k_bounds_zrange_pipe<TILES>) in the frame of the
-// class-filtered mean-height raster (scan_zsum_classes.hip): one wave per workgroup, TILES tiles per step, two register sets,
-// 2 x (3 + 2) loads per set behind the counted s_waitcnt (PipeRegs<TILES, COL_U8>), the cursor SegCursor<COL_RASTER_U8> over a
-// DevRasterClassSegment table — that entry's table under that entry's kind: the two kernels read every field alike, so a table
-// uploaded by one entry serves the other — the clamped tail prefetch, skipped empty segments, the cell by two exact divisions, the six
-// straight-line slots, the exit into `partials` (max in the high word, min in the low one).  What differs:
+// k_bounds_zrange_classes_pipe<TILES> is the height raster's kernel (scan_zrange.hip: k_bounds_zrange_pipe<TILES>) with the class bytes
+// as a second column: pipe_scan (scan_tiles.h) with the cursor SegCursor<COL_RASTER_U8> over a DevRasterClassSegment table — the
+// class-filtered mean-height raster's table under that entry's kind: the two kernels read every field alike, so a table uploaded by
+// one entry serves the other — 2 x (3 + 2) loads per set behind the counted s_waitcnt, the two halves of that kernel's tile
+// (tile_slot_masks, tile_slot_cells: raster_cells.h), the rasters' leftover loop (raster_leftovers), the exit into `partials` (max in
+// the high word, min in the low one).  This file's own:
 //
 //   class sets    two ClassSet by value among the kernel's arguments, sixteen dwords (raster_classes.h says why not in the segment
 //                 table), spread at entry into ONE table of 256 bytes in front of the raster's words in the wave's LDS: bit 0 of byte
 //                 c says that c is in the low set, bit 1 that it is in the high set.  A class byte costs one ds_read_u8 for both.
-//   verdicts      class_slot_masks2 (raster_classes.h) gives, per tile, twelve wave masks: low and high for the six slots, from six
-//                 ds_bpermute of one word that carries both bits per byte.  A tile none of whose points passes the BOX is skipped
-//                 before the transport, and again before the divisions when no passing point is in either set.
+//   verdicts      class_slot_masks2 (raster_classes.h) gives, per tile, twelve wave masks: low and high for the six
+//                 slots, from six ds_bpermute of one word that carries both bits per byte.  A tile none of whose points passes the BOX
+//                 is skipped before the transport, and again before the divisions when no passing point is in either set.
 //   fold          a lane whose point passes the box and the low mask does one ds_min_i32 on zmin[cell], one whose point passes the box
 //                 and the high mask one ds_max_i32 on zmax[cell]; a point in both sets does both, a point in neither nothing.
-//   leftovers     the one-lane-per-point loop reads cls[p] and tests it with the same class_in_sets.
+//   leftovers     the one-lane-per-point loop reads cls[p] and tests it with the same class_in_sets (the hook TwoSets).
 //   finish        k_finish_zrange_classes below, not pcq_launch_finish_zrange: the two halves of a cell's word are folded each on its
 //                 own (that finish skips a cell whose minimum lies above its maximum, which two sets make an ordinary case).
-//
-// The slots of tile_zrange_classes are tile_zrange's (scan_zrange.hip), spelt out again: that file's kernel and scan_zsum_classes.hip's
-// are to come out of the compiler as they were (profiles/zrange_classes_asm_compare.log).
 #include "pcq_internal.h"
 #include "raster_cells.h"
 #include "raster_classes.h"
@@ -35,132 +32,81 @@
 namespace {
 
 // Workgroups (of one wave) per CU: the height raster's rule (scan_zrange.hip: ZRANGE_WAVES_PER_CU) — the smaller of this constant and
-// what a CU's LDS holds at the launch's raster size (ZRANGE_CLASSES_LDS_PER_CU / (256 + 8 nx ny): 4 at PCQ_ZRANGE_CLASSES_CELLS_MAX),
-// rounded down to a multiple of four from four on.  16 is the sweep's winner (profiles/zrange_classes_rate_sweep.log, option
+// what a CU's LDS holds at the launch's raster size (RASTER_LDS_PER_CU / (256 + 8 nx ny): 4 at PCQ_ZRANGE_CLASSES_CELLS_MAX),
+// rounded down to a multiple of four from four on (raster_waves_per_cu).  16 is the sweep's winner (profiles/zrange_classes_rate_sweep.log, option
 // zrange_classes_waves_per_cu of the lab library, which takes the value as given up to the LDS limit; 16 files x 163 M points, 45 % of
 // class 2, every point inside the box, generator order, ms for ground {2} and surface all but {7, 18} / both sets {2} / both sets full
 // by workgroups per CU): 8 x 8 cells: 3: 14.7 / 14.6 / 14.8, 4: 10.8 / 10.7 / 11.0, 6: 9.1 / 9.0 / 9.6, 8: 7.0 / 6.8 / 8.0, 12: 6.6 /
 // 6.3 / 7.7, 16: 6.4 / 6.2 / 7.5; 4096 cells: 3: 14.6 / 14.6 - 18.1 / 14.7, 4 (the LDS limit): 13.6 / 13.6 / 13.7.  DESIGN.md §4 "How
 // high above the ground is this box" has the rates beside the unfiltered raster's.
 constexpr int ZRANGE_CLASSES_WAVES_PER_CU = 16;
-constexpr uint32_t ZRANGE_CLASSES_LDS_PER_CU = 160 * 1024;
+
+// A slot's two masks, and what the leftover loop (raster_leftovers) asks of a point beside the box: its class against both sets.
+struct LowHigh {
+    uint64_t low, high;
+};
+struct TwoSets {
+    const uint32_t *table;  // class_table_fill2
+    __device__ __forceinline__ uint32_t point(bool box, const DevRasterClassSegment &g, uint64_t p) const {
+        return box ? class_in_sets(table, g.cls[p]) : 0u;
+    }
+    __device__ __forceinline__ LowHigh masks(uint32_t in) const { return {__ballot((in & CLASS_LOW) != 0), __ballot((in & CLASS_HIGH) != 0)}; }
+};
 
 // One slot: the z of the lanes in `low` into the minimum of their cells, of the lanes in `high` into the maximum (both uniform).
-__device__ __forceinline__ void zrange_classes_fold(int *zmin, int *zmax, uint64_t low, uint64_t high, uint32_t cell, int z, int lane) {
-    if ((low >> lane) & 1ull) atomicMin(&zmin[cell], z);  // (results unused: ds_min_i32 / ds_max_i32, exec-masked)
-    if ((high >> lane) & 1ull) atomicMax(&zmax[cell], z);
-}
+struct zrange_classes_fold {
+    int *zmin, *zmax;
+    __device__ __forceinline__ void operator()(const LowHigh &m, uint32_t cell, int z, int lane) const {
+        if ((m.low >> lane) & 1ull) atomicMin(&zmin[cell], z);  // (results unused: ds_min_i32 / ds_max_i32, exec-masked)
+        if ((m.high >> lane) & 1ull) atomicMax(&zmax[cell], z);
+    }
+};
 
 // One tile in registers: the z of every point that passes the box into its cell's minimum when its class is in the low set and into
-// its cell's maximum when its class is in the high set.
+// its cell's maximum when its class is in the high set.  A tile none of whose points passes the BOX is skipped before the transport of
+// the class verdicts, and again in front of the divisions when no passing point is in either set.
 __device__ __forceinline__ void tile_zrange_classes(const v4i (&v)[3], const Col2Regs<COL_U8> &cr, const LaneBox &lb, const RasterClassCol &c,
-                                                    const Col2<COL_U8> &lanes, const uint32_t *table, uint32_t nx, int *zmin, int *zmax,
-                                                    int lane) {
-    uint64_t t[3][4], s012[3], s3[3];
-    tile_start_masks(v, lb, t);
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        s012[k] = (t[k][0] & start_lanes(k)) | (t[k][1] & start_lanes(k + 1)) | (t[k][2] & start_lanes(k + 2));
-        s3[k] = t[k][3] & start_lanes(k + 3);
-    }
-    if ((s012[0] | s012[1] | s012[2] | s3[0] | s3[1] | s3[2]) == 0) return;
+                                                    const Col2<COL_U8> &lanes, const uint32_t *table, uint32_t nx,
+                                                    const zrange_classes_fold &fold, int lane) {
+    uint64_t s012[3], s3[3];
+    if (!tile_slot_masks(v, lb, s012, s3)) return;
     uint64_t la[3], lb3[3], ha[3], hb3[3];
     class_slot_masks2(cr, c.shift, lanes, table, la, lb3, ha, hb3);
+    LowHigh ma[3], mb[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) la[k] &= s012[k], ha[k] &= s012[k], lb3[k] &= s3[k], hb3[k] &= s3[k];
-    if ((la[0] | la[1] | la[2] | lb3[0] | lb3[1] | lb3[2] | ha[0] | ha[1] | ha[2] | hb3[0] | hb3[1] | hb3[2]) == 0) return;
+    for (int k = 0; k < 3; k++) ma[k] = {la[k] & s012[k], ha[k] & s012[k]}, mb[k] = {lb3[k] & s3[k], hb3[k] & s3[k]};
+    if ((ma[0].low | ma[1].low | ma[2].low | mb[0].low | mb[1].low | mb[2].low | ma[0].high | ma[1].high | ma[2].high | mb[0].high |
+         mb[1].high | mb[2].high) == 0)
+        return;
     uint32_t ca[3], cb[3];
     int za[3], zb[3];
+    tile_slot_cells(v, c.r, nx, lane, ca, za, cb, zb);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const bool j0_0 = (start_lanes(k) >> lane) & 1ull, j0_1 = (start_lanes(k + 1) >> lane) & 1ull;
-        // dwords 4 and 5 of the lane: the next lane's 0 and 1; behind lane 63, lane 0 of the next load (the tile ends with load 2)
-        const int n0 = next_lane(v[k][0], k < 2 ? __builtin_amdgcn_readlane(v[k < 2 ? k + 1 : k][0], 0) : 0);
-        const int n1 = next_lane(v[k][1], k < 2 ? __builtin_amdgcn_readlane(v[k < 2 ? k + 1 : k][1], 0) : 0);
-        const int x = j0_0 ? v[k][0] : (j0_1 ? v[k][1] : v[k][2]);
-        const int y = j0_0 ? v[k][1] : (j0_1 ? v[k][2] : v[k][3]);
-        za[k] = j0_0 ? v[k][2] : (j0_1 ? v[k][3] : n0);
-        ca[k] = cell_of(x, y, c.r, nx);
-        cb[k] = cell_of(v[k][3], n0, c.r, nx);
-        zb[k] = n1;
+        fold(ma[k], ca[k], za[k], lane);
+        fold(mb[k], cb[k], zb[k], lane);
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        zrange_classes_fold(zmin, zmax, la[k], ha[k], ca[k], za[k], lane);
-        zrange_classes_fold(zmin, zmax, lb3[k], hb3[k], cb[k], zb[k], lane);
-    }
-}
-
-template <int TILES>
-__device__ __forceinline__ void zrange_classes_eval(const PipeRegs<TILES, COL_U8> &P, const SegCursor<COL_RASTER_U8> &c, const Col2<COL_U8> &lanes,
-                                                    const uint32_t *table, uint32_t nx, int *zmin, int *zmax, int lane) {
-#pragma unroll
-    for (int t = 0; t < TILES; t++) tile_zrange_classes(P.r[t], P.c[t], c.lb, c.col, lanes, table, nx, zmin, zmax, lane);
 }
 
 template <int TILES>
 __global__ __launch_bounds__(64) void k_bounds_zrange_classes_pipe(const DevRasterClassSegment *__restrict__ segs, int nseg, uint64_t total_steps,
                                                                   uint32_t nx, uint32_t cells, ClassSet low, ClassSet high,
                                                                   uint64_t *__restrict__ partials) {
-    constexpr int COL = COL_RASTER_U8;
-    constexpr uint64_t STEP_POINTS = (uint64_t)TILES * TILE_POINTS;
-    constexpr int LOADS = PipeRegs<TILES, COL_U8>::LOADS;  // per register set
-    extern __shared__ int zrange_classes_words[];          // the class table, then 2 x `cells` words: the launch's dynamic shared memory
+    extern __shared__ int zrange_classes_words[];  // the class table, then 2 x `cells` words: the launch's dynamic shared memory
     uint32_t *const table = reinterpret_cast<uint32_t *>(zrange_classes_words);
     int *const zmin = zrange_classes_words + CLASS_TABLE_BYTES / 4, *const zmax = zmin + cells;
+    const zrange_classes_fold fold = {zmin, zmax};
+    const TwoSets hook = {table};
     const int lane = threadIdx.x;
-    const uint64_t stride = gridDim.x;
     class_table_fill2(table, low, high, lane);
     for (uint32_t i = lane; i < cells; i += 64) zmin[i] = INT32_MAX, zmax[i] = INT32_MIN;
     __syncthreads();
-    if (blockIdx.x < total_steps) {
-        Col2<COL_U8> lanes{};
-        lanes.off_lo = 4 * lane;
-        col2_lanes<COL_U8>(lanes, lane);
-        PipeRegs<TILES, COL_U8> A, B;
-        SegCursor<COL> ca = {0, 0, 0, nullptr, {}, true, {}}, cb;
-        uint64_t u = blockIdx.x;
-        seg_seek<TILES, COL>(ca, segs, nseg, u, lane);
-        pipe_load<TILES, COL_U8>(A, ca.base, u - ca.begin, lane, col2_of(lanes, ca.col));
-        for (;;) {
-            const uint64_t u1 = u + stride;
-            cb = ca;
-            if (u1 < total_steps) seg_seek<TILES, COL>(cb, segs, nseg, u1, lane);
-            pipe_load<TILES, COL_U8>(B, cb.base, (u1 < total_steps ? u1 : u) - cb.begin, lane, col2_of(lanes, cb.col));  // clamped at the tail: an L2 hit
-            pipe_wait<LOADS>(A);
-            if (!ca.empty) zrange_classes_eval<TILES>(A, ca, lanes, table, nx, zmin, zmax, lane);
-            if (u1 >= total_steps) break;
-            const uint64_t u2 = u1 + stride;
-            ca = cb;
-            if (u2 < total_steps) seg_seek<TILES, COL>(ca, segs, nseg, u2, lane);
-            pipe_load<TILES, COL_U8>(A, ca.base, (u2 < total_steps ? u2 : u1) - ca.begin, lane, col2_of(lanes, ca.col));
-            pipe_wait<LOADS>(B);
-            if (!cb.empty) zrange_classes_eval<TILES>(B, cb, lanes, table, nx, zmin, zmax, lane);
-            if (u2 >= total_steps) break;
-            u = u2;
-        }
-        pipe_wait<0>(A);  // the clamped tail prefetch is still in flight: land it before the registers die
-        pipe_wait<0>(B);
-    }
-    for (int i = blockIdx.x; i < nseg; i += gridDim.x) {  // fewer-than-a-step leftovers of segment i, one lane per point
-        const DevRasterClassSegment &g = segs[i];
-        if (g.empty) continue;
-        const uint64_t n = g.n;
-        const int *q0 = reinterpret_cast<const int *>(g.xyz);
-        const uint8_t *cls = g.cls;
-        const RasterCol c = {g.lo[0], g.lo[1], g.cw[0], g.cw[1], g.magic[0], g.magic[1]};
-        for (uint64_t p = (n / STEP_POINTS) * STEP_POINTS + lane; p < ((n + 63) & ~63ull); p += 64) {  // (whole waves: the slot's masks are the wave's)
-            uint32_t in = 0;
-            int x = 0, y = 0, z = 0;
-            if (p < n) {
-                const int *q = q0 + 3 * p;
-                x = q[0], y = q[1], z = q[2];
-                const bool box = ((uint32_t)(x - g.lo[0]) <= g.width[0]) & ((uint32_t)(y - g.lo[1]) <= g.width[1]) & ((uint32_t)(z - g.lo[2]) <= g.width[2]);
-                in = box ? class_in_sets(table, cls[p]) : 0u;
-            }
-            zrange_classes_fold(zmin, zmax, __ballot((in & CLASS_LOW) != 0), __ballot((in & CLASS_HIGH) != 0), cell_of(x, y, c, nx), z, lane);
-        }
-    }
+    pipe_scan<TILES, COL_RASTER_U8>(
+        segs, nseg, total_steps, lane, [&](const PipeRegs<TILES, COL_U8> &P, const SegCursor<COL_RASTER_U8> &c, const Col2<COL_U8> &lanes) {
+#pragma unroll
+            for (int t = 0; t < TILES; t++) tile_zrange_classes(P.r[t], P.c[t], c.lb, c.col, lanes, table, nx, fold, lane);
+        });
+    raster_leftovers<TILES>(segs, nseg, nx, lane, hook, fold);
     __syncthreads();
     for (uint32_t i = lane; i < cells; i += 64)
         partials[(uint64_t)i * gridDim.x + blockIdx.x] = ((uint64_t)(uint32_t)zmax[i] << 32) | (uint64_t)(uint32_t)zmin[i];
@@ -212,35 +158,20 @@ extern "C" int pcq_scan_dev_zrange_raster_batch_classes(pcq_ctx *ctx, const pcq_
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const uint32_t cells = nx * ny;
     const size_t lds = CLASS_TABLE_BYTES + 2 * cells * sizeof(int);
-    int waves = ZRANGE_CLASSES_WAVES_PER_CU;
-    bool whole_simds = true;
-#ifdef PCQ_LAB  // (tools/resident_zrange_classes_rate.py sweeps it; the sweep sees 5 and 6 as they are)
-    if (ctx->zrange_classes_waves_per_cu) waves = ctx->zrange_classes_waves_per_cu, whole_simds = false;
+    int lab_waves = 0;
+#ifdef PCQ_LAB  // (tools/resident_zrange_classes_rate.py sweeps it)
+    lab_waves = ctx->zrange_classes_waves_per_cu;
 #endif
-    const int by_lds = (int)(ZRANGE_CLASSES_LDS_PER_CU / lds);  // (>= 4: cells <= PCQ_ZRANGE_CLASSES_CELLS_MAX, and the table)
-    if (waves > by_lds) waves = by_lds;
-    if (whole_simds && waves > 4) waves &= ~3;
+    const int waves = raster_waves_per_cu(ZRANGE_CLASSES_WAVES_PER_CU, lds, lab_waves);
     ClassSet low, high;
     uint32_t any = 0;
     for (int w = 0; w < 8; w++) any |= (low.w[w] = low_set[w]) | (high.w[w] = high_set[w]);
-    const auto admit = [&](size_t i) {
-        return preds[i].kind != PCQ_PRED_BOUNDS
-                   ? pcq_fail(PCQ_ERR_ARG, "zrange_raster_batch_classes: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                   : (int)PCQ_OK;
-    };
-    const auto fill = [&](DevRasterClassSegment &g, size_t i) {
-        if (cols[i].n && (cols[i].cls_stride != 1 || !cols[i].cls))
-            return pcq_fail(PCQ_ERR_ARG, "zrange_raster_batch_classes: LAST classification blocks only (stride 1, not null), segment %zu", i);
-        const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
-        const uint32_t dim[2] = {nx, ny};
-        g.cls = (const uint8_t *)cols[i].cls;
-        return raster_segment_fill("zrange_raster_batch_classes", g, preds[i], cols[i], cw, dim, i);
-    };
     // (the class-filtered mean-height raster's table under its kind: the two kernels read it alike)
     K1Batch b = {"zrange_raster_batch_classes", PCQ_SEGMENTS_RASTER_CLASSES, waves, (int)cells, (int)cells, /*null_refused=*/true};
     b.checks_only = !any;  // both sets empty: every check of the table, then no upload, no launch, the words as they were
     return k1_batch_launch<DevRasterClassSegment>(
-        ctx, b, cols, nsegments, s, admit, fill,
+        ctx, b, cols, nsegments, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
+        [&](DevRasterClassSegment &g, size_t i) { return raster_segment_fill(b.prefix, g, preds[i], cols[i], cell_xy + 2 * i, nx, ny, i); },
         [&](unsigned g, uint64_t steps) {
             hipLaunchKernelGGL((k_bounds_zrange_classes_pipe<K1_TILES>), dim3(g), dim3(64), lds, s,
                                reinterpret_cast<const DevRasterClassSegment *>(ctx->d_segments), (int)nsegments, steps, nx, cells, low, high,

@@ -19,6 +19,11 @@
 // At exit the wave writes two u64 per cell to partials[slice * gridDim.x + blockIdx.x]: slice `cell` the count, slice `cells + cell`
 // the sum; pcq_launch_finish_zsum (scan_count_multi.hip: k_finish_counts per array) adds slice c into device_count[c] and slice
 // cells + c into device_zsum[c], modulo 2^64 as well.
+// This kernel keeps its own text of the pipeline loop, the tile and the leftover loop.  On pipe_scan (scan_tiles.h), a tile shared
+// with the height raster and raster_leftovers (raster_cells.h) it compiled to a kernel structurally equal to this one (equal VGPRs, occupancy,
+// waits, loads, LDS operations and compares) that ran 0.48 % slower (7.531 against 7.495 ms, the parent's spread 0.022) at the largest raster, where
+// the LDS leaves one wave per SIMD, and inside the parent's spread at 8 x 8 cells (profiles/raster_frame_rate.log): outside the rule
+// of that change, so the copy stays.
 #include "pcq_internal.h"
 #include "raster_cells.h"
 #include "raster_div.h"
@@ -28,7 +33,7 @@
 namespace {
 
 // Workgroups (of one wave) per CU: the height raster's rule with twice its LDS per cell — the smaller of this constant and what a
-// CU's LDS holds at the launch's raster size (ZSUM_LDS_PER_CU / (16 nx ny): 5 at PCQ_ZSUM_CELLS_MAX, 20 at 16 x 32), rounded down to
+// CU's LDS holds at the launch's raster size (RASTER_LDS_PER_CU / (16 nx ny): 5 at PCQ_ZSUM_CELLS_MAX, 20 at 16 x 32), rounded down to
 // a multiple of four from four on, so that no SIMD of a CU carries a wave more than another.  Measured (16 files x 163 M points,
 // every point inside the box, generator order, ms by workgroups per CU): 8 x 8 cells: 2: 15.5, 4: 7.8, 8: 7.0, 16: 7.0; 2048 cells:
 // 3: 10.3, 4: 7.5, 5 (the LDS limit): 13.8.  In scan-strip order all 64 lanes of a slot meet one LDS word and the pass takes
@@ -36,7 +41,6 @@ namespace {
 // (profiles/zsum_raster_rate_sweep.log, option zsum_waves_per_cu of the lab library, which takes the value as given up to the LDS
 // limit).
 constexpr int ZSUM_WAVES_PER_CU = 16;
-constexpr uint32_t ZSUM_LDS_PER_CU = 160 * 1024;
 
 // One slot: a point and its z from the lanes in `pass` (uniform) into the two words of their cells.
 __device__ __forceinline__ void zsum_fold(unsigned long long *cnt, unsigned long long *sum, uint64_t pass, uint32_t cell, int z, int lane) {
@@ -159,28 +163,16 @@ extern "C" int pcq_scan_dev_zsum_raster_batch(pcq_ctx *ctx, const pcq_columns *c
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const uint32_t cells = nx * ny;
     const size_t lds = 2 * cells * sizeof(uint64_t);
-    int waves = ZSUM_WAVES_PER_CU;
-    bool whole_simds = true;
-#ifdef PCQ_LAB  // (tools/resident_zsum_rate.py sweeps it; the sweep sees 5 and 6 as they are)
-    if (ctx->zsum_waves_per_cu) waves = ctx->zsum_waves_per_cu, whole_simds = false;
+    int lab_waves = 0;
+#ifdef PCQ_LAB  // (tools/resident_zsum_rate.py sweeps it)
+    lab_waves = ctx->zsum_waves_per_cu;
 #endif
-    const int by_lds = (int)(ZSUM_LDS_PER_CU / lds);  // (>= 5: cells <= PCQ_ZSUM_CELLS_MAX)
-    if (waves > by_lds) waves = by_lds;
-    if (whole_simds && waves > 4) waves &= ~3;
+    const int waves = raster_waves_per_cu(ZSUM_WAVES_PER_CU, lds, lab_waves);
     // (the density raster's table under its kind: the three kernels read it alike)
     const K1Batch b = {"zsum_raster_batch", PCQ_SEGMENTS_RASTER, waves, 2 * (int)cells, 2 * (int)cells, /*null_refused=*/true};
     return k1_batch_launch<DevRasterSegment>(
-        ctx, b, cols, nsegments, s,
-        [&](size_t i) {
-            return preds[i].kind != PCQ_PRED_BOUNDS
-                       ? pcq_fail(PCQ_ERR_ARG, "zsum_raster_batch: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                       : (int)PCQ_OK;
-        },
-        [&](DevRasterSegment &g, size_t i) {
-            const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
-            const uint32_t dim[2] = {nx, ny};
-            return raster_segment_fill("zsum_raster_batch", g, preds[i], cols[i], cw, dim, i);
-        },
+        ctx, b, cols, nsegments, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
+        [&](DevRasterSegment &g, size_t i) { return raster_segment_fill(b.prefix, g, preds[i], cols[i], cell_xy + 2 * i, nx, ny, i); },
         [&](unsigned g, uint64_t steps) {
             hipLaunchKernelGGL((k_bounds_zsum_pipe<K1_TILES>), dim3(g), dim3(64), lds, s, reinterpret_cast<const DevRasterSegment *>(ctx->d_segments),
                                (int)nsegments, steps, nx, cells, ctx->d_partials);

@@ -20,6 +20,11 @@
 //
 // The slots of tile_zsum_classes are tile_zsum's (scan_zsum.hip), spelt out again: that file's kernel is to come out of the compiler
 // as it was (profiles/zsum_classes_asm_compare.log).
+// This kernel keeps its own text of the pipeline loop, the tile and the leftover loop.  On pipe_scan (scan_tiles.h), a tile shared
+// with the height raster and raster_leftovers (raster_cells.h) it compiled to a kernel structurally equal to this one (equal VGPRs, occupancy,
+// waits, loads, LDS operations and compares) that ran 1.2 % and 1.0 % slower (9.747 against 9.634 ms, 10.602 against 10.497; spreads 0.025, 0.030) at the largest raster, where
+// the LDS leaves one wave per SIMD, and inside the parent's spread at 8 x 8 cells (profiles/raster_frame_rate.log): outside the rule
+// of that change, so the copy stays.
 #include "pcq_internal.h"
 #include "raster_cells.h"
 #include "raster_classes.h"
@@ -30,14 +35,13 @@
 namespace {
 
 // Workgroups (of one wave) per CU: the mean-height raster's rule (scan_zsum.hip: ZSUM_WAVES_PER_CU) — the smaller of this constant and
-// what a CU's LDS holds at the launch's raster size (ZSUM_CLASSES_LDS_PER_CU / (256 + 16 nx ny): 4 at PCQ_ZSUM_CELLS_MAX), rounded
+// what a CU's LDS holds at the launch's raster size (RASTER_LDS_PER_CU / (256 + 16 nx ny): 4 at PCQ_ZSUM_CELLS_MAX), rounded
 // down to a multiple of four from four on.  16 is the sweep's winner (profiles/zsum_classes_rate_sweep.log, option
 // zsum_classes_waves_per_cu of the lab library, which takes the value as given up to the LDS limit; 16 files x 163 M points, 45 % of
 // class 2, every point inside the box, generator order, ms for the set {2} / all 256 classes by workgroups per CU): 8 x 8 cells: 3:
 // 13.3 / 13.6, 4: 9.7 / 10.3, 6: 8.0 / 9.2, 8: 6.4 / 8.1, 12: 5.9 / 8.1, 16: 5.9 / 8.0; 2048 cells: 3: 13.2 / 13.2, 4 (the LDS limit):
 // 9.6 / 9.6.  DESIGN.md §4 "How high is the ground in this box" has the rates beside the unfiltered raster's.
 constexpr int ZSUM_CLASSES_WAVES_PER_CU = 16;
-constexpr uint32_t ZSUM_CLASSES_LDS_PER_CU = 160 * 1024;
 
 // One slot: a point and its z from the lanes in `pass` (uniform) into the two words of their cells.
 __device__ __forceinline__ void zsum_classes_fold(unsigned long long *cnt, unsigned long long *sum, uint64_t pass, uint32_t cell, int z, int lane) {
@@ -173,34 +177,19 @@ extern "C" int pcq_scan_dev_zsum_raster_batch_classes(pcq_ctx *ctx, const pcq_co
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const uint32_t cells = nx * ny;
     const size_t lds = CLASS_TABLE_BYTES + 2 * cells * sizeof(uint64_t);
-    int waves = ZSUM_CLASSES_WAVES_PER_CU;
-    bool whole_simds = true;
-#ifdef PCQ_LAB  // (tools/resident_zsum_classes_rate.py sweeps it; the sweep sees 5 and 6 as they are)
-    if (ctx->zsum_classes_waves_per_cu) waves = ctx->zsum_classes_waves_per_cu, whole_simds = false;
+    int lab_waves = 0;
+#ifdef PCQ_LAB  // (tools/resident_zsum_classes_rate.py sweeps it)
+    lab_waves = ctx->zsum_classes_waves_per_cu;
 #endif
-    const int by_lds = (int)(ZSUM_CLASSES_LDS_PER_CU / lds);  // (>= 4: cells <= PCQ_ZSUM_CELLS_MAX, and the table)
-    if (waves > by_lds) waves = by_lds;
-    if (whole_simds && waves > 4) waves &= ~3;
+    const int waves = raster_waves_per_cu(ZSUM_CLASSES_WAVES_PER_CU, lds, lab_waves);
     ClassSet set;
     uint32_t any = 0;
     for (int w = 0; w < 8; w++) any |= (set.w[w] = class_set[w]);
-    const auto admit = [&](size_t i) {
-        return preds[i].kind != PCQ_PRED_BOUNDS
-                   ? pcq_fail(PCQ_ERR_ARG, "zsum_raster_batch_classes: predicate kind %d of segment %zu (PCQ_PRED_BOUNDS only)", preds[i].kind, i)
-                   : (int)PCQ_OK;
-    };
-    const auto fill = [&](DevRasterClassSegment &g, size_t i) {
-        if (cols[i].n && (cols[i].cls_stride != 1 || !cols[i].cls))
-            return pcq_fail(PCQ_ERR_ARG, "zsum_raster_batch_classes: LAST classification blocks only (stride 1, not null), segment %zu", i);
-        const uint32_t cw[2] = {cell_xy[2 * i], cell_xy[2 * i + 1]};
-        const uint32_t dim[2] = {nx, ny};
-        g.cls = (const uint8_t *)cols[i].cls;
-        return raster_segment_fill("zsum_raster_batch_classes", g, preds[i], cols[i], cw, dim, i);
-    };
     K1Batch b = {"zsum_raster_batch_classes", PCQ_SEGMENTS_RASTER_CLASSES, waves, 2 * (int)cells, 2 * (int)cells, /*null_refused=*/true};
     b.checks_only = !any;  // the empty set: every check of the table, then no upload, no launch, the words as they were
     return k1_batch_launch<DevRasterClassSegment>(
-        ctx, b, cols, nsegments, s, admit, fill,
+        ctx, b, cols, nsegments, s, [&](size_t i) { return admit_bounds_only(b.prefix, preds[i], i); },
+        [&](DevRasterClassSegment &g, size_t i) { return raster_segment_fill(b.prefix, g, preds[i], cols[i], cell_xy + 2 * i, nx, ny, i); },
         [&](unsigned g, uint64_t steps) {
             hipLaunchKernelGGL((k_bounds_zsum_classes_pipe<K1_TILES>), dim3(g), dim3(64), lds, s,
                                reinterpret_cast<const DevRasterClassSegment *>(ctx->d_segments), (int)nsegments, steps, nx, cells, set, ctx->d_partials);
